@@ -16,6 +16,13 @@ scaling: 10k trajectories per GPU.
 
     python bench.py                       # N=1, C2 (configs[1]): 10k x 600 pts @1 Hz
     python bench.py --gpus 8              # self-launches 8 ranks (or run under torch.distributed.run)
+    python bench.py --full                # also the CPU baseline, rooflines, turn costs, service lines
+    python bench.py --dump-outputs DIR    # the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times --steps steps and prints the result line; every other
+measurement (CPU baseline, all-reduce and matching alone, concurrent parts, per-stage
+rooflines, the workload with turn costs, C1 latency, JSON boundary, service throughput) runs
+only with --full.
 
 Prints ONE JSON line (rank 0).  No PyTorch is loaded: RCCL is bound natively
 by libreporter_match.so and ranks rendezvous through a node-local file.
@@ -54,7 +61,7 @@ def parse():
     ap.add_argument("--streams", type=int, default=1,
                     help="the batch runs as this many concurrent parts, one HIP stream each (1 = one stream)")
     ap.add_argument("--parts-extra", type=int, default=2,
-                    help="also time the batch as this many concurrent parts (engine.MultiMatcher), reported "
+                    help="with --full: also time the batch as this many concurrent parts (engine.MultiMatcher), reported "
                          "beside the value as concurrent_parts (0 = skip; batches <= 20 M points)")
     ap.add_argument("--exchange", choices=("allreduce", "reduce_scatter"), default="allreduce",
                     help="allreduce: every rank ends with the whole histogram and duration sums; reduce_scatter: "
@@ -63,14 +70,23 @@ def parse():
                     help="rccl: one rank per GPU over xGMI (the measured configuration); host: the same "
                          "collectives over TCP on the host (rm_comm_init_host), ranks may share a GPU -- a "
                          "functional run of the multi-rank path on fewer GPUs, not a scaling measurement")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C1 latency and JSON-boundary lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure, also measure everything else: the CPU baseline, the all-reduce "
+                         "and the matching alone, the concurrent parts, the per-stage rooflines, the C2 workload with "
+                         "turn costs, and the C1 latency / JSON-boundary / service lines (a plain run sets up, warms "
+                         "up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0's histogram, "
+                         "duration sums, segments and reports) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the turn-cost, C1 latency, JSON-boundary and service lines")
     ap.add_argument("--json-traces", type=int, default=10000, help="traces sent through rm_match_batch as JSON")
     ap.add_argument("--ball-radius", type=float, default=None,
                     help="route-ball radius in m (default: the config's, else the engine's automatic radius)")
     ap.add_argument("--turn-penalty", type=float, default=0.0,
                     help="turn_penalty_factor of every trace (meili's stock auto default is 200; DESIGN.md rule 3b); "
-                         "the default C2 run also measures the workload at 200 beside the value (turn_costs)")
+                         "a --full C2 run also measures the workload at 200 beside the value (turn_costs)")
     ap.add_argument("--traffic-json", default=None,
                     help="rocprofv3 PMC summary giving HBM bytes per stage launch (scripts/pmc_summary.py; default "
                          "profiles/r03/pmc_routes_<config>.json; used only when it was measured on this engine.hip "
@@ -431,6 +447,126 @@ def extras(gpath, tr, json_traces, tmpdir):
     return out
 
 
+def stage_rooflines(a, mo, eng, counts, balls, tiers, ms, n_per):
+    """(K2 roofline, per-stage rooflines) of the --full run: `counts` from the CPU baseline leg,
+    `ms` the per-stage launch ms per step."""
+    ball_tier = balls["radius_m"] > 0 and balls["keys"] > 0
+    # bytes of the formulation the launch runs: route-ball probes (every item answered by
+    # the tables when nothing was handed over), else the bounded searches
+    if counts and ball_tier and tiers["ball_to_search"] == 0 and a.turn_penalty > 0:
+        abytes = mo.routes_ball_turn_algorithmic_bytes(counts)
+        formulation = "route-ball table probes + turn rows (turn_penalty_factor %g)" % a.turn_penalty
+    elif counts and ball_tier and tiers["ball_to_search"] == 0:
+        abytes, formulation = mo.routes_ball_algorithmic_bytes(counts), "route-ball table probes"
+    elif counts and "settled_to_targets" in counts:
+        abytes = mo.routes_targets_algorithmic_bytes(counts)
+        formulation = "bounded searches stopped at their targets (label-setting order)"
+    elif counts:
+        abytes, formulation = mo.routes_algorithmic_bytes(counts), "bounded searches"
+    else:
+        abytes, formulation = None, None
+    tpath = a.traffic_json
+    if not tpath:   # the newest PMC summary of this workload (sha-checked by load_traffic)
+        for rnd in ("r06", "r05", "r04"):
+            tpath = os.path.join(ROOT, "profiles", rnd, "pmc_routes_%s%s.json" % (
+                a.config.lower(), "_turn%g" % a.turn_penalty if a.turn_penalty > 0 else ""))
+            if os.path.exists(tpath):
+                break
+    traffic, traffic_note = load_traffic(tpath, a.config, n_per, max(1, a.streams), a.turn_penalty)
+    tr_of = lambda st: (traffic.get(st) or {}).get("hbm_bytes_per_launch")
+    va_of = lambda st: (traffic.get(st) or {}).get("valu_instrs")
+    k2 = roofline("K2", "K2 route stage: k_src_items + k_routes_ball2 + search tiers for hand-overs", abytes,
+                  ms["routes"], formulation, tr_of("routes"), va_of("routes"))
+    k2["l2_hit_rate"] = (traffic.get("routes") or {}).get("l2_hit_rate")
+    k2["traffic_source"] = traffic_note
+    k2.update({"search_equivalent_bytes_per_launch": mo.routes_algorithmic_bytes(counts) if counts else None,
+               "counts": counts, "route_tiers": tiers, "route_balls": balls, "k1_grid_split": eng.grid_split()})
+    rooflines = {
+        "K1": roofline("K1", "k_candidates_lane + k_candidates_wave", mo.candidates_algorithmic_bytes(counts)
+                       if counts else None, ms["candidates"], "cell-major 32 B records on the engine grid (file cells "
+                       "split %dx%d; items counted by the oracle on that grid), per-road minima in registers"
+                       % (eng.grid_split(), eng.grid_split()), tr_of("candidates"), va_of("candidates")),
+        "K2": {k: k2.get(k) for k in ("kernel", "achieved", "frac", "algorithmic_bytes_per_launch", "avg_launch_ms",
+                                      "traffic", "dram_frac", "valu_frac")},
+        "K3": roofline("K3", "k_viterbi", mo.viterbi_algorithmic_bytes(counts) if counts else None, ms["viterbi"],
+                       "u32 routes + f32 emissions, fp64 costs in registers", tr_of("viterbi"), va_of("viterbi")),
+        "paths": roofline("paths", "path stage: k_paths_ball + search tiers for hand-overs",
+                          mo.paths_algorithmic_bytes(counts) if counts and "path_rows" in counts else None,
+                          ms["paths"], "route-ball labels, walk back by canonical predecessors over "
+                          "self-contained in-edge records", tr_of("paths"), va_of("paths")),
+        "K4": roofline("K4", "segments stage: trav_off scan + k_rec_slot + k_seg_wave",
+                       mo.segments_algorithmic_bytes(counts) if counts else None, ms["segments"],
+                       "wave per trace, 64 traversal records per step in registers, runs by ballot/scan",
+                       tr_of("segments"), va_of("segments")),
+    }
+    return k2, rooflines
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # of all the --dump-outputs arrays together (the limit is 64 MB)
+DUMP_SEED = 20240607
+
+
+def _dump_rows(arr, max_bytes, rng):
+    """arr as float64 rows, or a seeded sample of its rows (in order) when it exceeds max_bytes;
+    returns (rows, their indices or None)."""
+    import numpy as np
+    arr = np.ascontiguousarray(arr, np.float64)
+    row_bytes = max(1, arr[0].nbytes) if len(arr) else 1
+    keep = max_bytes // row_bytes
+    if len(arr) <= keep:
+        return arr, None
+    idx = np.sort(rng.choice(len(arr), int(keep), replace=False))
+    return arr[idx], idx
+
+
+def _fields_f64(rec, names):
+    import numpy as np
+    out = np.empty((len(rec), len(names)), np.float64)
+    for j, nm in enumerate(names):
+        out[:, j] = rec[nm]
+    return out
+
+
+def dump_outputs(ddir, bm, hist, dur):
+    """--dump-outputs: what a caller of the timed step receives, as float64 DIR/<name>.npy --
+    the 16-bin speed histogram and the duration sum per segment (after the exchange), and this
+    rank's matched segments, reports and per-trace statistics with their per-trace offsets
+    (columns in the field order of engine.SEGMENT_DTYPE / REPORT_DTYPE / STATS_DTYPE; every
+    field is exact in float64).  An array over its share of the byte budget is written as a
+    seeded sample of its rows, with the rows' indices in <name>_rows.npy."""
+    import numpy as np
+    from reporter_amd import engine
+    os.makedirs(ddir, exist_ok=True)
+    bms = bm.bms if isinstance(bm, engine.MultiMatcher) else [bm]
+    seg_off, segs, rep_off, reps, stats = [np.zeros(1, np.uint64)], [], [np.zeros(1, np.uint64)], [], []
+    for b in bms:   # concurrent parts are contiguous trace ranges: offsets continue, records append
+        so, sg = b.segments()
+        ro, rp, st = b.reports()
+        seg_off.append(so[1:].astype(np.uint64) + seg_off[-1][-1])
+        rep_off.append(ro[1:].astype(np.uint64) + rep_off[-1][-1])
+        segs.append(_fields_f64(sg, engine.SEGMENT_DTYPE.names))
+        reps.append(_fields_f64(rp, [n for n in engine.REPORT_DTYPE.names if n != "pad"]))
+        stats.append(_fields_f64(st, engine.STATS_DTYPE.names))
+    arrays = {"histogram": np.asarray(hist).reshape(-1, 16), "duration_sum": np.asarray(dur).reshape(-1, 1),
+              "segment_offsets": np.concatenate(seg_off).reshape(-1, 1), "segments": np.concatenate(segs),
+              "report_offsets": np.concatenate(rep_off).reshape(-1, 1), "reports": np.concatenate(reps),
+              "trace_stats": np.concatenate(stats)}
+    rng = np.random.default_rng(DUMP_SEED)
+    left = DUMP_BUDGET_BYTES
+    names = sorted(arrays, key=lambda n: (arrays[n].size, n))   # smallest first: what they spare goes to the rest
+    for k, name in enumerate(names):
+        arr = arrays[name]
+        share = left // (len(names) - k)
+        # a sampled array also writes one float64 row index per row
+        rows, idx = _dump_rows(arr, share if arr.size * 8 <= share else share * arr.shape[1] // (arr.shape[1] + 1), rng)
+        left -= rows.nbytes + (idx.size * 8 if idx is not None else 0)
+        np.save(os.path.join(ddir, name + ".npy"), rows if rows.shape[1:] != (1,) else rows[:, 0])
+        if idx is not None:
+            np.save(os.path.join(ddir, name + "_rows.npy"), idx.astype(np.float64))
+        elif os.path.exists(os.path.join(ddir, name + "_rows.npy")):   # left by an earlier, sampled dump
+            os.remove(os.path.join(ddir, name + "_rows.npy"))
+
+
 def main():
     a = parse()
     if a.gpus > 1 and "RANK" not in os.environ:
@@ -484,7 +620,7 @@ def main():
 
     # CPU leg first, before this process touches the GPU (forked workers never inherit a HIP context)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         procs = a.cpu_procs or min(16, os.cpu_count() or 1)
         cpu = cpu_baseline_leg(gpath, tr, cfg["search_radius"], procs, opts_all, trace_opt)
 
@@ -553,13 +689,18 @@ def main():
     elapsed = timed(step, a.steps, comm, sync)
     kt_live = bm.kernel_times()
     bm.set_timing(False)
-    t_ar = timed(allreduce, a.steps, comm, sync)             # the all-reduce alone, reported alongside
-    t_match = timed(lambda: bm.rerun(**rp), a.steps, comm, sync)   # matching alone
+    # what the last timed step left: the exchanged histogram and duration sums, and rank 0's
+    # segments and reports
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, bm, hist.download(), dur.download(np.uint64))
+    t_ar, t_match, conc, t_staged, kt = None, None, None, None, {"routes": kt_live["routes"]}
+    if a.full:
+        t_ar = timed(allreduce, a.steps, comm, sync)             # the all-reduce alone, reported alongside
+        t_match = timed(lambda: bm.rerun(**rp), a.steps, comm, sync)   # matching alone
     # the same batch as concurrent parts, one HIP stream each (rm_runners_rerun): gather-bound
     # stages of one part overlap issue-bound stages of another; reported beside the value (the
     # parts share the GPU, so their per-launch K2 roofline is not the kernel's)
-    conc = None
-    if a.parts_extra > 1 and a.streams == 1 and P <= 20_000_000:
+    if a.full and a.parts_extra > 1 and a.streams == 1 and P <= 20_000_000:
         mm = engine.MultiMatcher(eng, a.parts_extra)
         mm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts, trace_opt, **rp)
         for _ in range(a.warmup):
@@ -572,16 +713,18 @@ def main():
                         "balanced by points, run concurrently on their own HIP streams (engine.MultiMatcher / "
                         "rm_runners_rerun); bit-identical results (tests/test_gpu_multistream.py)"}
         mm.close()
-    # per-stage breakdown (the other rooflines): a separate pass with every stage timed
-    bm.set_timing(True)
-    bm.reset_times()
-    t_staged = timed(lambda: bm.rerun(**rp), a.steps, comm, sync)
-    kt = bm.kernel_times()
-    bm.set_timing(False)
-    kt["routes"] = kt_live["routes"]
+    if a.full:
+        # per-stage breakdown (the other rooflines): a separate pass with every stage timed
+        bm.set_timing(True)
+        bm.reset_times()
+        t_staged = timed(lambda: bm.rerun(**rp), a.steps, comm, sync)
+        kt = bm.kernel_times()
+        bm.set_timing(False)
+        kt["routes"] = kt_live["routes"]
     total_points = comm.allreduce_host(P, dist.SUM) if comm is not None else P
     sizes = bm.sizes()
-    step()   # one more exchanged step: the totals below are of the reduced arrays
+    if a.full:
+        step()   # one more exchanged step: the totals below are of the reduced arrays
     hist_sum = int(hist.download().sum())
     dur_sum = int(dur.download(np.uint64).sum())
     if rs and comm is not None:   # each rank holds its range: the totals are the sums of the ranges
@@ -593,7 +736,7 @@ def main():
     # the C2 workload with meili's stock auto turn costs (200, rule 3b), beside the value: the same
     # points re-run with the factor on every trace, K2 timed live as in the official step
     turn = None
-    if a.config == "C2" and world == 1 and a.turn_penalty == 0 and a.streams == 1 and not a.no_extras:
+    if a.full and a.config == "C2" and world == 1 and a.turn_penalty == 0 and a.streams == 1 and not a.no_extras:
         topts = engine.default_options(1, search_radius=cfg["search_radius"], turn_penalty_factor=200.0)
         bm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], topts, None, **rp)
         for _ in range(a.warmup):
@@ -616,55 +759,9 @@ def main():
         steps = max(a.steps, 1)
         ms = {k: v[0] / steps for k, v in kt.items()}
         counts = cpu["counts"] if cpu else {}
-        ball_tier = balls["radius_m"] > 0 and balls["keys"] > 0
-        # bytes of the formulation the launch runs: route-ball probes (every item answered by
-        # the tables when nothing was handed over), else the bounded searches
-        if counts and ball_tier and tiers["ball_to_search"] == 0 and a.turn_penalty > 0:
-            abytes = mo.routes_ball_turn_algorithmic_bytes(counts)
-            formulation = "route-ball table probes + turn rows (turn_penalty_factor %g)" % a.turn_penalty
-        elif counts and ball_tier and tiers["ball_to_search"] == 0:
-            abytes, formulation = mo.routes_ball_algorithmic_bytes(counts), "route-ball table probes"
-        elif counts and "settled_to_targets" in counts:
-            abytes = mo.routes_targets_algorithmic_bytes(counts)
-            formulation = "bounded searches stopped at their targets (label-setting order)"
-        elif counts:
-            abytes, formulation = mo.routes_algorithmic_bytes(counts), "bounded searches"
-        else:
-            abytes, formulation = None, None
-        tpath = a.traffic_json
-        if not tpath:   # the newest round's PMC summary of this workload (sha-checked by load_traffic)
-            for rnd in ("r06", "r05", "r04"):
-                tpath = os.path.join(ROOT, "profiles", rnd, "pmc_routes_%s%s.json" % (
-                    a.config.lower(), "_turn%g" % a.turn_penalty if a.turn_penalty > 0 else ""))
-                if os.path.exists(tpath):
-                    break
-        traffic, traffic_note = load_traffic(tpath, a.config, n_per, max(1, a.streams), a.turn_penalty)
-        tr_of = lambda st: (traffic.get(st) or {}).get("hbm_bytes_per_launch")
-        va_of = lambda st: (traffic.get(st) or {}).get("valu_instrs")
-        k2 = roofline("K2", "K2 route stage: k_src_items + k_routes_ball2 + search tiers for hand-overs", abytes,
-                      ms["routes"], formulation, tr_of("routes"), va_of("routes"))
-        k2["l2_hit_rate"] = (traffic.get("routes") or {}).get("l2_hit_rate")
-        k2["traffic_source"] = traffic_note
-        k2.update({"search_equivalent_bytes_per_launch": mo.routes_algorithmic_bytes(counts) if counts else None,
-                   "counts": counts, "route_tiers": tiers, "route_balls": balls, "k1_grid_split": eng.grid_split()})
-        rooflines = {
-            "K1": roofline("K1", "k_candidates_lane + k_candidates_wave", mo.candidates_algorithmic_bytes(counts)
-                           if counts else None, ms["candidates"], "cell-major 32 B records on the engine grid (file cells split "
-                           "%dx%d; items counted by the oracle on that grid), per-road minima in registers"
-                           % (eng.grid_split(), eng.grid_split()), tr_of("candidates"), va_of("candidates")),
-            "K2": {k: k2.get(k) for k in ("kernel", "achieved", "frac", "algorithmic_bytes_per_launch", "avg_launch_ms",
-                                      "traffic", "dram_frac", "valu_frac")},
-            "K3": roofline("K3", "k_viterbi", mo.viterbi_algorithmic_bytes(counts) if counts else None, ms["viterbi"],
-                           "u32 routes + f32 emissions, fp64 costs in registers", tr_of("viterbi"), va_of("viterbi")),
-            "paths": roofline("paths", "path stage: k_paths_ball + search tiers for hand-overs",
-                              mo.paths_algorithmic_bytes(counts) if counts and "path_rows" in counts else None,
-                              ms["paths"], "route-ball labels, walk back by canonical predecessors over "
-                              "self-contained in-edge records", tr_of("paths"), va_of("paths")),
-            "K4": roofline("K4", "segments stage: trav_off scan + k_rec_slot + k_seg_wave",
-                           mo.segments_algorithmic_bytes(counts) if counts else None, ms["segments"],
-                           "wave per trace, 64 traversal records per step in registers, runs by ballot/scan",
-                           tr_of("segments"), va_of("segments")),
-        }
+        k2, rooflines = None, None
+        if a.full:
+            k2, rooflines = stage_rooflines(a, mo, eng, counts, balls, tiers, ms, n_per)
         step_ms = elapsed / steps * 1e3
         build_ms = balls["build_ms"]
         out = {
@@ -699,28 +796,34 @@ def main():
                                "stream each" % (world, "host-transport (TCP)" if a.comm == "host" else "RCCL", nseg,
                                                 max(1, a.streams)),
             },
-            "ms_allreduce": t_ar / steps * 1e3,
+            "full": a.full,
             "allreduce_bytes": nseg * 16 * 4 + nseg * 8,
             "exchange": a.exchange,
-            "ms_matching_only": t_match / steps * 1e3,
-            "value_matching_only": total_points * a.steps / t_match,
-            "roofline": k2,
-            "rooflines": rooflines,
             "cold_start": {"graph_upload_and_first_run_s": cold_s, "route_ball_build_ms": build_ms,
                            "ball_build_in_steps": build_ms / step_ms,
                            "value_over_first_hour_incl_ball_build": total_points / (step_ms * 1e-3) *
                            max(0.0, 3600.0 - build_ms * 1e-3) / 3600.0,
                            "note": "the route balls are built once per graph and travel mode (host, at rm_configure); "
                                    "they are outside the timed step"},
-            "concurrent_parts": conc,
             "kernels_ms_per_step": ms,
-            "kernels_ms_note": ("summed launch ms of each stage per step over the %d part(s); routes timed live in the "
-                                "official step, the other stages in a separate pass with every stage timed (%.3f ms "
-                                "per step)" % (max(1, a.streams), t_staged / steps * 1e3)),
+            "kernels_ms_note": "summed launch ms of the routes stage per step over the %d part(s), timed live in the "
+                               "official step; --full times the other stages too" % max(1, a.streams),
             "sizes_rank0": sizes,
             "histogram_total": hist_sum,
             "duration_sum_total_s": dur_sum,
         }
+        if a.full:
+            out.update({
+                "ms_allreduce": t_ar / steps * 1e3,
+                "ms_matching_only": t_match / steps * 1e3,
+                "value_matching_only": total_points * a.steps / t_match,
+                "roofline": k2,
+                "rooflines": rooflines,
+                "concurrent_parts": conc,
+                "kernels_ms_note": ("summed launch ms of each stage per step over the %d part(s); routes timed live in "
+                                    "the official step, the other stages in a separate pass with every stage timed "
+                                    "(%.3f ms per step)" % (max(1, a.streams), t_staged / steps * 1e3)),
+            })
         if turn is not None:
             ttraffic, tnote = {}, None
             for rnd in ("r06", "r05"):
@@ -760,7 +863,7 @@ def main():
     dur.close()
     bm.close()
     eng.close()
-    if rank == 0 and world == 1 and not a.no_extras and a.config == "C2":
+    if a.full and rank == 0 and world == 1 and not a.no_extras and a.config == "C2":
         out.update(extras(gpath, tr, a.json_traces, gdir))
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -8,7 +8,7 @@ CFG=$1; TR=$2; TAG=$3; shift 3
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
-ARGS="--config $CFG --traces $TR --no-extras --parts-extra 0 $*"
+ARGS="--full --config $CFG --traces $TR --no-extras --parts-extra 0 $*"
 cd /tmp
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_kt -o run -- python3 $R/bench.py $ARGS --steps 5 --warmup 1 --no-cpu-baseline > $O/prof_kt.log 2>&1 || { echo "$TAG kt failed"; tail -5 $O/prof_kt.log; exit 1; }
 echo "$TAG kt done"

@@ -13,5 +13,5 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
 fi
 bash scripts/gpu_pmc_cfg.sh C2 10000 r05_c2 || exit 1
 cd $R
-timeout -k 10 900 python -u bench.py > $O/bench_c2_default.json 2> $O/bench_c2_default.err || { echo "bench failed"; tail -20 $O/bench_c2_default.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_c2_default.json 2> $O/bench_c2_default.err || { echo "bench failed"; tail -20 $O/bench_c2_default.err; exit 1; }
 echo FINALDONE

@@ -12,9 +12,10 @@ if [ "$1" = pmc ]; then
   done
 else
   mkdir -p $R/gpurun_out/r06_cfgs
+  O=$_   # the folder just made
   for c in ${CFGS:-C3 C4 C5 CITY}; do
     lc=$(echo $c | tr A-Z a-z)
-    timeout -k 10 600 python -u bench.py --config $c --no-extras > $R/gpurun_out/r06_cfgs/bench_${lc}_n1.json 2> $R/gpurun_out/r06_cfgs/bench_${lc}_n1.err || { echo "bench $c failed"; tail -20 $R/gpurun_out/r06_cfgs/bench_${lc}_n1.err; exit 1; }
+    timeout -k 10 600 python -u bench.py --full --config $c --no-extras > $O/bench_${lc}_n1.json 2> $O/bench_${lc}_n1.err || { echo "bench $c failed"; tail -20 $O/bench_${lc}_n1.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$R/gpurun_out/r06_cfgs/bench_${lc}_n1.json'))
 print('$c', round(d['value']/1e6,1), 'M points/s', round(d['ms_per_step'],2), 'ms/step', 'K2', round(d['roofline']['avg_launch_ms'],3), 'frac', d['roofline']['frac'])"

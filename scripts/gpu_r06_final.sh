@@ -16,7 +16,7 @@ cp $R/gpurun_out/r06_c2/summary/pmc_r06_c2.json $R/profiles/r06/pmc_routes_c2.js
 TURN=200 bash scripts/gpu_pmc_cfg.sh C2 10000 r06_c2_turn200 --turn-penalty 200 || exit 1
 cp $R/gpurun_out/r06_c2_turn200/summary/pmc_r06_c2_turn200.json $R/profiles/r06/pmc_routes_c2_turn200.json
 cd $R
-timeout -k 10 900 python -u bench.py > $O/bench_c2_default.json 2> $O/bench_c2_default.err || { echo "bench failed"; tail -20 $O/bench_c2_default.err; exit 1; }
+timeout -k 10 900 python -u bench.py --full > $O/bench_c2_default.json 2> $O/bench_c2_default.err || { echo "bench failed"; tail -20 $O/bench_c2_default.err; exit 1; }
 python - <<PY
 import json; d = json.load(open("$O/bench_c2_default.json"))
 r = d["roofline"]; t = d.get("turn_costs") or {}

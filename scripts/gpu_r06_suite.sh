@@ -8,7 +8,7 @@ cd $R
 timeout -k 10 800 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $O/pytest_gpu.txt 2>&1 || { echo "tests failed"; tail -30 $O/pytest_gpu.txt; exit 1; }
 tail -2 $O/pytest_gpu.txt
 if [ "${BENCH:-1}" = 1 ]; then
-  timeout -k 10 300 python -u bench.py > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
+  timeout -k 10 300 python -u bench.py --full > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -20 $O/bench.err; exit 1; }
   python - <<PY
 import json; d = json.load(open("$O/bench.json"))
 print("value %.1f M  step %.3f ms  K2 %.3f ms frac %.3f" % (d["value"] / 1e6, d["ms_per_step"], d["roofline"]["avg_launch_ms"], d["roofline"]["frac"]))

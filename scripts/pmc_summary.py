@@ -40,7 +40,7 @@ def main():
     ap.add_argument("--streams", type=int, default=2, help="concurrent parts the profiled bench ran (bench --streams)")
     ap.add_argument("--turn-penalty", type=float, default=0.0, help="turn_penalty_factor of the profiled bench")
     ap.add_argument("--tag", default=None, help="output pmc_<tag>.json instead of pmc_routes_<config>.json")
-    ap.add_argument("--what", default="python bench.py --steps 10 --warmup 2 --no-cpu-baseline",
+    ap.add_argument("--what", default="python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline",
                     help="the profiled command, for the kernel-stats title")
     a = ap.parse_args()
     os.makedirs(a.out, exist_ok=True)

@@ -51,6 +51,19 @@ int rm_match_batch(rm_matcher* m, const char* const* traces, size_t n, char** ou
  * (*buf)[off[i], off[i+1]) (off: n+1 entries, caller-allocated).  One allocation and one free
  * (rm_free(*buf)) instead of n: the Python binding reads the replies out of one memoryview. */
 int rm_match_batch_packed(rm_matcher* m, const char* const* traces, size_t n, char** buf, uint64_t* off);
+/* Matched points (DESIGN.md §3 rule 9): where every GPS point of the request ended up on the road,
+ * the points the interpolation rule dropped between two states included.  Same request JSON as
+ * rm_match; the reply is {"segments":[...],"matched_points":[...]} with the segments of rm_match
+ * for that request, byte for byte, and one entry per input point, in input order:
+ *   {"lat","lon","type":"matched"|"interpolated","edge_id","way_id","distance_along_edge",
+ *    "distance_from_trace_point"}   or   {"lat","lon","type":"unmatched"} (the input position)
+ * lat / lon: the snapped position; edge_id: the directed edge; distance_along_edge: the fraction
+ * of that edge behind the position (offset / length, as Valhalla's trace_attributes reports it);
+ * distance_from_trace_point: metres from the measurement to the snapped position.  Both calls
+ * run their requests as one uncoalesced batch (they never enter the coalescer); any failing trace
+ * fails the call, naming the trace.  Replies are released with rm_free. */
+int rm_match_points(rm_matcher* m, const char* trace_json, char** out_json);
+int rm_match_points_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs);
 void rm_free(char* p);
 /* Host wall times (ms) of the matcher's last uncoalesced rm_match_batch: out[0] JSON parse
  * (single pass, up to 16 host threads), [1] staging into pinned host arrays, [2] engine run
@@ -261,6 +274,21 @@ int rm_runner_get_routes(rm_runner* r, uint32_t* trans_off, double* gc, uint32_t
 int rm_runner_get_route_terms(rm_runner* r, double* route_d, int* present);
 int rm_runner_get_viterbi(rm_runner* r, int8_t* choice, uint8_t* chain_start);
 int rm_runner_get_paths(rm_runner* r, uint32_t* path_off, uint32_t* path_cnt, uint32_t* path_edges, uint32_t* route_dist);
+/* Matched points of the last run / rerun (DESIGN.md §3 rule 9): one 32-byte record per input
+ * point, in batch point order (index trace_off[k] + q; n_points of rm_runner_sizes).  The stage
+ * runs on this call, over what the run left in HBM (kernel id "points"); a run launches nothing
+ * for it.  type 0 records (no chosen candidate at or before the point on its chain, or a trace
+ * that failed under isolation) hold zeros except edge = 0xFFFFFFFF. */
+typedef struct {
+  float lon, lat;      /* snapped position */
+  float sq;            /* squared distance in m^2 from the measurement to it (K1's local frame at the point) */
+  uint32_t edge;       /* directed edge id, 0xFFFFFFFF when unmatched */
+  uint32_t off_cm;     /* offset from the start of that directed edge */
+  uint32_t way;        /* way id of the edge */
+  uint32_t type;       /* 0 unmatched, 1 matched (a state with a chosen candidate), 2 interpolated */
+  uint32_t route_cm;   /* distance along the transition's route from the previous state; 0 for type 1 */
+} rm_matched_point;
+int rm_runner_get_matched_points(rm_runner* r, rm_matched_point* out);
 /* segments: 56-byte records (rm::SegmentRec); seg_off has n_traces+1 entries */
 int rm_runner_get_segments(rm_runner* r, uint32_t* seg_off, void* segs);
 /* reports: 48-byte records (rm::ReportRec); stats: 40-byte rm::ReportStats per trace */

@@ -70,6 +70,11 @@ class RmReportDesc(C.Structure):
                 ("transition_mask", C.c_void_p)]
 
 
+class RmMatchedPoint(C.Structure):
+    _fields_ = [("lon", C.c_float), ("lat", C.c_float), ("sq", C.c_float), ("edge", C.c_uint32),
+                ("off_cm", C.c_uint32), ("way", C.c_uint32), ("type", C.c_uint32), ("route_cm", C.c_uint32)]
+
+
 class RmTileParams(C.Structure):
     _fields_ = [("quantisation", C.c_uint32), ("privacy", C.c_uint32), ("source", C.c_char_p), ("mode", C.c_char_p)]
 
@@ -89,6 +94,8 @@ PROTOTYPES = [
     ("rm_match", C.c_int, [P, C.c_char_p, C.POINTER(P)]),
     ("rm_match_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P)]),
     ("rm_match_batch_packed", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P), C.POINTER(C.c_uint64)]),
+    ("rm_match_points", C.c_int, [P, C.c_char_p, C.POINTER(P)]),
+    ("rm_match_points_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P)]),
     ("rm_free", None, [P]),
     ("rm_matcher_timing", C.c_int, [P, P]),
     ("rm_coalesce_stats", C.c_int, [C.POINTER(C.c_uint64)]),
@@ -134,6 +141,7 @@ PROTOTYPES = [
     ("rm_runner_get_route_terms", C.c_int, [P, P, P]),
     ("rm_runner_get_viterbi", C.c_int, [P, P, P]),
     ("rm_runner_get_paths", C.c_int, [P, P, P, P, P]),
+    ("rm_runner_get_matched_points", C.c_int, [P, P]),
     ("rm_runner_get_segments", C.c_int, [P, P, P]),
     ("rm_runner_get_reports", C.c_int, [P, P, P, P]),
     ("rm_runner_set_timing", C.c_int, [P, C.c_int]),

@@ -524,7 +524,16 @@ struct PackedOut {
   uint64_t* off;
 };
 
-void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** outs, const PackedOut* pk = nullptr) {
+// the request's points of a batch whose replies also carry matched_points (rm_match_points*):
+// trace i's points are lon / lat [off[i], off[i+1])
+struct PointsIn {
+  const float* lon;
+  const float* lat;
+  const uint32_t* off;
+};
+
+void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** outs, const PackedOut* pk = nullptr,
+                       const PointsIn* pin = nullptr) {
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   std::vector<uint32_t> terr(n, 0u);
@@ -535,6 +544,11 @@ void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** o
   std::vector<uint32_t> soff;
   std::vector<SegmentRec> segs;
   mt.get_segments(soff, segs);
+  std::vector<MatchedPoint> mp;
+  if (pin) {   // the matched-points stage runs here, on request, over what the run left in HBM
+    mp.resize(pin->off[n]);
+    mt.matched_points(mp.data());
+  }
   m->ms[3] = ms_since(t3);
   const auto t4 = clk::now();
   if (pk) {   // each thread formats its range into one string, then they are copied into one buffer
@@ -565,6 +579,12 @@ void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** o
       std::string js;
       for (size_t i = a; i < b; ++i) {
         tj::format_segments(segs.data() + soff[i], soff[i + 1] - soff[i], js);
+        if (pin) {
+          const std::vector<EdgeRec>& edges = mt.engine().host().edges;
+          const uint32_t o = pin->off[i];
+          tj::append_matched_points(mp.data() + o, pin->off[i + 1] - o, pin->lon + o, pin->lat + o,
+                                    [&](uint32_t e) { return edges[e].len_cm; }, js);
+        }
         outs[i] = dup_string(js);
       }
     });
@@ -722,9 +742,11 @@ bool json_device_enabled() {
 // requests into its own point arrays, copies them into the matcher's pinned staging at their
 // batch offsets, and after the engine's run formats its range's replies straight into the
 // caller's output strings.  Any failing trace fails the call, naming the trace.
+// points: the replies also carry matched_points (rm_match_points*); the requests are then parsed
+// on the host, whose staging keeps the input points an unmatched entry reports.
 void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs,
-                      const PackedOut* pk = nullptr) {
-  if (n && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk)) return;
+                      const PackedOut* pk = nullptr, bool points = false) {
+  if (n && !points && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk)) return;
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   const auto t0 = clk::now();
@@ -784,7 +806,8 @@ void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char**
   mt.set_isolation(true);
   mt.run(hb, rp);
   m->ms[2] = ms_since(t2);
-  finish_json_batch(m, mt, n, nt, outs, pk);
+  const PointsIn pin{hs.lon, hs.lat, off.data()};
+  finish_json_batch(m, mt, n, nt, outs, pk, points ? &pin : nullptr);
   m->ms[5] = ms_since(t0);
 }
 
@@ -972,6 +995,28 @@ int rm_match_batch_packed(rm_matcher* m, const char* const* traces, size_t n, ch
     const PackedOut pk{buf, off};
     match_json_batch(m, traces, n, nullptr, &pk);   // any failing trace fails the call, naming the trace
   });
+}
+
+int rm_match_points_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("matcher is NULL");
+    for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    if (n == 0) return;
+    for (size_t i = 0; i < n; ++i)
+      if (!traces[i]) throw std::runtime_error("trace string is NULL");
+    try {
+      match_json_batch(m, traces, n, outs, nullptr, true);   // uncoalesced, whatever n is
+    } catch (...) {
+      for (size_t i = 0; i < n; ++i) { std::free(outs[i]); outs[i] = nullptr; }
+      throw;
+    }
+  });
+}
+
+int rm_match_points(rm_matcher* m, const char* trace_json, char** out_json) {
+  if (!out_json) return fail("out_json is NULL");
+  *out_json = nullptr;
+  return rm_match_points_batch(m, &trace_json, 1, out_json);
 }
 
 int rm_match(rm_matcher* m, const char* trace_json, char** out_json) {
@@ -1344,6 +1389,10 @@ int rm_runner_get_route_terms(rm_runner* r, double* a, int* present) {
 int rm_runner_get_viterbi(rm_runner* r, int8_t* a, uint8_t* b) { return guarded([&] { r->m->get_viterbi(a, b); }); }
 int rm_runner_get_paths(rm_runner* r, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t* d) {
   return guarded([&] { r->m->get_paths(a, b, c, d); });
+}
+int rm_runner_get_matched_points(rm_runner* r, rm_matched_point* out) {
+  static_assert(sizeof(rm_matched_point) == sizeof(MatchedPoint), "rm_matched_point is rm::MatchedPoint");
+  return guarded([&] { r->m->matched_points(reinterpret_cast<MatchedPoint*>(out)); });
 }
 int rm_runner_get_segments(rm_runner* r, uint32_t* off, void* segs) {
   return guarded([&] { r->m->get_segments(off, (SegmentRec*)segs); });

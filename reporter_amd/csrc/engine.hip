@@ -38,7 +38,8 @@
 namespace rm {
 
 const char* const kKernelNames[kNumKernels] = {"states", "candidates", "scan", "routes",
-                                               "viterbi", "paths", "segments", "report", "locality"};
+                                               "viterbi", "paths", "segments", "report", "locality",
+                                               "points"};
 
 namespace {
 
@@ -48,7 +49,6 @@ constexpr int kBigH = 4096;     // LDS hash slots, retry tier (one source at a t
 constexpr int kMidH = 512;      // LDS hash slots, first wave tier
 constexpr uint32_t kMidGrid = 4096;   // blocks of the 512-slot wave tiers (16 per CU)
 constexpr int kCandH = 256;     // road hash slots in the candidate kernel
-constexpr int kInlinePath = 8;  // path edges stored inline per slot (no allocation)
 constexpr int kReg2Grid = 512;  // blocks of the second register tiers (grid-stride over their work lists)
 constexpr uint32_t kMaxBoundCm = 100000000u;
 constexpr double kQueueSpeedMps = 2.7777777777777777;  // 10 km/h
@@ -5307,6 +5307,7 @@ Matcher::~Matcher() {
   for (auto& ev : free_ev_) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   ws_.release();
   if (dl_dev_) (void)hipFree(dl_dev_);
+  if (mp_dev_) (void)hipFree(mp_dev_);
   if (dl_host_) (void)hipHostFree(dl_host_);
   for (void* q : {(void*)jdev_, jspan_, (void*)jflag_, jtsp_})
     if (q) (void)hipFree(q);

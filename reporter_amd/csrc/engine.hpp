@@ -122,12 +122,13 @@ struct InputView {
 
 // Kernel ids for per-kernel HIP-event timing.
 enum KernelId { kKStates = 0, kKCandidates, kKScan, kKRoutes, kKViterbi, kKPaths, kKSegments, kKReport, kKLocality,
-                kNumKernels };
+                kKPoints, kNumKernels };
 extern const char* const kKernelNames[kNumKernels];
 
 // Device workspace of one batch.  All arrays are indexed by point slot p
 // (state s of trace k lives at slot trace_off[k] + s).
 constexpr int kCtlWords = 16;
+constexpr int kInlinePath = 8;  // path edges stored inline per slot (no allocation)
 
 struct Workspace {
   uint64_t cap_points = 0, cap_traces = 0, cap_trans = 0, cap_path = 0, cap_opts = 0, cap_segs = 0, cap_src = 0;
@@ -306,6 +307,9 @@ class Matcher {
   uint64_t count_segments();
   void get_reports(uint32_t* rep_off, ReportRec* reps, ReportStats* stats);
   uint64_t count_reports();
+  // Matched points of the last run()/rerun (rule 9; points.hip): one record per input point in
+  // batch point order (n_points()), computed on request from what the run left in HBM
+  void matched_points(MatchedPoint* out);
   // accumulated kernel time (ms) per KernelId since the last reset
   void kernel_times(double* ms, uint64_t* launches);
   // overflow-list sizes of the last run: routes A, routes B, paths A, candidates
@@ -397,6 +401,8 @@ class Matcher {
   void* dl_dev_ = nullptr;     // grow-only device / pinned host buffers of download_compacted
   void* dl_host_ = nullptr;
   size_t dl_dev_bytes_ = 0, dl_host_bytes_ = 0;
+  void* mp_dev_ = nullptr;     // grow-only device buffer of matched_points (mp_cap_ records)
+  uint64_t mp_cap_ = 0;
   hipStream_t stream_ = nullptr;
   Workspace ws_;
   uint32_t n_traces_ = 0;
@@ -478,6 +484,9 @@ class Engine {
   bool locality_default() const { return locality_default_; }
   uint32_t locality_shift() const { return locality_shift_; }
   uint32_t locality_bits() const { return locality_bits_; }
+  // per road its first shape vertex (R + 1 words) in HBM, uploaded on first use: only the
+  // matched-points stage walks a road's shape by road id (K1 reads cell records); thread-safe
+  const uint32_t* road_vert_off_dev();
 
  private:
   int device_;
@@ -499,6 +508,7 @@ class Engine {
   double turn_ms_[5] = {};
   bool build_balls_gpu(int mode, uint32_t radius_cm, uint32_t max_keys, uint64_t avail_bytes);
   double ball_info_[5][4] = {};
+  uint32_t* road_vert_off_ = nullptr;
 };
 
 }  // namespace rm

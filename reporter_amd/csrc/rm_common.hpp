@@ -455,6 +455,19 @@ struct ReportStats {        // per trace (reporter_service.py:164-177)
   int32_t n_reports;
 };
 
+// One matched point (DESIGN.md §3 rule 9): where an input point ended up on the road.  Same
+// layout as rm_matched_point (reporter_match.h).
+struct MatchedPoint {
+  float lon, lat;      // snapped position
+  float sq;            // squared distance (m^2) from the measurement to it, in K1's frame at the point
+  uint32_t edge;       // directed edge (kNone: unmatched)
+  uint32_t off_cm;     // offset from the start of that edge
+  uint32_t way;        // edge_way[edge]
+  uint32_t type;       // 0 unmatched, 1 matched (a state with a choice), 2 interpolated
+  uint32_t route_cm;   // distance along the transition's route from the previous state (0 for type 1)
+};
+static_assert(sizeof(MatchedPoint) == 32, "MatchedPoint is two dwordx4");
+
 constexpr int kHistBins = 16;           // 10 km/h bins, 0..160 (reporter_service.py:133)
 
 }  // namespace rm

@@ -725,5 +725,43 @@ inline void format_segments(const SegmentRec* s, uint32_t n, std::string& o) {
   o += "]}";
 }
 
+inline void put_f32(std::string& o, float x) {
+  char b[24];
+  const auto r = std::to_chars(b, b + sizeof b, x);   // shortest digits that round-trip the float
+  o.append(b, r.ptr);
+}
+
+// Extends a {"segments":[...]} reply to {"segments":[...],"matched_points":[...]}: one entry per
+// input point (DESIGN.md §3 rule 9; the fields Valhalla's trace_attributes gives a matched point).
+// in_lon / in_lat are the request's points (an unmatched entry carries them and its type only);
+// edge_len(e) is the directed edge's length in cm.
+template <class EdgeLen>
+inline void append_matched_points(const MatchedPoint* mp, uint32_t n, const float* in_lon, const float* in_lat,
+                                  EdgeLen&& edge_len, std::string& o) {
+  o.pop_back();   // the closing brace of {"segments":[...]}
+  o.reserve(o.size() + 32 + (size_t)n * 176);
+  o += ",\"matched_points\":[";
+  for (uint32_t k = 0; k < n; ++k) {
+    const MatchedPoint& r = mp[k];
+    if (k) o += ',';
+    if (r.type == 0u) {
+      o += "{\"lat\":"; put_f32(o, in_lat[k]);
+      o += ",\"lon\":"; put_f32(o, in_lon[k]);
+      o += ",\"type\":\"unmatched\"}";
+      continue;
+    }
+    o += "{\"lat\":"; put_f32(o, r.lat);
+    o += ",\"lon\":"; put_f32(o, r.lon);
+    o += r.type == 1u ? ",\"type\":\"matched\"" : ",\"type\":\"interpolated\"";
+    o += ",\"edge_id\":"; put_u64(o, r.edge);
+    o += ",\"way_id\":"; put_u64(o, r.way);
+    const uint32_t len = edge_len(r.edge);
+    o += ",\"distance_along_edge\":"; put_num(o, len ? (double)r.off_cm / (double)len : 0.0);
+    o += ",\"distance_from_trace_point\":"; put_num(o, std::sqrt((double)r.sq));
+    o += '}';
+  }
+  o += "]}";
+}
+
 }  // namespace tj
 }  // namespace rm

@@ -28,6 +28,12 @@ STATS_DTYPE = np.dtype([
     ("invalid_times", "<i4"), ("unassociated", "<i4"), ("shape_used", "<i4"), ("n_reports", "<i4")])
 assert STATS_DTYPE.itemsize == 40
 
+# one matched point (rm_matched_point): type 0 unmatched, 1 matched (a state), 2 interpolated
+MATCHED_POINT_DTYPE = np.dtype([
+    ("lon", "<f4"), ("lat", "<f4"), ("sq", "<f4"), ("edge", "<u4"), ("off_cm", "<u4"), ("way", "<u4"),
+    ("type", "<u4"), ("route_cm", "<u4")])
+assert MATCHED_POINT_DTYPE.itemsize == 32
+
 OPTIONS_DTYPE = np.dtype([
     ("mode", "<i4"), ("sigma_z", "<f4"), ("beta", "<f4"), ("search_radius", "<f4"), ("gps_accuracy", "<f4"),
     ("breakage_distance", "<f4"), ("interpolation_distance", "<f4"), ("max_route_distance_factor", "<f4"),
@@ -326,6 +332,14 @@ class BatchMatcher:
         segs = np.empty(max(sz["segments"], 1), SEGMENT_DTYPE)
         _lib.check(_lib.lib().rm_runner_get_segments(self._h, off.ctypes.data, segs.ctypes.data))
         return off, segs[: sz["segments"]]
+
+    def matched_points(self):
+        """Where every input point of the last run ended up on the road (DESIGN.md §3 rule 9):
+        one MATCHED_POINT_DTYPE record per point, in batch point order.  The stage runs on this
+        call (kernel id "points"), not during run()."""
+        out = np.empty(self.sizes()["points"], MATCHED_POINT_DTYPE)
+        _lib.check(_lib.lib().rm_runner_get_matched_points(self._h, out.ctypes.data))
+        return out
 
     def reports(self):
         sz = self.sizes()

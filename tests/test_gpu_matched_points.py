@@ -1,0 +1,332 @@
+"""Matched points on the GPU (DESIGN.md §3 rule 9; points.hip k_matched_points).
+
+Every case compares BatchMatcher.matched_points() with the independent restatement
+(tests/matched_points_ref.py, run on the oracle's outputs) field by field, floats as bits.
+"""
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+
+import matched_points_ref as mp
+import meili_oracle as mo
+from parity_util import compare_all
+from reporter_amd import engine, graphfile, world
+
+pytestmark = pytest.mark.gpu
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _oracle(g, tr, opts, topt):
+    return mo.match(g, mo.Batch(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts, topt))
+
+
+def assert_records_equal(got, want, what=""):
+    assert got.dtype == engine.MATCHED_POINT_DTYPE and len(got) == len(want), (what, len(got), len(want))
+    for f in want.dtype.names:
+        a, b = got[f].view(np.uint32), want[f].view(np.uint32)
+        if not np.array_equal(a, b):
+            i = int(np.nonzero(a != b)[0][0])
+            raise AssertionError("%s: field %s differs at point %d (%d points differ): gpu %s reference %s" % (
+                what, f, i, int((a != b).sum()), got[i], want[i]))
+
+
+def run_and_compare(path, tr, opts, topt=None, what="", eng=None):
+    """One run of the batch, matched_points() against the reference; returns (records, oracle)."""
+    g = graphfile.load(path)
+    T = len(tr["trace_off"]) - 1
+    topt = np.zeros(T, np.uint32) if topt is None else topt
+    ref = _oracle(g, tr, opts, topt)
+    want = mp.matched_points(g, tr, opts, topt, ref)
+    own = eng is None
+    eng = eng or engine.Engine(path, 0)
+    bm = engine.BatchMatcher(eng)
+    bm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts, topt)
+    got = bm.matched_points()
+    assert_records_equal(got, want, what)
+    compare_all(bm, ref, tr["trace_off"])   # the stage leaves the run's outputs as they were
+    bm.close()
+    if own:
+        eng.close()
+    return got, ref
+
+
+def _set(path, hz4=False, seed=301):
+    if hz4:
+        return world.generate_traces(path, n_traces=40, n_points=120, rate_s=0.25, noise_m=5.0, seed=seed)
+    return world.generate_traces(path, n_traces=40, n_points=60, rate_s=1.0, noise_m=5.0, seed=seed)
+
+
+@pytest.mark.parametrize("hz4", [False, True])
+def test_baseline(built_lib, small_world, hz4):
+    """1. The 1 Hz and 4 Hz sets of the CPU test: 42 % and 80 % of the points are not states."""
+    tr = _set(small_world, hz4)
+    got, ref = run_and_compare(small_world, tr, engine.default_options(1), what="4hz" if hz4 else "1hz")
+    assert (got["type"] == mp.MATCHED).sum() > 900 and (got["type"] == mp.INTERPOLATED).sum() > 1000
+
+
+def test_run_paths_and_rerun(built_lib, small_world, monkeypatch):
+    """2. The small run, the ordinary run (RM_SMALL_BATCH_POINTS=0) and a rerun leave the same
+    bytes, and every stage output still equals the oracle after the stage ran."""
+    g = graphfile.load(small_world)
+    tr = _set(small_world)
+    opts = engine.default_options(1)
+    ref = _oracle(g, tr, opts, np.zeros(40, np.uint32))
+    want = mp.matched_points(g, tr, opts, np.zeros(40, np.uint32), ref)
+    eng = engine.Engine(small_world, 0)
+    bm = engine.BatchMatcher(eng)
+    got = {}
+    for way in ("small", "ordinary", "rerun"):
+        if way == "ordinary":
+            monkeypatch.setenv("RM_SMALL_BATCH_POINTS", "0")
+        else:
+            monkeypatch.delenv("RM_SMALL_BATCH_POINTS", raising=False)
+        if way == "rerun":
+            bm.rerun()
+        else:
+            bm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts)
+        rec = bm.matched_points()
+        assert_records_equal(rec, want, way)
+        got[way] = rec.tobytes()
+        compare_all(bm, ref, tr["trace_off"])
+        assert bm.matched_points().tobytes() == got[way]   # asked twice: the same records
+    assert got["small"] == got["ordinary"] == got["rerun"]
+    bm.close()
+    eng.close()
+
+
+def _assemble(traces):
+    """Trace set from [(lon, lat, time)] arrays (accuracy 5 m, as the generator gives)."""
+    off = np.concatenate([[0], np.cumsum([len(t[0]) for t in traces])]).astype(np.uint32)
+    out = {k: np.concatenate([np.asarray(t[i], np.float64) for t in traces]) for i, k in enumerate(("lon", "lat", "time"))}
+    out["accuracy"] = np.full(int(off[-1]), 5.0, np.float32)
+    out["trace_off"] = off
+    return out
+
+
+def test_hand_made_batch(built_lib, small_world):
+    """3. A 90-point stop, a state 5 km off the map with followers, a jump beyond the breakage
+    distance, a two-point trace and a trace that ends in non-state points."""
+    base = _set(small_world, seed=311)
+    rng = np.random.default_rng(5)
+    mlat, mlon = 110567.0, 111320.0 * math.cos(math.radians(float(base["lat"][0])))
+
+    def tr(k, a=0, b=60):
+        o = int(base["trace_off"][k])
+        return [base[f][o + a:o + b].copy() for f in ("lon", "lat", "time")]
+
+    def jitter(lon, lat, n, m):   # n points within m metres of (lon, lat)
+        r, th = rng.uniform(0, m, n), rng.uniform(0, 2 * math.pi, n)
+        return lon + r * np.cos(th) / mlon, lat + r * np.sin(th) / mlat
+
+    traces = []
+    # a vehicle that drives 20 s and then stands for 90 s: one state, then a gap of 90 points
+    lon, lat, t = tr(0, 0, 20)
+    jl, ja = jitter(lon[-1], lat[-1], 90, 2.9)
+    traces.append((np.concatenate([lon, jl]), np.concatenate([lat, ja]), np.concatenate([t, t[-1] + 1 + np.arange(90)])))
+    stop_gap = (len(lon), len(lon) + 90)
+    # ... and one that only stands: its single state has no path on either side
+    lon, lat, t = tr(1, 0, 1)
+    jl, ja = jitter(lon[0], lat[0], 90, 2.9)
+    traces.append((np.concatenate([lon, jl]), np.concatenate([lat, ja]), np.concatenate([t, t[0] + 1 + np.arange(90)])))
+    # the middle state 5 km north of the map, with three followers around it
+    lon, lat, t = tr(2, 0, 30)
+    far_lat = lat[14] + 5000.0 / mlat
+    jl, ja = jitter(lon[14], far_lat, 3, 2.0)
+    lon = np.concatenate([lon[:14], [lon[14]], jl, lon[15:]])
+    lat = np.concatenate([lat[:14], [far_lat], ja, lat[15:]])
+    far = (sum(len(x[0]) for x in traces) + 14, 4)
+    traces.append((lon, lat, t[0] + np.arange(len(lon), dtype=np.float64)))
+    # a jump beyond breakage_distance: the first 20 points of one trace, then of one > 2.5 km away
+    la, aa, ta = tr(3, 0, 20)
+    k2 = next(k for k in range(4, 40) if math.hypot((base["lon"][base["trace_off"][k]] - la[-1]) * mlon,
+                                                    (base["lat"][base["trace_off"][k]] - aa[-1]) * mlat) > 2500.0)
+    lb, ab, _ = tr(k2, 0, 20)
+    traces.append((np.concatenate([la, lb]), np.concatenate([aa, ab]), ta[0] + np.arange(40, dtype=np.float64)))
+    jump = sum(len(x[0]) for x in traces[:-1]) + 20
+    traces.append(tuple(x[:2] for x in tr(5)))                          # two points
+    lon, lat, t = tr(6, 0, 25)                                          # ends in non-state points
+    jl, ja = jitter(lon[-1], lat[-1], 3, 2.0)
+    traces.append((np.concatenate([lon, jl]), np.concatenate([lat, ja]), np.concatenate([t, t[-1] + 1 + np.arange(3)])))
+    batch = _assemble(traces)
+    got, ref = run_and_compare(small_world, batch, engine.default_options(1), what="hand-made")
+    # the cases are what they claim to be
+    off = batch["trace_off"].astype(np.int64)
+
+    def slot(k, p):   # state slot of point p of trace k
+        so = ref["state_orig"][off[k]:off[k] + int(ref["n_states"][k])]
+        return int(off[k] + np.nonzero(so == p - off[k])[0][0])
+
+    assert (got["type"][stop_gap[0]:stop_gap[1]] == mp.INTERPOLATED).sum() >= 85
+    assert int(ref["n_states"][1]) == 1 and got["type"][off[1]] == mp.MATCHED
+    assert (got["type"][off[1] + 1:off[2]] == mp.INTERPOLATED).all()
+    assert len(set(got["edge"][off[1]:off[2]])) == 1                       # the stop stays on the state's edge
+    assert (got["type"][far[0]:far[0] + far[1]] == mp.UNMATCHED).all()
+    assert got["type"][far[0] + far[1]] == mp.MATCHED and ref["chain_start"][slot(2, far[0] + far[1])]
+    assert got["type"][jump] == mp.MATCHED and ref["chain_start"][slot(3, jump)]
+    assert off[5] - off[4] == 2 and (got["type"][off[4]:off[5]] != mp.UNMATCHED).all()
+    assert got["type"][-1] == mp.INTERPOLATED
+
+
+def test_long_polylines(built_lib, tmpdir_session):
+    """4. 120 s sampling: the gaps sit on paths of tens of edges, read from the path pool beyond
+    the inline count and walked in more than one 16-piece chunk."""
+    path = str(tmpdir_session / "mp_sparse.rmg")
+    world.build_world(path, 48, 48, 100.0, seed=12, cell_m=100.0)
+    base = world.generate_traces(path, n_traces=40, n_points=12, rate_s=120.0, noise_m=5.0, seed=302)
+    mlat, mlon = 110567.0, 111320.0 * math.cos(math.radians(float(base["lat"][0])))
+    traces = []
+    for k in range(40):
+        o = int(base["trace_off"][k])
+        lon, lat, t = (base[f][o:o + 12] for f in ("lon", "lat", "time"))
+        L, A, Tm = [], [], []
+        for i in range(12):
+            L.append(lon[i]); A.append(lat[i]); Tm.append(t[i])
+            if i + 1 < 12:   # two extra points, each 4 m beyond its predecessor, towards the next state
+                dx, dy = (lon[i + 1] - lon[i]) * mlon, (lat[i + 1] - lat[i]) * mlat
+                d = max(math.hypot(dx, dy), 1.0)
+                for j in (1, 2):
+                    L.append(lon[i] + 4.0 * j * dx / d / mlon); A.append(lat[i] + 4.0 * j * dy / d / mlat); Tm.append(t[i] + j)
+        traces.append((L, A, Tm))
+    batch = _assemble(traces)
+    opts = engine.default_options(1, search_radius=60.0)
+    got, ref = run_and_compare(path, batch, opts, what="long polylines")
+    st = np.zeros(len(got), bool)
+    for k in range(40):
+        o = int(batch["trace_off"][k])
+        st[o + ref["state_orig"][o:o + int(ref["n_states"][k])]] = True
+    assert (~st).sum() >= 800                                              # the inserted points are not states
+    chained = (ref["chain_start"] == 0) & (ref["choice"] >= 0)
+    assert (ref["path_cnt"][chained] > 8).sum() > 100 and (ref["path_cnt"][chained] > 16).sum() > 20
+    assert (got["type"] == mp.INTERPOLATED).sum() >= 700
+
+
+def test_osm_city_modes(built_lib, tmp_path_factory):
+    """5. Curved multi-vertex ways, one-way pairs and reverse edges a mode cannot use."""
+    d = tmp_path_factory.mktemp("mp_city")
+    city = world.build_city(str(d / "city.rmg"), rows=24, cols=24, seed=7)
+    parts = [world.generate_traces(city, 20, 60, rate_s=1.0, noise_m=5.0, seed=81, mode="auto"),
+             world.generate_traces(city, 20, 60, rate_s=1.0, noise_m=5.0, seed=82, mode="pedestrian")]
+    tr = world.concat_traces(*parts)
+    opts = engine.default_options(2)
+    opts[1]["mode"] = world.MODES["pedestrian"]
+    topt = np.repeat(np.arange(2, dtype=np.uint32), 20)
+    got, ref = run_and_compare(city, tr, opts, topt, what="city")
+    g = graphfile.load(city)
+    nseg = np.diff(g["road_vert_off"].astype(np.int64)) - 1
+    m = got["type"] != mp.UNMATCHED
+    road = g["edges"].reshape(-1, 4)[got["edge"][m].astype(np.int64), 3] >> 1
+    assert (nseg[road] > 1).sum() > 200          # positions on curved ways
+    assert (got["type"] == mp.INTERPOLATED).sum() > 300
+
+
+def test_turn_costs(built_lib, small_world):
+    """6. turn_penalty_factor 200: the records follow the oracle's (changed) choices."""
+    tr = _set(small_world)
+    run_and_compare(small_world, tr, engine.default_options(1, turn_penalty_factor=200.0), what="turn costs")
+
+
+def test_json_replies(built_lib, small_world, tmp_path):
+    """7. MatchPoints: one entry per input point, types and edges of the array API, the two
+    distances as the records give them, and Match's segments string for string."""
+    import valhalla
+    g = graphfile.load(small_world)
+    tr = _set(small_world)
+    opts = engine.default_options(1)
+    eng = engine.Engine(small_world, 0)
+    bm = engine.BatchMatcher(eng)
+    bm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts)
+    rec = bm.matched_points()
+    bm.close()
+    eng.close()
+    elen = g["edges"].reshape(-1, 4)[:, 1]
+    conf = valhalla.write_config(str(tmp_path / "mp.json"), small_world, device=0)
+    valhalla.Configure(conf)
+    sm = valhalla.SegmentMatcher()
+    reqs = [json.dumps(world.trace_to_request(tr, k), separators=(",", ":")) for k in range(3)]
+    outs = [sm.MatchPoints(reqs[0])] + sm.MatchPointsMany(reqs[1:])
+    names = {mp.UNMATCHED: "unmatched", mp.MATCHED: "matched", mp.INTERPOLATED: "interpolated"}
+    for k in range(3):
+        plain = sm.Match(reqs[k])
+        assert outs[k].startswith(plain[:-1] + ',"matched_points":['), k    # the segments, string for string
+        rep = json.loads(outs[k])
+        assert set(rep) == {"segments", "matched_points"} and rep["segments"] == json.loads(plain)["segments"]
+        pts = rep["matched_points"]
+        o = int(tr["trace_off"][k])
+        assert len(pts) == 60
+        for q, p in enumerate(pts):
+            r = rec[o + q]
+            assert p["type"] == names[int(r["type"])], (k, q)
+            if r["type"] == mp.UNMATCHED:
+                assert set(p) == {"lat", "lon", "type"}
+                assert np.float32(p["lat"]) == np.float32(tr["lat"][o + q]) and np.float32(p["lon"]) == np.float32(tr["lon"][o + q])
+                continue
+            assert set(p) == {"lat", "lon", "type", "edge_id", "way_id", "distance_along_edge", "distance_from_trace_point"}
+            assert p["edge_id"] == int(r["edge"]) and p["way_id"] == int(r["way"])
+            assert np.float32(p["lat"]) == r["lat"] and np.float32(p["lon"]) == r["lon"]
+            assert p["distance_along_edge"] == pytest.approx(int(r["off_cm"]) / int(elen[r["edge"]]), rel=1e-6)
+            assert p["distance_from_trace_point"] == pytest.approx(math.sqrt(float(r["sq"])), rel=1e-6)
+        assert sum(p["type"] == "interpolated" for p in pts) > 10
+    sm.close()
+
+
+def test_manila_reply_bytes(built_lib, tmp_path):
+    """7b. rm_match's reply for the README's Manila trace, byte for byte what it was before the
+    stage existed (tests/golden/manila_match_reply.json), and MatchPoints' segments with it."""
+    import valhalla
+    from test_gpu_manila import manila_world
+    path = str(tmp_path / "manila.rmg")
+    req = manila_world(path)
+    with open(os.path.join(HERE, "golden", "manila_match_reply.json")) as f:
+        want = f.read().strip()
+    conf = valhalla.write_config(str(tmp_path / "manila.json"), path, device=0)
+    valhalla.Configure(conf)
+    sm = valhalla.SegmentMatcher()
+    text = json.dumps(req, separators=(",", ":"))
+    got = sm.Match(text)
+    assert got == want
+    both = sm.MatchPoints(text)
+    assert both.startswith(want[:-1] + ',"matched_points":[')
+    pts = json.loads(both)["matched_points"]
+    # 7-29 s apart: every point is a state, matched or (no road within its radius) unmatched
+    assert len(pts) == len(req["trace"]) and {p["type"] for p in pts} <= {"matched", "unmatched"}
+    assert sum(p["type"] == "matched" for p in pts) >= 10
+    sm.close()
+
+
+def test_isolation(built_lib, tmpdir_session):
+    """8. A trace that fails under isolation (more than 192 roads in its radius) is all type 0;
+    its neighbours equal the reference."""
+    path = str(tmpdir_session / "mp_dense.rmg")
+    world.build_world(path, 60, 60, 20.0, seed=2, cell_m=20.0)
+    g = graphfile.load(path)
+    T = 8
+    tr = world.generate_traces(path, n_traces=T, n_points=40, rate_s=1.0, noise_m=3.0, seed=73)
+    opts = engine.default_options(2, search_radius=30.0)
+    opts[1]["search_radius"] = 200.0
+    topt = np.zeros(T, np.uint32)
+    topt[3] = 1
+    eng = engine.Engine(path, 0)
+    bm = engine.BatchMatcher(eng)
+    bm.set_isolation(True)
+    bm.run(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts, topt)
+    errs = bm.trace_errors()
+    assert np.nonzero(errs)[0].tolist() == [3], errs
+    got = bm.matched_points()
+    bm.close()
+    eng.close()
+    o = tr["trace_off"].astype(np.int64)
+    bad = got[o[3]:o[4]]
+    assert (bad["type"] == mp.UNMATCHED).all() and (bad["edge"] == mp.NONE).all()
+    for f in ("lon", "lat", "sq", "off_cm", "way", "route_cm"):
+        assert not bad[f].any(), f
+    good = [k for k in range(T) if k != 3]
+    sel = np.concatenate([np.arange(o[k], o[k + 1]) for k in good])
+    sub = {k: tr[k][sel] for k in ("lon", "lat", "time", "accuracy")}
+    sub["trace_off"] = (np.arange(len(good) + 1) * 40).astype(np.uint32)
+    ref = _oracle(g, sub, opts[:1], np.zeros(len(good), np.uint32))
+    want = mp.matched_points(g, sub, opts[:1], np.zeros(len(good), np.uint32), ref)
+    assert_records_equal(got[sel], want, "neighbours of the failed trace")
+    assert (want["type"] == mp.INTERPOLATED).sum() > 30

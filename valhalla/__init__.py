@@ -87,6 +87,28 @@ class SegmentMatcher(object):
         finally:
             _lib.lib().rm_free(buf)
 
+    def MatchPoints(self, trace_json):
+        """Match plus the snapped road position of every input point: the same request in,
+        {"segments": [...], "matched_points": [...]} out (rm_match_points; one entry per point,
+        "type" matched / interpolated / unmatched, as Valhalla's trace_attributes names them)."""
+        return self.MatchPointsMany([trace_json])[0]
+
+    def MatchPointsMany(self, trace_jsons):
+        """MatchPoints for many requests in one uncoalesced GPU batch (rm_match_points_batch)."""
+        n = len(trace_jsons)
+        if n == 0:
+            return []
+        arr = (C.c_char_p * n)(*[t.encode("utf-8") if isinstance(t, str) else t for t in trace_jsons])
+        outs = (C.c_void_p * n)()
+        rc = _lib.lib().rm_match_points_batch(self._h, arr, n, outs)
+        if rc != 0:
+            raise RuntimeError(_lib.last_error())
+        try:
+            return [C.string_at(outs[i]).decode("utf-8") for i in range(n)]
+        finally:
+            for i in range(n):
+                _lib.lib().rm_free(outs[i])
+
     def last_timing(self):
         """Host wall ms of the last uncoalesced MatchMany: parse, stage, engine, download, format, total."""
         out = (C.c_double * 6)()

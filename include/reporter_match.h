@@ -265,6 +265,15 @@ int rm_runner_sizes(rm_runner* r, uint64_t out[10]);
  * [6] route items the 16-lane group tier passed to the 512-slot wave tier, [7] likewise for paths,
  * [8] route items the 512-slot wave tier passed to the 4096-slot one, [9] likewise for paths */
 int rm_runner_route_tiers(rm_runner* r, uint64_t out[10]);
+/* counters since the runner was created: [0] steady runs (large batches after the first, without
+ * read-backs between the stages), [1] steady runs gated off on the device and run again the ordinary
+ * way, [2] steady runs that did not launch the routes stage's hand-over tiers, [3] likewise the
+ * path stage's */
+int rm_runner_run_stats(rm_runner* r, uint64_t out[4]);
+/* the steady scans' block bases on the host (test hook for rm_common.hpp scan_base_lane): part
+ * holds nb pairs of block partials, base receives nb pairs of exclusive prefixes, formed as a
+ * block of `lanes` threads forms them from the coarse buckets and its group's partials */
+int rm_scan_block_bases(const uint64_t* part, uint32_t nb, uint32_t lanes, uint64_t* base);
 int rm_runner_get_states(rm_runner* r, uint32_t* n_states, uint32_t* state_orig);
 int rm_runner_get_candidates(rm_runner* r, uint8_t* cand_n, uint32_t* road, uint32_t* s_cm, float* sq);
 int rm_runner_get_routes(rm_runner* r, uint32_t* trans_off, double* gc, uint32_t* route_cm);

@@ -123,6 +123,8 @@ PROTOTYPES = [
     ("rm_engine_turn_rows", C.c_int, [P, P, P]),
     ("rm_engine_ball_lookup", C.c_int, [P, C.c_int, C.c_uint64, P, P, P, P]),
     ("rm_runner_route_tiers", C.c_int, [P, P]),
+    ("rm_runner_run_stats", C.c_int, [P, P]),
+    ("rm_scan_block_bases", C.c_int, [P, C.c_uint32, C.c_uint32, P]),
     ("rm_balls_lookup", C.c_int, [C.c_char_p, C.c_int, C.c_double, C.c_uint64, P, P, P, P]),
     ("rm_graph_auto_ball_radius", C.c_int, [C.c_char_p, P]),
     ("rm_graph_fit_ball_radius", C.c_int, [C.c_char_p, C.c_int, C.c_double, C.c_double, P]),

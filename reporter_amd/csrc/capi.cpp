@@ -1378,6 +1378,27 @@ int rm_runner_route_tiers(rm_runner* r, uint64_t out[10]) {
 #endif
   });
 }
+int rm_runner_run_stats(rm_runner* r, uint64_t out[4]) { return guarded([&] { r->m->run_stats(out); }); }
+int rm_scan_block_bases(const uint64_t* part, uint32_t nb, uint32_t lanes, uint64_t* base) {
+  return guarded([&] {
+    if (!lanes) throw std::invalid_argument("lanes must be positive");
+    std::vector<unsigned long long> p(2 * (size_t)nb), bkt(2 * (size_t)scan_buckets(nb) + 2, 0ull);
+    for (size_t i = 0; i < p.size(); ++i) p[i] = part[i];
+    for (uint32_t q = 0; q < nb; ++q) {   // as k_scan_buckets does
+      bkt[2 * (size_t)scan_bucket(q)] += p[2 * (size_t)q];
+      bkt[2 * (size_t)scan_bucket(q) + 1] += p[2 * (size_t)q + 1];
+    }
+    for (uint32_t q = 0; q < nb; ++q) {   // as an apply block does, lane by lane
+      unsigned long long a = 0, c = 0;
+      for (uint32_t l = 0; l < lanes; ++l) {
+        unsigned long long la, lc;
+        scan_base_lane(p.data(), bkt.data(), q, l, lanes, la, lc);
+        a += la; c += lc;
+      }
+      base[2 * (size_t)q] = a; base[2 * (size_t)q + 1] = c;
+    }
+  });
+}
 int rm_runner_get_states(rm_runner* r, uint32_t* a, uint32_t* b) { return guarded([&] { r->m->get_states(a, b); }); }
 int rm_runner_get_candidates(rm_runner* r, uint8_t* a, uint32_t* b, uint32_t* c, float* d) {
   return guarded([&] { r->m->get_candidates(a, b, c, d); });

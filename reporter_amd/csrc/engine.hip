@@ -97,6 +97,9 @@ struct DevBatch {  // POD view of the workspace for kernels
   // 4: a steady run (Matcher::run_steady) sized from the pools an earlier run of the matcher left:
   // every stage after the transition scan skips a batch with more transitions or K2 sources than
   // trans_cap / src_cap (steady_abort), and the host re-runs it the ordinary way
+  // 8: a steady run that did not launch the routes stage's hand-over tiers (the matcher's last runs
+  // handed nothing over): items handed over after all (ctl[1]) make K3 and everything after it skip;
+  // 16: likewise the path stage's tiers (ctl[8]): K4 and the report skip.  The host re-runs either.
   const unsigned long long* tot;
   uint64_t seg_cap;
   uint64_t trans_cap, src_cap;
@@ -104,14 +107,14 @@ struct DevBatch {  // POD view of the workspace for kernels
 };
 
 __device__ __forceinline__ bool steady_abort(const DevBatch& b) {
-  return (b.gate & 4u) && (b.tot[0] > b.trans_cap || b.tot[1] > b.src_cap);
+  return ((b.gate & 4u) && (b.tot[0] > b.trans_cap || b.tot[1] > b.src_cap)) || ((b.gate & 8u) && b.ctl[1] != 0u);
 }
 
 __device__ __forceinline__ bool small_abort(const DevBatch& b) {
   if (!b.gate) return false;
   const uint32_t* c = b.ctl;
   return (c[2] & kErrPathOverflow) != 0u || ((b.gate & 2u) && (c[9] | c[10]) != 0u) || b.tot[2] > b.seg_cap ||
-         steady_abort(b);
+         ((b.gate & 16u) && c[8] != 0u) || steady_abort(b);
 }
 
 // A failure that belongs to one trajectory (too many roads in a radius, a search beyond every
@@ -310,26 +313,32 @@ __global__ void __launch_bounds__(64) k_states(DevBatch b) {
   // paid a memory round trip before their first instruction)
   const uint32_t nl = n ? n - 1u : 0u;
   float nlo = b.lon[o + min((uint32_t)lane, nl)], nla = b.lat[o + min((uint32_t)lane, nl)];
+  double ntm = b.time[o + min((uint32_t)lane, nl)];   // a state's time goes to its slot (K4 reads the times by slot)
   // a chunk's stores are issued at the top of the next chunk, before its prefetch: vmcnt counts
   // loads and stores in issue order, so stores issued after a prefetch would make the next
   // chunk's wait for that prefetch wait for them too
   bool w_slot = false, w_state = false, w_gc = false;
   uint32_t w_i = 0, w_si = 0;
-  double w_gcv = 0.0;
+  double w_gcv = 0.0, w_tm = 0.0;
   for (uint32_t c0 = 0; c0 < n; c0 += 64) {
     const uint32_t i = c0 + lane, m = min(64u, n - c0);
     const bool act = i < n;
     float lo = act ? nlo : 0.f, la = act ? nla : 0.f;
+    double tm = act ? ntm : 0.0;
     // the previous prefetch is consumed here, before the stores below are issued (its wait then
     // waits for nothing newer) and before the next prefetch (whose loads can then land in the
     // same registers instead of being copied at the back edge, a copy that waits for them)
-    __asm__ volatile("" : "+v"(lo), "+v"(la) : : "memory");
-    if (w_slot) b.slot_trace[o + w_i] = k;
-    if (w_state) b.state_orig[o + w_si] = w_i;
+    __asm__ volatile("" : "+v"(lo), "+v"(la), "+v"(tm) : : "memory");
+    // every slot starts without a chosen candidate and without path edges (K3 sets the chosen
+    // candidates; the path stage counts chosen transitions): written here, with the stores this
+    // kernel makes to every slot anyway, instead of in the bandwidth-bound k_trans_count
+    if (w_slot) { b.slot_trace[o + w_i] = k; b.choice[o + w_i] = -1; b.path_cnt[o + w_i] = 0u; }
+    if (w_state) { b.state_orig[o + w_si] = w_i; b.state_time[o + w_si] = w_tm; }
     if (w_gc) b.gc[o + w_si] = w_gcv;
     __asm__ volatile("" : : : "memory");
     nlo = b.lon[o + min(i + 64u, nl)];
     nla = b.lat[o + min(i + 64u, nl)];
+    ntm = b.time[o + min(i + 64u, nl)];
     w_slot = act;
     w_i = i;
     float lo1 = __shfl_up(lo, 1, 64), la1 = __shfl_up(la, 1, 64);
@@ -394,6 +403,7 @@ __global__ void __launch_bounds__(64) k_states(DevBatch b) {
       q = nq + 1;
     }
     w_state = ((st >> lane) & 1ull) != 0ull;
+    w_tm = tm;
     w_gc = false;
     if (w_state) {
       const unsigned long long below = st & ((1ull << lane) - 1ull);
@@ -415,8 +425,8 @@ __global__ void __launch_bounds__(64) k_states(DevBatch b) {
     c1lo = lane_f(lo, 63); c1la = lane_f(la, 63);
     c2lo = lane_f(lo, 62); c2la = lane_f(la, 62);
   }
-  if (w_slot) b.slot_trace[o + w_i] = k;
-  if (w_state) b.state_orig[o + w_si] = w_i;
+  if (w_slot) { b.slot_trace[o + w_i] = k; b.choice[o + w_i] = -1; b.path_cnt[o + w_i] = 0u; }
+  if (w_state) { b.state_orig[o + w_si] = w_i; b.state_time[o + w_si] = w_tm; }
   if (w_gc) b.gc[o + w_si] = w_gcv;
   if (lane == 0) b.n_states[k] = ns;
 }
@@ -973,22 +983,20 @@ __global__ void __launch_bounds__(256) k_trans_count(DevBatch b, unsigned long l
   const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint32_t c = 0, ns = 0;
   if (p < b.P) {   // every lane reaches the block sum below (it holds a barrier)
-    b.choice[p] = -1;      // K3 sets the chosen candidates; the path stage counts chosen transitions
-    b.path_cnt[p] = 0u;
+    // (k_states, which every run launches first, left choice = -1, path_cnt = 0 and the states'
+    // times by slot: this pass is bandwidth-bound and reads the two times from there, coalesced)
     const uint32_t k = b.slot_trace[p];
     const uint32_t o = b.trace_off[k];
     const uint32_t s = (uint32_t)(p - o);
     const uint32_t S = b.n_states[k];
-    if (s < S) b.state_time[p] = b.time[o + b.state_orig[p]];   // K4 reads the state times by slot
     if (s >= 1 && s < S) {
       const uint32_t KA = b.cand_n[p - 1], KB = b.cand_n[p];
       c = KA * KB;
       ns = KB ? KA : 0u;
-      const uint32_t pa = o + b.state_orig[p - 1], pb = o + b.state_orig[p];
       const double gc = b.gc[p];   // written by k_states (the rule's own measurement)
       const MatchOptions op = b.opts[b.trace_opt[k]];
       // .w: the pair's turn_penalty_factor (float bits) when its routes carry turn costs (rule 3b), else 0
-      b.pair_info[p] = make_uint4(route_bound(gc, op), time_bound(b.time[pb] - b.time[pa], op),
+      b.pair_info[p] = make_uint4(route_bound(gc, op), time_bound(b.state_time[p] - b.state_time[p - 1], op),
                                   KA | (KB << 8) | ((uint32_t)op.mode << 16),
                                   op.turn_penalty_factor > 0.f ? __float_as_uint(op.turn_penalty_factor) : 0u);
     }
@@ -1090,6 +1098,123 @@ __global__ void __launch_bounds__(256) k_path_apply_small(DevBatch b, const unsi
       if (o + q < b.seg_cap) rec_slot[o + q] = (uint32_t)x;
     o += c;
   }
+}
+
+// ---- steady runs (Matcher::run_steady): the same two fused passes for a batch of any size.  A
+// block cannot fold 23 k partials, so k_scan_buckets first sums every kScanGroup partials into
+// one coarse bucket (one wave per bucket, every bucket written: ~3 us on C2's 367 buckets) and an
+// apply block's base is the buckets before its group plus the partials before it inside the group
+// (rm_common.hpp scan_base_lane; C2: at most 366 + 63 pairs, L2-resident).  The last block's base
+// plus its own sum is the total.  No block waits for another, and the one-block k_scan_parts
+// between the passes (24 us of a C2 step, twice) and the separate fill passes (k_src_items,
+// k_rec_slot) are gone from the step.  (Adding the block sums into the buckets from the counting
+// kernels instead -- no middle launch -- cost more than it saved: 23 k u64 atomics on 367
+// addresses took k_trans_count from 62 to 82 us and k_sum_u64 from 6.9 to 13.)
+__global__ void __launch_bounds__(256) k_scan_buckets(const unsigned long long* part, uint32_t nb, unsigned long long* bkt) {
+  const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);   // one wave per bucket
+  if (g >= scan_buckets(nb)) return;
+  const uint32_t q = g * kScanGroup + (threadIdx.x & 63u);
+  static_assert(kScanGroup == 64, "one lane per partial of the bucket");
+  unsigned long long a = q < nb ? part[2 * (uint64_t)q] : 0ull, c = q < nb ? part[2 * (uint64_t)q + 1] : 0ull;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    a += __shfl_down(a, d, 64); c += __shfl_down(c, d, 64);
+  }
+  if ((threadIdx.x & 63u) == 0) { bkt[2 * (uint64_t)g] = a; bkt[2 * (uint64_t)g + 1] = c; }
+}
+
+__device__ __forceinline__ void block_base_parts(const unsigned long long* part, const unsigned long long* bkt,
+                                                 unsigned long long* pre) {
+  __shared__ unsigned long long s[4][2];
+  unsigned long long a, c;
+  scan_base_lane(part, bkt, blockIdx.x, threadIdx.x, blockDim.x, a, c);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    a += __shfl_down(a, d, 64); c += __shfl_down(c, d, 64);
+  }
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s[wv][0] = a; s[wv][1] = c; }
+  __syncthreads();
+  pre[0] = s[0][0] + s[1][0] + s[2][0] + s[3][0];
+  pre[1] = s[0][1] + s[1][1] + s[2][1] + s[3][1];
+}
+
+// k_scan_apply2 + k_src_items; totals to tot[0..1].  The totals come out of this launch, so the
+// item writes cannot be gated by steady_abort: each is bounded by src_cap instead (the run is
+// then gated off after this kernel, and the host runs the batch again the ordinary way).
+__global__ void __launch_bounds__(256) k_trans_apply_steady(DevBatch b, const unsigned long long* part,
+                                                            const unsigned long long* bkt, unsigned long long* tot) {
+  // (the counts first: their loads are in flight while the base is formed)
+  const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+  const uint32_t va = p < b.P ? b.trans_cnt[p] : 0u, vc = p < b.P ? b.src_cnt[p] : 0u;
+  unsigned long long pre[2];
+  block_base_parts(part, bkt, pre);
+  __shared__ uint32_t sa[4], sc[4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t ia = va, ic = vc;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t ta = __shfl_up(ia, d, 64), tc = __shfl_up(ic, d, 64);
+    if (lane >= d) { ia += ta; ic += tc; }
+  }
+  if (lane == 63) { sa[wv] = ia; sc[wv] = ic; }
+  __syncthreads();
+  uint32_t ba = 0, bc = 0;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    ba += w < wv ? sa[w] : 0u;
+    bc += w < wv ? sc[w] : 0u;
+  }
+  if (p < b.P) {
+    const unsigned long long at = pre[1] + bc + ic - vc;
+    b.trans_off[p] = (uint32_t)(pre[0] + ba + ia - va);
+    b.src_off[p] = (uint32_t)at;
+    for (uint32_t i = 0; i < vc; ++i)
+      if (at + i < b.src_cap) b.src_item[at + i] = (uint32_t)p;
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {   // (lanes past P counted 0)
+    tot[0] = pre[0] + ba + ia;
+    tot[1] = pre[1] + bc + ic;
+  }
+}
+
+// k_scan_apply4 + k_rec_slot; total to tot[2].  Records past seg_cap are not written (the run is
+// then gated off: small_abort).
+__global__ void __launch_bounds__(256) k_path_apply_steady(DevBatch b, const unsigned long long* part,
+                                                           const unsigned long long* bkt, unsigned long long* tot,
+                                                           uint32_t* rec_slot) {
+  __shared__ unsigned long long sa[4], sc[4];
+  const uint64_t n = b.P;
+  const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
+  uint32_t v[4] = {0u, 0u, 0u, 0u};
+  if (i + 4 <= n) {
+    const uint4 q = *reinterpret_cast<const uint4*>(b.path_cnt + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    for (uint64_t x = i; x < n; ++x) v[x - i] = b.path_cnt[x];
+  }
+  unsigned long long pre[2];
+  block_base_parts(part, bkt, pre);
+  const unsigned long long mine = (unsigned long long)v[0] + v[1] + v[2] + v[3];
+  unsigned long long ea, ec;
+  block_excl_scan2(mine, 0ull, ea, ec, sa, sc, 4);
+  const unsigned long long base = pre[0] + ea;
+  const uint32_t o0 = (uint32_t)base, o1 = o0 + v[0], o2 = o1 + v[1], o3 = o2 + v[2];
+  if (i + 4 <= n) {
+    *reinterpret_cast<uint4*>(b.trav_off + i) = make_uint4(o0, o1, o2, o3);
+  } else {
+    const uint32_t o[4] = {o0, o1, o2, o3};
+    for (uint64_t x = i; x < n; ++x) b.trav_off[x] = o[x - i];
+  }
+  unsigned long long o = base;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const uint32_t c = v[j];   // (0 past n)
+    for (uint32_t q = 0; q < c; ++q)
+      if (o + q < b.seg_cap) rec_slot[o + q] = (uint32_t)(i + j);
+    o += c;
+  }
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) tot[2] = base + mine;
 }
 
 // Compaction for the downloads: trace k's records [base[k], base[k] + cnt[k]) of a per-trace
@@ -5374,6 +5499,8 @@ void Matcher::alloc_points(uint64_t cp, uint64_t ct, uint64_t co, uint64_t keep_
     w.trace_err = dalloc<uint32_t>(L, ct);
     w.tot64 = dalloc<unsigned long long>(L, 4);
     w.tot_part = dalloc<unsigned long long>(L, 2 * ((cp + 255) / 256) + 2);
+    // a steady run's coarse scan buckets (k_scan_buckets): one pair per kScanGroup counting blocks
+    w.scan_bkt = dalloc<unsigned long long>(L, 2 * (scan_buckets((uint32_t)((cp + 255) / 256)) + 1));
     w.cap_points = cp; w.cap_traces = ct; w.cap_opts = co;
     w.gsearch = nullptr;
     w.route = nullptr; w.route_d = nullptr; w.cap_turn = 0; w.walk = nullptr; w.cap_walk = 0; w.rl_routes_a = nullptr; w.rl_routes_b = nullptr; w.rl_routes_0 = nullptr; w.rl_routes_c = nullptr; w.path_pool = nullptr; w.segs = nullptr; w.reps = nullptr; w.src_item = nullptr; w.rec_slot = nullptr;
@@ -6070,6 +6197,23 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   locality_used_ = false;
   const uint32_t count_grid = (uint32_t)((P + 255) / 256);
   const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);
+  const bool balls = (mode_mask_ & g.ball_mask) != 0u;
+  // A stage's five hand-over tiers are empty launches (~4.7 us each on the in-order stream) when
+  // its ball tier hands nothing over, so they are not launched once the matcher's last two runs
+  // ended with that stage's lists empty.  The prediction is checked on the device every run: items
+  // handed over after all gate the later stages off (gate bits 8 and 16), and the host runs the
+  // batch again the ordinary way and launches the tiers until two clean runs have passed.
+  // RM_STEADY_TIERS=0 always launches them (A/B; read per run: tests switch it).
+  const char* tiers_env = std::getenv("RM_STEADY_TIERS");
+  const bool may_skip = balls && !(tiers_env && *tiers_env == '0');
+  const bool skip_routes = may_skip && clean_routes_ >= 2;
+  const bool skip_paths = may_skip && clean_paths_ >= 2;
+  if (skip_paths) v.gate |= 16u;
+  DevBatch vk = v;   // the routes stage's own view: its ball tier is what counts ctl[1]
+  if (skip_routes) v.gate |= 8u;
+  ++run_stats_[0];
+  if (skip_routes) ++run_stats_[2];
+  if (skip_paths) ++run_stats_[3];
   // the hand-over tiers' grids from the previous run's list lengths (each is a grid-stride loop:
   // any grid is correct, and a list that grew runs on fewer blocks than it could): mostly empty
   // launches of 64 blocks instead of up to 4,096
@@ -6091,34 +6235,37 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   toc(kKCandidates);
   tic(kKScan);
   hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
-  hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, count_grid, w.tot64);
-  hipLaunchKernelGGL(k_scan_apply2, dim3(count_grid), dim3(256), 0, st, (const uint32_t*)w.trans_cnt,
-                     (const uint32_t*)w.src_cnt, P, (const unsigned long long*)w.tot_part, w.trans_off, w.src_off);
+  hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(count_grid) + 3) / 4), dim3(256), 0, st,
+                     (const unsigned long long*)w.tot_part, count_grid, w.scan_bkt);
+  hipLaunchKernelGGL(k_trans_apply_steady, dim3(count_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
+                     (const unsigned long long*)w.scan_bkt, w.tot64);
   toc(kKScan);
-  const bool balls = (mode_mask_ & g.ball_mask) != 0u;
   const uint32_t item_grid = (uint32_t)((src_cover + kK2Items - 1) / kK2Items);
   const uint32_t lane_grid = (uint32_t)((src_cover + 255) / 256);
   tic(kKRoutes);
-  hipLaunchKernelGGL(k_src_items, dim3(count_grid), dim3(256), 0, st, v);
   if (balls) {
     if (v.route_d) {
-      hipLaunchKernelGGL(k_routes_ball2<true>, dim3(item_grid), dim3(kK2Threads), 0, st, g, v, kNone);
-      hipLaunchKernelGGL(k_turn_walks, dim3(item_grid), dim3(kWalkThreads), 0, st, g, v, kNone);
-      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, v);
+      hipLaunchKernelGGL(k_routes_ball2<true>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, kNone);
+      hipLaunchKernelGGL(k_turn_walks, dim3(item_grid), dim3(kWalkThreads), 0, st, g, vk, kNone);
+      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, vk);
     } else {
-      hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, v, kNone);
+      hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, kNone);
     }
-    const uint32_t lg = std::min<uint32_t>(lane_grid, sgrid(kListedGrid, 1, 256));
-    if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-    else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
+    if (!skip_routes) {
+      const uint32_t lg = std::min<uint32_t>(lane_grid, sgrid(kListedGrid, 1, 256));
+      if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
+      else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
+    }
   } else {
     if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
     else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
   }
-  hipLaunchKernelGGL(k_routes_reg2, dim3(sgrid(kReg2Grid, 3, 256)), dim3(256), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_grp, dim3(sgrid(kGrpGrid, 5, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
-  hipLaunchKernelGGL(k_routes_wave_s, dim3(sgrid(kMidGrid, 11, 1)), dim3(64), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_wave, dim3(sgrid(1024, 13, 1)), dim3(64), 0, st, g, v, 0);
+  if (!skip_routes) {
+    hipLaunchKernelGGL(k_routes_reg2, dim3(sgrid(kReg2Grid, 3, 256)), dim3(256), 0, st, g, v);
+    hipLaunchKernelGGL(k_routes_grp, dim3(sgrid(kGrpGrid, 5, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
+    hipLaunchKernelGGL(k_routes_wave_s, dim3(sgrid(kMidGrid, 11, 1)), dim3(64), 0, st, g, v);
+    hipLaunchKernelGGL(k_routes_wave, dim3(sgrid(1024, 13, 1)), dim3(64), 0, st, g, v, 0);
+  }
   if (w.gsearch) hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
   toc(kKRoutes);
   tic(kKViterbi);
@@ -6127,23 +6274,26 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   tic(kKPaths);
   if (balls) {
     hipLaunchKernelGGL(k_paths_ball, dim3(count_grid), dim3(256), 0, st, g, v);
-    hipLaunchKernelGGL(k_paths_lane, dim3(std::min<uint32_t>(count_grid, sgrid(kListedGrid, 8, 256))), dim3(256), 0, st, g, v, 1);
+    if (!skip_paths)
+      hipLaunchKernelGGL(k_paths_lane, dim3(std::min<uint32_t>(count_grid, sgrid(kListedGrid, 8, 256))), dim3(256), 0, st, g, v, 1);
   } else {
     hipLaunchKernelGGL(k_paths_lane, dim3(count_grid), dim3(256), 0, st, g, v, 0);
   }
-  hipLaunchKernelGGL(k_paths_reg2, dim3(sgrid(kReg2Grid, 4, 256)), dim3(256), 0, st, g, v);
-  hipLaunchKernelGGL(k_paths_grp, dim3(sgrid(kGrpGrid, 6, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
-  hipLaunchKernelGGL(k_paths_wave_s, dim3(sgrid(kMidGrid, 12, 1)), dim3(64), 0, st, g, v);
-  hipLaunchKernelGGL(k_paths_wave, dim3(sgrid(1024, 14, 1)), dim3(64), 0, st, g, v, 0);
+  if (!skip_paths) {
+    hipLaunchKernelGGL(k_paths_reg2, dim3(sgrid(kReg2Grid, 4, 256)), dim3(256), 0, st, g, v);
+    hipLaunchKernelGGL(k_paths_grp, dim3(sgrid(kGrpGrid, 6, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
+    hipLaunchKernelGGL(k_paths_wave_s, dim3(sgrid(kMidGrid, 12, 1)), dim3(64), 0, st, g, v);
+    hipLaunchKernelGGL(k_paths_wave, dim3(sgrid(1024, 14, 1)), dim3(64), 0, st, g, v, 0);
+  }
   if (w.gsearch) hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
   toc(kKPaths);
   tic(kKSegments);
   hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
-  hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, sum_grid, w.tot64 + 2);
-  hipLaunchKernelGGL(k_scan_apply4, dim3(sum_grid), dim3(256), 0, st, (const uint32_t*)w.path_cnt, P,
-                     (const unsigned long long*)w.tot_part, w.trav_off);
+  hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(sum_grid) + 3) / 4), dim3(256), 0, st,
+                     (const unsigned long long*)w.tot_part, sum_grid, w.scan_bkt);
+  hipLaunchKernelGGL(k_path_apply_steady, dim3(sum_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
+                     (const unsigned long long*)w.scan_bkt, w.tot64, w.rec_slot);
   if (rp.do_report && rp.zero_hist) zero_hist(rp);
-  hipLaunchKernelGGL(k_rec_slot, dim3(count_grid), dim3(256), 0, st, v, w.rec_slot);
   hipLaunchKernelGGL(k_seg_wave, dim3(T), dim3(64), 0, st, g, v, (const uint32_t*)w.rec_slot, kNone, report_args(rp));
   toc(kKSegments);
   RM_HIP(hipGetLastError());
@@ -6151,13 +6301,16 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   RM_HIP(hipMemcpyAsync(htot, w.tot64, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   sync();
   if (htot[0] > w.cap_trans || htot[1] > src_cover || (hctl_[2] & kErrPathOverflow) ||
-      (!w.gsearch && (hctl_[9] | hctl_[10])) || htot[2] > v.seg_cap)
+      (!w.gsearch && (hctl_[9] | hctl_[10])) || htot[2] > v.seg_cap || (skip_routes && hctl_[1]) ||
+      (skip_paths && hctl_[8])) {
+    ++run_stats_[1];
     return false;
+  }
   n_trans_ = htot[0];
   n_path_ = htot[2];
   seg_used_ = htot[2];
   steady_src_ = htot[1];
-  std::memcpy(steady_ctl_, hctl_, sizeof(steady_ctl_));
+  keep_ctl();
   has_report_ = rp.do_report != 0;
   err_bits_ = hctl_[2] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
   if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
@@ -6388,7 +6541,9 @@ void Matcher::run_device(const RunParams& rp) {
   has_report_ = rp.do_report != 0;
   if (!locality_used_) {
     steady_src_ = steady_next;
-    std::memcpy(steady_ctl_, hctl_, sizeof(steady_ctl_));
+    keep_ctl();
+  } else {
+    count_clean(hctl_);   // (a run in locality order hands over what a steady run of the batch would)
   }
   err_bits_ = hctl_[2] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
   if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
@@ -6509,6 +6664,21 @@ void Matcher::get_paths(uint32_t* path_off, uint32_t* path_cnt, uint32_t* pool, 
     std::memcpy(pool + at, src, n * 4ull);
     at += n;
   }
+}
+
+// the completed run's control words for the next steady run: its tier grids, and how many runs
+// in a row ended with a stage's hand-over lists empty (run_steady then leaves the tiers out)
+void Matcher::keep_ctl() {
+  std::memcpy(steady_ctl_, hctl_, sizeof(steady_ctl_));
+  count_clean(steady_ctl_);
+}
+void Matcher::count_clean(const uint32_t* c) {
+  clean_routes_ = (c[1] | c[3] | c[5] | c[11] | c[13]) ? 0u : std::min(clean_routes_ + 1u, 2u);
+  clean_paths_ = (c[8] | c[4] | c[6] | c[12] | c[14]) ? 0u : std::min(clean_paths_ + 1u, 2u);
+}
+
+void Matcher::run_stats(uint64_t* out4) const {
+  for (int i = 0; i < 4; ++i) out4[i] = run_stats_[i];
 }
 
 void Matcher::ctl_words(uint32_t* out) {

@@ -168,6 +168,7 @@ struct Workspace {
   uint32_t* rl_routes_c = nullptr; uint32_t* rl_paths_c = nullptr; void* gsearch = nullptr;
   uint32_t* trace_err = nullptr;            // per trace: error bits (kErr*) of that trace alone
   unsigned long long* tot64 = nullptr;      // u64 totals: [0] transitions [1] sources [2] path edges
+  unsigned long long* scan_bkt = nullptr;   // a steady run's coarse scan buckets (rm_common.hpp scan_base_lane)
   unsigned long long* tot_part = nullptr;   // per-block partial pairs of those totals (k_sum_parts folds them)
   // locality order (engine.hip k_loc_count / k_loc_scatter): the sorted state slots, each slot's
   // region bucket, the bucket cursors and the item counts in sorted order; allocated on the first
@@ -316,6 +317,9 @@ class Matcher {
   void tier_counts(uint32_t* out4);
   // the kCtlWords control words of the last run (zeros before any run)
   void ctl_words(uint32_t* out);
+  // since creation: [0] steady runs [1] steady runs gated off and run again the ordinary way
+  // [2] steady runs without the routes stage's hand-over tiers [3] ... without the path stage's
+  void run_stats(uint64_t* out4) const;
   void reset_kernel_times();
   void set_timing(bool on) { timing_mask_ = on ? ~0u : 0u; }
   void set_timing_mask(uint32_t mask) { timing_mask_ = mask; }   // bit k: stage k (kernel_name)
@@ -386,6 +390,10 @@ class Matcher {
   bool run_steady(const RunParams& rp, const DevGraph& g);
   uint64_t steady_src_ = 0;    // the last ordinary / steady run's K2 sources (0: no steady run yet)
   uint32_t steady_ctl_[16] = {0};   // ... and its control words (the hand-over lists' lengths)
+  uint32_t clean_routes_ = 0, clean_paths_ = 0;   // completed runs in a row (at most 2) with a stage's lists empty
+  uint64_t run_stats_[4] = {0, 0, 0, 0};          // run_stats()
+  void keep_ctl();
+  void count_clean(const uint32_t* ctl);
   void zero_hist(const RunParams& rp);
   void use_ws_inputs();
   void ensure_pack(uint64_t bytes);

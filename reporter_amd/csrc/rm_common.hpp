@@ -470,4 +470,22 @@ static_assert(sizeof(MatchedPoint) == 32, "MatchedPoint is two dwordx4");
 
 constexpr int kHistBins = 16;           // 10 km/h bins, 0..160 (reporter_service.py:133)
 
+// ---- block bases of the steady step's scans (engine.hip k_trans_apply_steady / k_path_apply_steady) ----
+// A counting kernel leaves one pair of u64 partials per block (part[2 * block]); every kScanGroup
+// of them are summed into one coarse bucket (bkt[2 * (block / kScanGroup)]).  Block blk's
+// base is the buckets of the groups before its own plus the partials before it inside its group:
+// at most nb / kScanGroup + kScanGroup - 1 pairs, which the apply block reads itself -- no
+// one-block scan between the two passes.  This is what lane `lane` of a block of `lanes` adds up;
+// the block's base is the sum over its lanes (any order: integers).
+constexpr uint32_t kScanGroup = 64;
+RM_HD uint32_t scan_bucket(uint32_t blk) { return blk / kScanGroup; }
+RM_HD uint32_t scan_buckets(uint32_t nb) { return (nb + kScanGroup - 1) / kScanGroup; }
+RM_HD void scan_base_lane(const unsigned long long* part, const unsigned long long* bkt, uint32_t blk, uint32_t lane,
+                          uint32_t lanes, unsigned long long& a, unsigned long long& c) {
+  const uint32_t g = scan_bucket(blk);
+  a = 0; c = 0;
+  for (uint32_t q = lane; q < g; q += lanes) { a += bkt[2 * q]; c += bkt[2 * q + 1]; }
+  for (uint32_t q = g * kScanGroup + lane; q < blk; q += lanes) { a += part[2 * q]; c += part[2 * q + 1]; }
+}
+
 }  // namespace rm

@@ -273,6 +273,14 @@ class BatchMatcher:
                          "wave_to_global", "paths_wave_to_global", "group_to_wave512", "paths_group_to_wave512",
                          "wave512_to_wave4096", "paths_wave512_to_wave4096"), [int(x) for x in out]))
 
+    def run_stats(self):
+        """Counters since creation: steady runs, steady runs gated off on the device and run again
+        the ordinary way, and steady runs that left out the routes / path stage's hand-over tiers."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rm_runner_run_stats(self._h, out))
+        return dict(zip(("steady", "steady_rerun", "routes_tiers_skipped", "paths_tiers_skipped"),
+                        [int(x) for x in out]))
+
     # ---- stage outputs (parity tests) ----
     def states(self):
         s = self.sizes()

@@ -1371,10 +1371,12 @@ int rm_runner_route_tiers(rm_runner* r, uint64_t out[10]) {
   return guarded([&] {
     uint32_t c[kCtlWords];
     r->m->ctl_words(c);
-    out[0] = c[1]; out[1] = c[3]; out[2] = c[5]; out[3] = c[8]; out[4] = c[9]; out[5] = c[10];
-    out[6] = c[11]; out[7] = c[12]; out[8] = c[13]; out[9] = c[14];
+    out[0] = c[kCtlBallToSearch]; out[1] = c[kCtlLaneToReg2]; out[2] = c[kCtlReg2ToGroup];
+    out[3] = c[kCtlPathsBallToSearch]; out[4] = c[kCtlWaveToGlobal]; out[5] = c[kCtlPathsWaveToGlobal];
+    out[6] = c[kCtlGroupToWave512]; out[7] = c[kCtlPathsGroupToWave512];
+    out[8] = c[kCtlWave512ToWave4096]; out[9] = c[kCtlPathsWave512ToWave4096];
 #ifdef RM_K2_STATS
-    out[9] = c[15];   // diagnostic build: K2's walked turn weights
+    out[9] = c[kCtlWalkOverflow];   // diagnostic build: K2's walked turn weights
 #endif
   });
 }

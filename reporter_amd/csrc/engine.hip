@@ -72,12 +72,7 @@ struct DevBatch {  // POD view of the workspace for kernels
   SegmentRec* segs; uint32_t* seg_base; uint32_t* seg_cnt;
   uint32_t* trav_off;
   ReportRec* reps; uint32_t* rep_cnt; ReportStats* stats;
-  // control words: [0] path pool used [2] error flags [3] routes list A [4] paths list A
-  // [5] routes list B [6] paths list B [7] candidates list [8] path ball hand-overs
-  // [9] routes list C [10] paths list C (the global-memory search tier)
-  // [11] routes list B2 [12] paths list B2 (the group tier's hand-overs to the 512-slot wave tier)
-  // [13] routes list B3 [14] paths list B3 (the 512-slot tier's hand-overs to the 4096-slot one)
-  uint32_t* rl_routes_0;  // items the K2 ball tier hands to the search tiers (count ctl[1])
+  uint32_t* rl_routes_0;  // items the K2 ball tier hands to the search tiers (count ctl[kCtlBallToSearch])
   uint32_t* ctl; uint32_t* rl_routes_a; uint32_t* rl_routes_b; uint32_t* rl_paths_a; uint32_t* rl_paths_b;
   uint32_t* rl_cand;
   uint32_t* rl_routes_c; uint32_t* rl_paths_c;
@@ -89,17 +84,9 @@ struct DevBatch {  // POD view of the workspace for kernels
   const uint32_t* perm;
   const uint32_t* perm_paths;   // perm for the path stage too (null: the path stage takes slot order)
   uint32_t search_delta;        // cm: the wave tiers' delta-stepping width (kNone: plain rounds)
-  // small runs (Matcher::run_small): the u64 totals the launches size themselves from on the
-  // device (Workspace::tot64), the traversal-record capacity, and gate bits -- 1: K4, the report
-  // and the segment gather skip a run whose path pool overflowed or whose records exceed seg_cap
-  // (the host then runs the batch the ordinary way); 2: also one that handed searches to the
-  // global-memory tier, which a small run does not launch before its scratch exists
-  // 4: a steady run (Matcher::run_steady) sized from the pools an earlier run of the matcher left:
-  // every stage after the transition scan skips a batch with more transitions or K2 sources than
-  // trans_cap / src_cap (steady_abort), and the host re-runs it the ordinary way
-  // 8: a steady run that did not launch the routes stage's hand-over tiers (the matcher's last runs
-  // handed nothing over): items handed over after all (ctl[1]) make K3 and everything after it skip;
-  // 16: likewise the path stage's tiers (ctl[8]): K4 and the report skip.  The host re-runs either.
+  // runs without read-backs (Matcher::run_small, run_steady): the u64 totals the launches size
+  // themselves from on the device (Workspace::tot64), the capacities a batch may not outgrow, and
+  // the GateBit bits saying which of them the kernels check
   const unsigned long long* tot;
   uint64_t seg_cap;
   uint64_t trans_cap, src_cap;
@@ -107,14 +94,16 @@ struct DevBatch {  // POD view of the workspace for kernels
 };
 
 __device__ __forceinline__ bool steady_abort(const DevBatch& b) {
-  return ((b.gate & 4u) && (b.tot[0] > b.trans_cap || b.tot[1] > b.src_cap)) || ((b.gate & 8u) && b.ctl[1] != 0u);
+  return ((b.gate & kGateSteady) && (b.tot[0] > b.trans_cap || b.tot[1] > b.src_cap)) ||
+         ((b.gate & kGateRoutesTiers) && b.ctl[kCtlBallToSearch] != 0u);
 }
 
 __device__ __forceinline__ bool small_abort(const DevBatch& b) {
   if (!b.gate) return false;
   const uint32_t* c = b.ctl;
-  return (c[2] & kErrPathOverflow) != 0u || ((b.gate & 2u) && (c[9] | c[10]) != 0u) || b.tot[2] > b.seg_cap ||
-         ((b.gate & 16u) && c[8] != 0u) || steady_abort(b);
+  return (c[kCtlErr] & kErrPathOverflow) != 0u ||
+         ((b.gate & kGateGlobal) && (c[kCtlWaveToGlobal] | c[kCtlPathsWaveToGlobal]) != 0u) || b.tot[2] > b.seg_cap ||
+         ((b.gate & kGatePathsTiers) && c[kCtlPathsBallToSearch] != 0u) || steady_abort(b);
 }
 
 // A failure that belongs to one trajectory (too many roads in a radius, a search beyond every
@@ -122,7 +111,7 @@ __device__ __forceinline__ bool small_abort(const DevBatch& b) {
 // one request (py/reporter_service.py:244-245) or skips one window (py/simple_reporter.py:169-173).
 __device__ __forceinline__ void trace_fail(const DevBatch& b, uint64_t p, uint32_t bit) {
   atomicOr(&b.trace_err[b.slot_trace[p]], bit);
-  atomicOr(&b.ctl[2], bit);
+  atomicOr(&b.ctl[kCtlErr], bit);
 }
 
 __device__ __forceinline__ bool edge_ok(uint32_t info, uint32_t acc) { return (((info >> 16) & 7u) & acc) != 0u; }
@@ -648,7 +637,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
     }
   }
   if (ovf) {
-    const uint32_t q = atomicAdd(&b.ctl[7], 1u);
+    const uint32_t q = atomicAdd(&b.ctl[kCtlK1LaneToWave], 1u);
     b.rl_cand[q] = (uint32_t)p;
     return;
   }
@@ -809,11 +798,11 @@ __device__ void cand_wave_one(const DevGraph& g, const DevBatch& b, CandSmem& sm
   if (lane == 0) b.cand_n[p] = (uint8_t)min(n_found, (uint32_t)kMaxCand);
 }
 
-// all = 0: the lane tier's hand-overs (ctl[7]); all = 1: every state slot of the batch (small
+// all = 0: the lane tier's hand-overs (ctl[kCtlK1LaneToWave]); all = 1: every state slot of the batch (small
 // runs: one wave per state is a few rounds of loads where a lane walks its cells one by one)
 __global__ void __launch_bounds__(64) k_candidates_wave(DevGraph g, DevBatch b, int all) {
   __shared__ CandSmem sm;
-  const uint32_t n_items = all ? (uint32_t)b.P : min(b.ctl[7], (uint32_t)b.P);
+  const uint32_t n_items = all ? (uint32_t)b.P : min(b.ctl[kCtlK1LaneToWave], (uint32_t)b.P);
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t p = all ? item : b.rl_cand[item];
     if (all) {
@@ -872,6 +861,59 @@ __device__ __forceinline__ void block_excl_scan2(unsigned long long a, unsigned 
   ec = bc + ic - c;
 }
 
+// The same inside a block of 256 on N u32 counts per lane (one of each array): a block's counts sum
+// to < 2^32 (at most 256 x 16 x 16), so the scan runs on u32 -- wave shuffles, then the four wave
+// totals through LDS.  e: the exclusive sums.  Every lane of the block calls it (it holds a barrier).
+template <int N>
+__device__ __forceinline__ void block256_excl_scan_u32(const uint32_t (&v)[N], uint32_t (&e)[N]) {
+  __shared__ uint32_t s[N][4];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  uint32_t iv[N];
+#pragma unroll
+  for (int j = 0; j < N; ++j) iv[j] = v[j];
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      const uint32_t t = __shfl_up(iv[j], d, 64);
+      iv[j] += lane >= d ? t : 0u;
+    }
+  }
+  if (lane == 63) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) s[j][wv] = iv[j];
+  }
+#pragma unroll
+  for (int j = 0; j < N; ++j) e[j] = iv[j] - v[j];   // exclusive inside the wave
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+#pragma unroll
+    for (int j = 0; j < N; ++j) e[j] += w < wv ? s[j][w] : 0u;
+  }
+}
+
+// Four counts per lane (k_sum_u64's blocks of 1024): the lane's counts a[i .. i + 4), 0 past n ...
+__device__ __forceinline__ void load_counts4(const uint32_t* a, uint64_t i, uint64_t n, uint32_t (&v)[4]) {
+  v[0] = v[1] = v[2] = v[3] = 0u;
+  if (i + 4 <= n) {
+    const uint4 q = *reinterpret_cast<const uint4*>(a + i);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+    for (uint64_t x = i; x < n; ++x) v[x - i] = a[x];
+  }
+}
+// ... and their offsets ao[i .. i + 4) from the offset of the lane's first
+__device__ __forceinline__ void store_offsets4(uint32_t* ao, uint64_t i, uint64_t n, uint32_t o0, const uint32_t (&v)[4]) {
+  const uint32_t o1 = o0 + v[0], o2 = o1 + v[1], o3 = o2 + v[2];
+  if (i + 4 <= n) {
+    *reinterpret_cast<uint4*>(ao + i) = make_uint4(o0, o1, o2, o3);
+  } else {
+    const uint32_t o[4] = {o0, o1, o2, o3};
+    for (uint64_t x = i; x < n; ++x) ao[x] = o[x - i];
+  }
+}
+
 __global__ void __launch_bounds__(1024) k_scan_parts(unsigned long long* part, uint32_t nb, unsigned long long* out) {
   __shared__ unsigned long long sa[16], sc[16];
   const uint32_t per = (nb + 1023u) / 1024u;
@@ -892,10 +934,11 @@ __global__ void __launch_bounds__(1024) k_scan_parts(unsigned long long* part, u
   if (threadIdx.x == 1023) { out[0] = ea; out[1] = ec; }
 }
 
-// one count of each array per thread, blocks of 256 (k_trans_count's partials); a block's
-// counts sum to < 2^32 (at most 256 x 16 x 16), so the in-block scan runs on u32 pairs
+// one count of each array per thread, blocks of 256 (k_trans_count's partials)
 __global__ void __launch_bounds__(256) k_scan_apply2(const uint32_t* a, const uint32_t* c, uint64_t n,
                                                      const unsigned long long* part, uint32_t* ao, uint32_t* co) {
+  // (block256_excl_scan_u32 written out: through the helper the two stores' addresses are formed
+  // together, at two more VGPRs)
   __shared__ uint32_t sa[4], sc[4];
   const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   const ulonglong2 base = reinterpret_cast<const ulonglong2*>(part)[blockIdx.x];
@@ -926,23 +969,11 @@ __global__ void __launch_bounds__(256) k_scan_apply4(const uint32_t* a, uint64_t
                                                      uint32_t* ao) {
   __shared__ unsigned long long sa[4], sc[4];
   const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
-  uint32_t v[4] = {0u, 0u, 0u, 0u};
-  if (i + 4 <= n) {
-    const uint4 q = *reinterpret_cast<const uint4*>(a + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    for (uint64_t x = i; x < n; ++x) v[x - i] = a[x];
-  }
+  uint32_t v[4];
+  load_counts4(a, i, n, v);
   unsigned long long ea, ec;
   block_excl_scan2((unsigned long long)v[0] + v[1] + v[2] + v[3], 0ull, ea, ec, sa, sc, 4);
-  const unsigned long long base = part[2 * blockIdx.x] + ea;
-  const uint32_t o0 = (uint32_t)base, o1 = o0 + v[0], o2 = o1 + v[1], o3 = o2 + v[2];
-  if (i + 4 <= n) {
-    *reinterpret_cast<uint4*>(ao + i) = make_uint4(o0, o1, o2, o3);
-  } else {
-    const uint32_t o[4] = {o0, o1, o2, o3};
-    for (uint64_t x = i; x < n; ++x) ao[x] = o[x - i];
-  }
+  store_offsets4(ao, i, n, (uint32_t)(part[2 * blockIdx.x] + ea), v);
 }
 
 __global__ void __launch_bounds__(256) k_perm_src_count(DevBatch b, uint32_t* pcnt, unsigned long long* part) {
@@ -957,23 +988,12 @@ __global__ void __launch_bounds__(256) k_perm_src_count(DevBatch b, uint32_t* pc
 }
 __global__ void __launch_bounds__(256) k_scan_apply_perm(const uint32_t* a, uint64_t n, const unsigned long long* part,
                                                          const uint32_t* perm, uint32_t* src_off) {
-  __shared__ uint32_t sa[4];
   const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   const uint32_t base = (uint32_t)reinterpret_cast<const ulonglong2*>(part)[blockIdx.x].x;
-  const uint32_t v = r < n ? a[r] : 0u;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t iv = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t t = __shfl_up(iv, d, 64);
-    if (lane >= d) iv += t;
-  }
-  if (lane == 63) sa[wv] = iv;
-  __syncthreads();
-  uint32_t bb = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) bb += w < wv ? sa[w] : 0u;
-  if (r < n && v) src_off[perm[r] + 1u] = base + bb + iv - v;
+  const uint32_t v[1] = {r < n ? a[r] : 0u};
+  uint32_t e[1];
+  block256_excl_scan_u32(v, e);
+  if (r < n && v[0]) src_off[perm[r] + 1u] = base + e[0];
 }
 
 // transition counts for the exclusive scan that lays out route[] compactly, plus the
@@ -1050,29 +1070,15 @@ __global__ void __launch_bounds__(256) k_trans_apply_small(DevBatch b, const uns
   unsigned long long pre[2], all[2];
   block_prefix_parts(part, nb, blockIdx.x, pre, all);
   if (blockIdx.x == 0 && threadIdx.x == 0) { tot[0] = all[0]; tot[1] = all[1]; }
-  __shared__ uint32_t sa[4], sc[4];
   const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const uint32_t va = p < b.P ? b.trans_cnt[p] : 0u, vc = p < b.P ? b.src_cnt[p] : 0u;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t ia = va, ic = vc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ta = __shfl_up(ia, d, 64), tc = __shfl_up(ic, d, 64);
-    if (lane >= d) { ia += ta; ic += tc; }
-  }
-  if (lane == 63) { sa[wv] = ia; sc[wv] = ic; }
-  __syncthreads();
-  uint32_t ba = 0, bc = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    ba += w < wv ? sa[w] : 0u;
-    bc += w < wv ? sc[w] : 0u;
-  }
+  const uint32_t v[2] = {p < b.P ? b.trans_cnt[p] : 0u, p < b.P ? b.src_cnt[p] : 0u};
+  uint32_t e[2];
+  block256_excl_scan_u32(v, e);
   if (p < b.P) {
-    const uint32_t at = (uint32_t)pre[1] + bc + ic - vc;
-    b.trans_off[p] = (uint32_t)pre[0] + ba + ia - va;
+    const uint32_t at = (uint32_t)pre[1] + e[1];
+    b.trans_off[p] = (uint32_t)pre[0] + e[0];
     b.src_off[p] = at;
-    for (uint32_t i = 0; i < vc; ++i) b.src_item[at + i] = (uint32_t)p;
+    for (uint32_t i = 0; i < v[1]; ++i) b.src_item[at + i] = (uint32_t)p;
   }
 }
 
@@ -1146,35 +1152,21 @@ __global__ void __launch_bounds__(256) k_trans_apply_steady(DevBatch b, const un
                                                             const unsigned long long* bkt, unsigned long long* tot) {
   // (the counts first: their loads are in flight while the base is formed)
   const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const uint32_t va = p < b.P ? b.trans_cnt[p] : 0u, vc = p < b.P ? b.src_cnt[p] : 0u;
+  const uint32_t v[2] = {p < b.P ? b.trans_cnt[p] : 0u, p < b.P ? b.src_cnt[p] : 0u};
   unsigned long long pre[2];
   block_base_parts(part, bkt, pre);
-  __shared__ uint32_t sa[4], sc[4];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t ia = va, ic = vc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ta = __shfl_up(ia, d, 64), tc = __shfl_up(ic, d, 64);
-    if (lane >= d) { ia += ta; ic += tc; }
-  }
-  if (lane == 63) { sa[wv] = ia; sc[wv] = ic; }
-  __syncthreads();
-  uint32_t ba = 0, bc = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    ba += w < wv ? sa[w] : 0u;
-    bc += w < wv ? sc[w] : 0u;
-  }
+  uint32_t e[2];
+  block256_excl_scan_u32(v, e);
   if (p < b.P) {
-    const unsigned long long at = pre[1] + bc + ic - vc;
-    b.trans_off[p] = (uint32_t)(pre[0] + ba + ia - va);
+    const unsigned long long at = pre[1] + e[1];
+    b.trans_off[p] = (uint32_t)(pre[0] + e[0]);
     b.src_off[p] = (uint32_t)at;
-    for (uint32_t i = 0; i < vc; ++i)
+    for (uint32_t i = 0; i < v[1]; ++i)
       if (at + i < b.src_cap) b.src_item[at + i] = (uint32_t)p;
   }
   if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {   // (lanes past P counted 0)
-    tot[0] = pre[0] + ba + ia;
-    tot[1] = pre[1] + bc + ic;
+    tot[0] = pre[0] + e[0] + v[0];
+    tot[1] = pre[1] + e[1] + v[1];
   }
 }
 
@@ -1186,26 +1178,16 @@ __global__ void __launch_bounds__(256) k_path_apply_steady(DevBatch b, const uns
   __shared__ unsigned long long sa[4], sc[4];
   const uint64_t n = b.P;
   const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
-  uint32_t v[4] = {0u, 0u, 0u, 0u};
-  if (i + 4 <= n) {
-    const uint4 q = *reinterpret_cast<const uint4*>(b.path_cnt + i);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    for (uint64_t x = i; x < n; ++x) v[x - i] = b.path_cnt[x];
-  }
+  // (the counts first: their loads are in flight while the base is formed)
+  uint32_t v[4];
+  load_counts4(b.path_cnt, i, n, v);
   unsigned long long pre[2];
   block_base_parts(part, bkt, pre);
   const unsigned long long mine = (unsigned long long)v[0] + v[1] + v[2] + v[3];
   unsigned long long ea, ec;
   block_excl_scan2(mine, 0ull, ea, ec, sa, sc, 4);
   const unsigned long long base = pre[0] + ea;
-  const uint32_t o0 = (uint32_t)base, o1 = o0 + v[0], o2 = o1 + v[1], o3 = o2 + v[2];
-  if (i + 4 <= n) {
-    *reinterpret_cast<uint4*>(b.trav_off + i) = make_uint4(o0, o1, o2, o3);
-  } else {
-    const uint32_t o[4] = {o0, o1, o2, o3};
-    for (uint64_t x = i; x < n; ++x) b.trav_off[x] = o[x - i];
-  }
+  store_offsets4(b.trav_off, i, n, (uint32_t)base, v);
   unsigned long long o = base;
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
@@ -2369,7 +2351,7 @@ __device__ __forceinline__ void k2_phase2_turn1(const DevGraph& g, SM& sm, const
       } else {   // marked in place for k_turn_walks_marked
         b.route[A.obase + q] = kRouteWalk;
         b.route_d[A.obase + q] = __longlong_as_double((long long)((unsigned long long)item << 4 | (di & 15u)));
-        b.ctl[15] = 1u;
+        b.ctl[kCtlWalkOverflow] = 1u;
       }
     }
   }
@@ -2431,7 +2413,7 @@ __device__ void k2_walk_one(const DevGraph& g, const DevBatch& b, uint32_t t, ui
   b.route[ro] = k2_route_turn(g, A, T, ta0, ta1, r1, r0, s1, s0, h1s, h0s, make_uint2(v1.x, v1.y),
                               make_uint2(v0.x, v0.y), g.turn_w, gc, ok, d);
   b.route_d[ro] = d;
-  if (!ok) b.rl_routes_0[atomicAdd(&b.ctl[1], 1u)] = t;
+  if (!ok) b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
 }
 // (launched with K2's grid and n_arg, one block per K2 block: the block's region of b.walk)
 #ifndef RM_WALK_THREADS
@@ -2453,9 +2435,9 @@ __global__ void __launch_bounds__(kWalkThreads) k_turn_walks(DevGraph g, DevBatc
 constexpr uint32_t kWalkScanGrid = 2048;
 // the walks a K2 block could not list (more than kWalkPerBlock): marked in place -- route
 // kRouteWalk, route_d's bits the item and target -- and found by one scan of the routes, run only
-// when some block overflowed (ctl[15])
+// when some block overflowed (ctl[kCtlWalkOverflow])
 __global__ void __launch_bounds__(256) k_turn_walks_marked(DevGraph g, DevBatch b) {
-  if (steady_abort(b) || b.ctl[15] == 0u) return;
+  if (steady_abort(b) || b.ctl[kCtlWalkOverflow] == 0u) return;
   const uint64_t n = b.tot[0];
   for (uint64_t x = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (uint64_t)gridDim.x * blockDim.x) {
     if (b.route[x] != kRouteWalk) continue;
@@ -2525,7 +2507,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
     if constexpr (TURN) turn_ok = !pi.w || ((g.ball_turn_mask >> mode) & 1u);   // no turn rows: the search tiers weigh the turns
     if (!fits || S.h1.y == 0u || S.h0.y == 0u || !turn_ok) {   // the search tiers take it (they run later)
       S.bound = kNone;
-      b.rl_routes_0[atomicAdd(&b.ctl[1], 1u)] = t;
+      b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
     }
   }
   // the block's transitions: an exclusive scan of the items' K_B (in slot order the items' routes
@@ -2578,7 +2560,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
   // items with a route the tables could not decide: the search tiers recompute all of its routes
   __syncthreads();
   if (live && ((sm.redo[threadIdx.x >> 5] >> (threadIdx.x & 31u)) & 1u) && sm.src[threadIdx.x].bound != kNone)
-    b.rl_routes_0[atomicAdd(&b.ctl[1], 1u)] = t;
+    b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
   if constexpr (TURN) {   // the count of the block's region of b.walk
     if (threadIdx.x == 0) b.walk[(uint64_t)blockIdx.x * (kWalkPerBlock + 1)] = min(sm.wn, kWalkPerBlock);
   }
@@ -2588,7 +2570,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
 // K2 lane tier: one lane per (layer pair, source) item.  The pair constants come from
 // one dwordx4 (pair_info) and every candidate from its 32-byte descriptor.  A search
 // that outgrows the registers is queued (as its item) for the LDS lane tier.
-// With `listed`, thread q takes the q-th item the ball tier handed over (rl_routes_0, ctl[1]).
+// With `listed`, thread q takes the q-th item the ball tier handed over (rl_routes_0, ctl[kCtlBallToSearch]).
 constexpr uint64_t kListedGrid = 4096;   // blocks of a grid-stride launch over hand-over lists
 
 // TURN: compiled with the turn-weight walks (rule 3b) only for batches with turn costs (they
@@ -2597,7 +2579,7 @@ template <bool TURN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LANE_WPE))) k_routes_lane(DevGraph g, DevBatch b, uint32_t n_items, int listed) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   // grid-stride: a listed launch is sized for every item but usually finds few hand-overs
-  const uint32_t n = listed ? b.ctl[1] : (n_items != kNone ? n_items : (uint32_t)b.tot[1]);
+  const uint32_t n = listed ? b.ctl[kCtlBallToSearch] : (n_items != kNone ? n_items : (uint32_t)b.tot[1]);
   __shared__ uint32_t s_res[kMaxCand][256];
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
   const uint32_t t = listed ? b.rl_routes_0[q] : q;
@@ -2615,7 +2597,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
   // costs more than the settles it saves (C2 --ball-radius 0: 2.1 -> 3.4 ms); tier 2 has it
   lane_search(S, g, g.relax[mode], bound, a0, a1, rk1, rk0);
   if (S.ovf) {
-    b.rl_routes_a[atomicAdd(&b.ctl[3], 1u)] = t;
+    b.rl_routes_a[atomicAdd(&b.ctl[kCtlLaneToReg2], 1u)] = t;
     continue;
   }
   route_targets(g, b, StoreLabel<RegLabels>{S}, SearchPathLabels<RegLabels>{S}, a0, p, KB, bound, tmax,
@@ -2632,7 +2614,7 @@ constexpr int kTier2Cap = RM_TIER2_CAP;
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_routes_reg2(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ uint32_t s_res[kMaxCand][256];
-  const uint32_t n_items = b.ctl[3];
+  const uint32_t n_items = b.ctl[kCtlLaneToReg2];
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_items; q += gridDim.x * blockDim.x) {
     const uint32_t t = b.rl_routes_a[q];
     const uint32_t p = b.src_item[t];
@@ -2650,7 +2632,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
     lane_search(S, g, g.relax[mode], bound, a0, a1, rk1, rk0,
                 StopAtTargets{b.cand_desc + (uint64_t)p * kMaxCand * 2, bound >= kStopMinBoundCm ? KB : 0u, a0, 0ull, 0u});
     if (S.ovf) {
-      const uint32_t x = atomicAdd(&b.ctl[5], 1u);
+      const uint32_t x = atomicAdd(&b.ctl[kCtlReg2ToGroup], 1u);
       b.rl_routes_b[x] = t;
       continue;
     }
@@ -2745,8 +2727,8 @@ __device__ __forceinline__ void path_walk(const DevGraph& g, const DevBatch& b, 
     return;
   }
   // long path: pool slot, second walk writing in travel order
-  const uint32_t at = atomicAdd(&b.ctl[0], n);
-  if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[2], kErrPathOverflow); b.path_off[p] = kNone; return; }
+  const uint32_t at = atomicAdd(&b.ctl[kCtlPathUsed], n);
+  if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[kCtlErr], kErrPathOverflow); b.path_off[p] = kNone; return; }
   b.path_off[p] = at;
   uint32_t* dst = b.path_pool + at;
   dst[n - 1] = entry_e;
@@ -2842,8 +2824,8 @@ __device__ void path_walk_ball(const DevGraph& g, const DevBatch& b, uint64_t p,
     return;
   }
   // long path: pool slot, second walk writing in travel order
-  const uint32_t at = atomicAdd(&b.ctl[0], n);
-  if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[2], kErrPathOverflow); b.path_off[p] = kNone; return; }
+  const uint32_t at = atomicAdd(&b.ctl[kCtlPathUsed], n);
+  if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[kCtlErr], kErrPathOverflow); b.path_off[p] = kNone; return; }
   b.path_off[p] = at;
   uint32_t* dst = b.path_pool + at;
   dst[n - 1] = entry_e;
@@ -2862,7 +2844,7 @@ __device__ void path_walk_ball(const DevGraph& g, const DevBatch& b, uint64_t p,
 }
 
 // path ball tier: one lane per chosen transition whose bound fits the ball radius; the
-// others go to the search tiers (rl_routes_0 reused after K2, count ctl[8])
+// others go to the search tiers (rl_routes_0 reused after K2, count ctl[kCtlPathsBallToSearch])
 #ifndef RM_PATHS_WPE
 #define RM_PATHS_WPE 1
 #endif
@@ -2900,7 +2882,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
     if (rk0 != kKeyInf) h0 = x0;
   }
   if (!fits || h1.y == 0u || h0.y == 0u) {
-    b.rl_routes_0[atomicAdd(&b.ctl[8], 1u)] = (uint32_t)p;
+    b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsBallToSearch], 1u)] = (uint32_t)p;
     return;
   }
   const BallPathLabels lab{g.ball_ent[mode], h1, h0, rk1, rk0, g.ball_road_mask};
@@ -2913,7 +2895,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
   const unsigned long long key = route_key_vals(a0, b0, b1, lab0, lab1, &combo);
   const uint32_t lim = ball_exact_limit(bound, g.ball_radius[mode], rk1, rk0);
   if (lim != kNone && (key == kKeyInf || key_dist(key) > lim)) {   // not decided by the tables
-    b.rl_routes_0[atomicAdd(&b.ctl[8], 1u)] = (uint32_t)p;
+    b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsBallToSearch], 1u)] = (uint32_t)p;
     return;
   }
   path_walk_ball(g, b, p, lab, mode, a0, a1, b0, b1, key, combo, (int)kBallMaxKeys, r1, r0);
@@ -2926,10 +2908,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
   const uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t p = q0;
   if (listed) {   // grid-stride over the ball tier's hand-overs
-    const uint32_t n = b.ctl[8];
+    const uint32_t n = b.ctl[kCtlPathsBallToSearch];
     for (uint64_t q = q0; q < n; q += (uint64_t)gridDim.x * blockDim.x) {
       RegLabels S;
-      if (!lane_path(g, b, b.rl_routes_0[q], S, kLaneCap)) b.rl_paths_a[atomicAdd(&b.ctl[4], 1u)] = b.rl_routes_0[q];
+      if (!lane_path(g, b, b.rl_routes_0[q], S, kLaneCap)) b.rl_paths_a[atomicAdd(&b.ctl[kCtlPathsLaneToReg2], 1u)] = b.rl_routes_0[q];
     }
     return;
   } else {
@@ -2947,7 +2929,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
   }
   RegLabels S;
   if (!lane_path(g, b, p, S, kLaneCap)) {
-    const uint32_t q = atomicAdd(&b.ctl[4], 1u);
+    const uint32_t q = atomicAdd(&b.ctl[kCtlPathsLaneToReg2], 1u);
     b.rl_paths_a[q] = (uint32_t)p;
   }
 }
@@ -2955,12 +2937,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
 // path second register tier
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_paths_reg2(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  const uint32_t n_items = b.ctl[4];
+  const uint32_t n_items = b.ctl[kCtlPathsLaneToReg2];
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_items; q += gridDim.x * blockDim.x) {
     const uint32_t p = b.rl_paths_a[q];
     RegLabelsT<kTier2Cap> S;
     if (!lane_path(g, b, p, S, kTier2Cap)) {
-      const uint32_t x = atomicAdd(&b.ctl[6], 1u);
+      const uint32_t x = atomicAdd(&b.ctl[kCtlPathsReg2ToGroup], 1u);
       b.rl_paths_b[x] = p;
     }
   }
@@ -3017,8 +2999,8 @@ __device__ bool routes_search_item(SearchSmem<H, false>& sm, uint4* s_src, const
 // and touch tens of nodes: the group tier runs four of them per wave, 16 lanes and a kGrpH-slot
 // hash each (four searches in the LDS of one); what outgrows it goes to the 512-slot wave tier
 // (10 KB, 16 waves per CU), then to the 4096-slot one (80 KB, 2 waves per CU).  Hand-over lists:
-// group tier <- rl_routes_b (ctl[5]) -> rl_routes_a (ctl[11], free once tier 2 has run) -> 512
-// tier -> rl_routes_0 (ctl[13], free once the lane tier has run) -> 4096 tier -> rl_routes_c.
+// group tier <- rl_routes_b (ctl[kCtlReg2ToGroup]) -> rl_routes_a (ctl[kCtlGroupToWave512], free once tier 2 has run) -> 512
+// tier -> rl_routes_0 (ctl[kCtlWave512ToWave4096], free once the lane tier has run) -> 4096 tier -> rl_routes_c.
 #ifndef RM_GRP_H
 #define RM_GRP_H 256
 #endif
@@ -3030,7 +3012,7 @@ constexpr int kGrpPathH = RM_GRP_PATH_H;
 constexpr int kGrpW = 16;
 constexpr uint32_t kGrpGrid = 4096;   // blocks of the group tiers (grid-stride over their lists)
 // short: a small run's short hand-over chain (Matcher::run_small, round 6): the group tier takes
-// the ball tier's hand-overs (rl_routes_0, ctl[1]) itself and the 4096-slot tier takes the group
+// the ball tier's hand-overs (rl_routes_0, ctl[kCtlBallToSearch]) itself and the 4096-slot tier takes the group
 // tier's; the lane, second register and 512-slot tiers are not launched (three launches fewer;
 // every tier is exact, so the routes are the same)
 __global__ void __launch_bounds__(64) k_routes_grp(DevGraph g, DevBatch b, int short_chain) {
@@ -3038,12 +3020,12 @@ __global__ void __launch_bounds__(64) k_routes_grp(DevGraph g, DevBatch b, int s
   __shared__ SearchSmem<kGrpH, false> sm[kWave / kGrpW];
   __shared__ uint4 s_src[kWave / kGrpW][2];
   const int gi = threadIdx.x / kGrpW;
-  const uint32_t n_items = short_chain ? b.ctl[1] : b.ctl[5];
+  const uint32_t n_items = short_chain ? b.ctl[kCtlBallToSearch] : b.ctl[kCtlReg2ToGroup];
   const uint32_t* list = short_chain ? b.rl_routes_0 : b.rl_routes_b;
   for (uint32_t item = blockIdx.x * (kWave / kGrpW) + gi; item < n_items; item += gridDim.x * (kWave / kGrpW)) {
     const uint32_t t = list[item];
     if (!routes_search_item<kGrpH, kGrpW>(sm[gi], s_src[gi], g, b, t) && grp_lane<kGrpW>() == 0)
-      b.rl_routes_a[atomicAdd(&b.ctl[11], 1u)] = t;
+      b.rl_routes_a[atomicAdd(&b.ctl[kCtlGroupToWave512], 1u)] = t;
   }
 }
 
@@ -3051,10 +3033,10 @@ __global__ void __launch_bounds__(64) k_routes_wave_s(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ SearchSmem<kMidH, false> sm;
   __shared__ uint4 s_src[2];
-  const uint32_t n_items = b.ctl[11];
+  const uint32_t n_items = b.ctl[kCtlGroupToWave512];
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t t = b.rl_routes_a[item];
-    if (!routes_search_item<kMidH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[13], 1u)] = t;
+    if (!routes_search_item<kMidH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[kCtlWave512ToWave4096], 1u)] = t;
   }
 }
 
@@ -3062,11 +3044,11 @@ __global__ void __launch_bounds__(64) k_routes_wave(DevGraph g, DevBatch b, int 
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ SearchSmem<kBigH, false> sm;
   __shared__ uint4 s_src[2];
-  const uint32_t n_items = short_chain ? b.ctl[11] : b.ctl[13];   // (short: the group tier's hand-overs)
+  const uint32_t n_items = short_chain ? b.ctl[kCtlGroupToWave512] : b.ctl[kCtlWave512ToWave4096];   // (short: the group tier's hand-overs)
   const uint32_t* list = short_chain ? b.rl_routes_a : b.rl_routes_0;
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t t = list[item];
-    if (!routes_search_item<kBigH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_c[atomicAdd(&b.ctl[9], 1u)] = t;
+    if (!routes_search_item<kBigH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_c[atomicAdd(&b.ctl[kCtlWaveToGlobal], 1u)] = t;
   }
 }
 
@@ -3083,7 +3065,7 @@ __global__ void __launch_bounds__(64) k_routes_global(DevGraph g, DevBatch b, Gl
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ uint4 s_src[2];
   GlobalRouteSmem& sm = *reinterpret_cast<GlobalRouteSmem*>(scratch + blockIdx.x);
-  const uint32_t n_items = b.ctl[9];
+  const uint32_t n_items = b.ctl[kCtlWaveToGlobal];
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t t = b.rl_routes_c[item];
     if (!routes_search_item<kGlobalH>(sm, s_src, g, b, t) && threadIdx.x == 0) trace_fail(b, b.src_item[t], kErrSearchOverflow);
@@ -4018,8 +4000,8 @@ __device__ bool paths_search_item(SearchSmem<H, true>& sm, uint4* s_src, const D
     }
     uint32_t at = 0;
     if (n > (uint32_t)kInlinePath) {
-      at = atomicAdd(&b.ctl[0], n);
-      if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[2], kErrPathOverflow); at = kNone; }
+      at = atomicAdd(&b.ctl[kCtlPathUsed], n);
+      if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[kCtlErr], kErrPathOverflow); at = kNone; }
     }
     b.path_cnt[p] = n;
     b.path_off[p] = at;
@@ -4039,20 +4021,20 @@ __device__ bool paths_search_item(SearchSmem<H, true>& sm, uint4* s_src, const D
   return true;
 }
 
-// path tiers, as the route tiers: group tier <- rl_paths_b (ctl[6]) -> rl_paths_a (ctl[12]) ->
-// 512 tier -> rl_routes_0 (ctl[14], free once the path lane tier has run) -> 4096 tier -> rl_paths_c
-// (short_chain: the path ball tier's hand-overs, rl_routes_0 / ctl[8], as k_routes_grp's)
+// path tiers, as the route tiers: group tier <- rl_paths_b (ctl[kCtlPathsReg2ToGroup]) -> rl_paths_a (ctl[kCtlPathsGroupToWave512]) ->
+// 512 tier -> rl_routes_0 (ctl[kCtlPathsWave512ToWave4096], free once the path lane tier has run) -> 4096 tier -> rl_paths_c
+// (short_chain: the path ball tier's hand-overs, rl_routes_0 / ctl[kCtlPathsBallToSearch], as k_routes_grp's)
 __global__ void __launch_bounds__(64) k_paths_grp(DevGraph g, DevBatch b, int short_chain) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ SearchSmem<kGrpPathH, true> sm[kWave / kGrpW];
   __shared__ uint4 s_src[kWave / kGrpW][2];
   const int gi = threadIdx.x / kGrpW;
-  const uint32_t n_items = short_chain ? b.ctl[8] : b.ctl[6];
+  const uint32_t n_items = short_chain ? b.ctl[kCtlPathsBallToSearch] : b.ctl[kCtlPathsReg2ToGroup];
   const uint32_t* list = short_chain ? b.rl_routes_0 : b.rl_paths_b;
   for (uint32_t item = blockIdx.x * (kWave / kGrpW) + gi; item < n_items; item += gridDim.x * (kWave / kGrpW)) {
     const uint32_t p = list[item];
     if (!paths_search_item<kGrpPathH, kGrpW>(sm[gi], s_src[gi], g, b, p) && grp_lane<kGrpW>() == 0)
-      b.rl_paths_a[atomicAdd(&b.ctl[12], 1u)] = p;
+      b.rl_paths_a[atomicAdd(&b.ctl[kCtlPathsGroupToWave512], 1u)] = p;
   }
 }
 
@@ -4060,10 +4042,10 @@ __global__ void __launch_bounds__(64) k_paths_wave_s(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ SearchSmem<kMidH, true> sm;
   __shared__ uint4 s_src[2];
-  const uint32_t n_items = b.ctl[12];
+  const uint32_t n_items = b.ctl[kCtlPathsGroupToWave512];
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t p = b.rl_paths_a[item];
-    if (!paths_search_item<kMidH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[14], 1u)] = p;
+    if (!paths_search_item<kMidH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsWave512ToWave4096], 1u)] = p;
   }
 }
 
@@ -4071,11 +4053,11 @@ __global__ void __launch_bounds__(64) k_paths_wave(DevGraph g, DevBatch b, int s
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ SearchSmem<kBigH, true> sm;
   __shared__ uint4 s_src[2];
-  const uint32_t n_items = short_chain ? b.ctl[12] : b.ctl[14];
+  const uint32_t n_items = short_chain ? b.ctl[kCtlPathsGroupToWave512] : b.ctl[kCtlPathsWave512ToWave4096];
   const uint32_t* list = short_chain ? b.rl_paths_a : b.rl_routes_0;
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t p = list[item];
-    if (!paths_search_item<kBigH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_paths_c[atomicAdd(&b.ctl[10], 1u)] = p;
+    if (!paths_search_item<kBigH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_paths_c[atomicAdd(&b.ctl[kCtlPathsWaveToGlobal], 1u)] = p;
   }
 }
 
@@ -4083,7 +4065,7 @@ __global__ void __launch_bounds__(64) k_paths_global(DevGraph g, DevBatch b, Glo
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ uint4 s_src[2];
   GlobalPathSmem& sm = scratch[blockIdx.x];
-  const uint32_t n_items = b.ctl[10];
+  const uint32_t n_items = b.ctl[kCtlPathsWaveToGlobal];
   for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
     const uint32_t p = b.rl_paths_c[item];
     if (!paths_search_item<kGlobalH>(sm, s_src, g, b, p) && threadIdx.x == 0) trace_fail(b, p, kErrSearchOverflow);
@@ -6025,12 +6007,173 @@ void Matcher::zero_hist(const RunParams& rp) {
   if (rp.hist) RM_HIP(hipMemsetAsync(rp.hist, 0, (size_t)eng_->n_segments() * kHistBins * sizeof(uint32_t), stream_));
   if (rp.dur) RM_HIP(hipMemsetAsync(rp.dur, 0, (size_t)eng_->n_segments() * 8u, stream_));
 }
+
+// The three ways to run a batch -- run_small, run_steady and the ordinary rest of run_device --
+// launch the same stages through Matcher::Stages (k1, routes, paths, k4) and differ in
+// this plan (and in their scans and read-backs, which stay with them: DESIGN.md §5).
+struct TierGrids {   // one stage's hand-over tiers
+  bool launch;       // false: none is launched (a steady run whose last two runs handed nothing over)
+  uint32_t listed;   // the lane tier over the ball tier's hand-overs (at most the stage's lane grid)
+  uint32_t reg2, grp, wave_s, wave;
+};
+struct LaunchPlan {
+  bool k1_wave_all;        // K1 takes every state a wave each: no lane tier
+  uint32_t k1_wave_grid;
+  // K2's item count when the host has read it back (k_src_items then runs first); kNone: the
+  // kernels read tot[1] on the device, and the scan's fused apply pass has written the items
+  uint32_t n_src;
+  uint64_t src_cover;      // sources the K2 item grid and lane grid cover (0: K2 is not launched)
+  // small runs: the ball tier hands straight to grp and grp to wave (no listed lane tier, reg2 or
+  // wave_s): with the route tables most small batches hand over nothing, and the five-tier chain's
+  // launches were a sixth of their engine time
+  bool short_chain;
+  TierGrids routes, paths;
+};
+
+// the hand-over tiers' grids of a run that does not know the lists' lengths
+static TierGrids tier_grids(uint64_t P) {
+  return {true, (uint32_t)kListedGrid, tier_grid(P, kReg2Grid), tier_grid(P, kGrpGrid), tier_grid(P, kMidGrid),
+          tier_grid(P, 1024)};
+}
+
+bool Matcher::route_balls(const DevGraph& g) const { return (mode_mask_ & g.ball_mask) != 0u; }
+
+struct Matcher::Stages {
+  Matcher& m;
+  const DevGraph& g;
+  LaunchPlan pl;
+  void attach_pools(DevBatch& v) const;
+  void k1(const DevBatch& v) const;
+  void routes(const DevBatch& v) const;
+  void paths(const DevBatch& v) const;
+  void k4(const RunParams& rp, const DevBatch& v, uint32_t total) const;
+};
+
+// the pools a run (re)allocates, attached to its view: the ordinary path calls this again after
+// each of them has grown
+void Matcher::Stages::attach_pools(DevBatch& v) const {
+  const Workspace& w = m.ws_;
+  v.route = w.route;
+  if (m.turn_mask_) { v.route_d = w.route_d; v.walk = w.walk; }   // the distance terms with turn costs (rule 3b), read by K3
+  v.src_item = w.src_item;
+  v.rl_routes_a = w.rl_routes_a; v.rl_routes_b = w.rl_routes_b; v.rl_routes_0 = w.rl_routes_0;
+  v.rl_routes_c = w.rl_routes_c;
+  v.segs = w.segs; v.reps = w.reps; v.seg_cap = w.cap_segs;
+}
+
+void Matcher::Stages::k1(const DevBatch& v) const {
+  hipStream_t st = m.stream_;
+  m.tic(kKCandidates);
+  DevGraph gk = g;   // K1's grid for the batch's radius
+  m.eng_->k1_grid(m.batch_radius_, gk);
+  if (pl.k1_wave_all) {
+    hipLaunchKernelGGL(k_candidates_wave, dim3(pl.k1_wave_grid), dim3(64), 0, st, gk, v, 1);
+  } else {
+    hipLaunchKernelGGL(k_candidates_lane, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, gk, v);
+    hipLaunchKernelGGL(k_candidates_wave, dim3(pl.k1_wave_grid), dim3(64), 0, st, gk, v, 0);
+  }
+  m.toc(kKCandidates);
+}
+
+// the routes stage (K2).  The ball tiers run when some mode of the batch has route balls; items
+// of a mode without them (or bounds above its radius) are handed to the search tiers
+void Matcher::Stages::routes(const DevBatch& v) const {
+  hipStream_t st = m.stream_;
+  const TierGrids& tg = pl.routes;
+  const bool balls = m.route_balls(g);
+  const bool chain = tg.launch && !pl.short_chain;   // every tier
+  const uint32_t item_grid = (uint32_t)((pl.src_cover + kK2Items - 1) / kK2Items);
+  const uint32_t lane_grid = (uint32_t)((pl.src_cover + 255) / 256);
+  m.tic(kKRoutes);
+  if (pl.n_src != kNone) hipLaunchKernelGGL(k_src_items, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, v);
+  if (pl.src_cover && balls) {
+    // the ball tier and the walks are what counts kCtlBallToSearch: they run without the gate bit
+    // that makes every later kernel skip the batch once that word is non-zero
+    DevBatch vk = v;
+    vk.gate &= ~(uint32_t)kGateRoutesTiers;
+    if (v.route_d) {
+      hipLaunchKernelGGL(k_routes_ball2<true>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, pl.n_src);
+      hipLaunchKernelGGL(k_turn_walks, dim3(item_grid), dim3(kWalkThreads), 0, st, g, vk, pl.n_src);
+      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, vk);
+    } else {
+      hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, pl.n_src);
+    }
+    if (chain) {
+      const uint32_t lg = std::min(lane_grid, tg.listed);
+      if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
+      else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
+    }
+  } else if (pl.src_cover) {
+    if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lane_grid), dim3(256), 0, st, g, v, pl.n_src, 0);
+    else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lane_grid), dim3(256), 0, st, g, v, pl.n_src, 0);
+  }
+  const int sc = pl.short_chain ? 1 : 0;
+  if (chain) hipLaunchKernelGGL(k_routes_reg2, dim3(tg.reg2), dim3(256), 0, st, g, v);
+  if (tg.launch) hipLaunchKernelGGL(k_routes_grp, dim3(tg.grp), dim3(64), 0, st, g, v, sc);
+  if (chain) hipLaunchKernelGGL(k_routes_wave_s, dim3(tg.wave_s), dim3(64), 0, st, g, v);
+  if (tg.launch) hipLaunchKernelGGL(k_routes_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
+  // the global tier runs in line once its scratch exists (ensure_global_search)
+  if (m.ws_.gsearch)
+    hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch);
+  m.toc(kKRoutes);
+}
+
+// the path stage, as the routes stage
+void Matcher::Stages::paths(const DevBatch& v) const {
+  hipStream_t st = m.stream_;
+  const TierGrids& tg = pl.paths;
+  const bool chain = tg.launch && !pl.short_chain;
+  const uint32_t count_grid = (uint32_t)((v.P + 255) / 256);
+  m.tic(kKPaths);
+  if (m.route_balls(g)) {
+    hipLaunchKernelGGL(k_paths_ball, dim3(count_grid), dim3(256), 0, st, g, v);
+    if (chain) hipLaunchKernelGGL(k_paths_lane, dim3(std::min(count_grid, tg.listed)), dim3(256), 0, st, g, v, 1);
+  } else {
+    hipLaunchKernelGGL(k_paths_lane, dim3(count_grid), dim3(256), 0, st, g, v, 0);
+  }
+  const int sc = pl.short_chain ? 1 : 0;
+  if (chain) hipLaunchKernelGGL(k_paths_reg2, dim3(tg.reg2), dim3(256), 0, st, g, v);
+  if (tg.launch) hipLaunchKernelGGL(k_paths_grp, dim3(tg.grp), dim3(64), 0, st, g, v, sc);
+  if (chain) hipLaunchKernelGGL(k_paths_wave_s, dim3(tg.wave_s), dim3(64), 0, st, g, v);
+  if (tg.launch) hipLaunchKernelGGL(k_paths_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
+  if (m.ws_.gsearch)
+    hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch);
+  m.toc(kKPaths);
+}
+
+// K4 and the report.  total: the traversal records when the host has read them back (k_rec_slot
+// then runs first); kNone: K4 reads tot[2], and the scan's fused apply pass has filled rec_slot
+void Matcher::Stages::k4(const RunParams& rp, const DevBatch& v, uint32_t total) const {
+  hipStream_t st = m.stream_;
+  if (rp.do_report && rp.zero_hist) m.zero_hist(rp);
+  if (total != kNone)
+    hipLaunchKernelGGL(k_rec_slot, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, v, m.ws_.rec_slot);
+  hipLaunchKernelGGL(k_seg_wave, dim3(v.T), dim3(64), 0, st, g, v, (const uint32_t*)m.ws_.rec_slot, total, report_args(rp));
+}
+
+// The end of every run: the control words come down (with the totals, for a run that has not read
+// them back on the way) ...
+void Matcher::read_back(bool totals) {
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipMemcpyAsync(hctl_, ws_.ctl, kCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, stream_));
+  if (totals) RM_HIP(hipMemcpyAsync(htot(), ws_.tot64, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream_));
+  sync();
+}
+// ... and, unless the run was gated off, its sizes and errors are recorded from them
+void Matcher::finish_run(const RunParams& rp) {
+  n_trans_ = htot()[0];
+  n_path_ = htot()[2];   // one traversal record (and at most one segment) per chosen path edge
+  seg_used_ = htot()[2];
+  has_report_ = rp.do_report != 0;
+  err_bits_ = hctl_[kCtlErr] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
+  if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
+}
+
 bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
   const uint32_t T = n_traces_;
   const uint64_t P = n_points_;
   Workspace& w = ws_;
   hipStream_t st = stream_;
-  unsigned long long* htot = reinterpret_cast<unsigned long long*>(hctl_ + 16);
   // sized for the next power of two of points (>= 4,096): a service's batch sizes wander, and each
   // regrowth frees and reallocates (hipFree synchronises the device: a stall of milliseconds)
   uint64_t Pc = 4096;
@@ -6038,93 +6181,42 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
   ensure_trans(Pc * kMaxCand * kMaxCand, Pc * kMaxCand);
   if (turn_mask_) ensure_turns();
   ensure_segs(Pc * kInlinePath + w.cap_path);
+  Stages s{*this, g, {}};
   DevBatch v = make_view(w, in_, T, P);
-  v.route = w.route;
-  if (turn_mask_) { v.route_d = w.route_d; v.walk = w.walk; }
-  v.src_item = w.src_item;
-  v.rl_routes_a = w.rl_routes_a; v.rl_routes_b = w.rl_routes_b; v.rl_routes_0 = w.rl_routes_0;
-  v.rl_routes_c = w.rl_routes_c;
-  v.segs = w.segs; v.reps = w.reps; v.seg_cap = w.cap_segs;
-  v.gate = w.gsearch ? 1u : 3u;
+  s.attach_pools(v);
+  v.gate = kGateRecords | (w.gsearch ? 0u : kGateGlobal);
   locality_used_ = false;   // a few thousand points: nothing to gain from the region order
   const uint32_t count_grid = (uint32_t)((P + 255) / 256);
   const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);
-  const uint64_t max_src = P * kMaxCand;
-  const uint32_t item_grid = (uint32_t)((max_src + kK2Items - 1) / kK2Items);
-  const uint32_t lane_grid = (uint32_t)((max_src + 255) / 256);
-  const auto tgrid = [P](uint32_t full) { return tier_grid(P, full); };
+  LaunchPlan& pl = s.pl;
+  pl.k1_wave_all = P <= kSmallWaveK1;   // one wave per state
+  pl.k1_wave_grid = pl.k1_wave_all ? (uint32_t)P : tier_grid(P, 2048);
+  pl.n_src = kNone;
+  pl.src_cover = P * kMaxCand;
+  // RM_SMALL_SHORT_CHAIN=0 launches every tier (A/B)
+  const char* sc_env = std::getenv("RM_SMALL_SHORT_CHAIN");   // (read per run: tests switch it)
+  pl.short_chain = route_balls(g) && !(sc_env && *sc_env == '0');
+  pl.routes = pl.paths = tier_grids(P);
 
   tic(kKStates);
   hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
   toc(kKStates);
-  tic(kKCandidates);
-  DevGraph gk = g;   // K1's grid for the batch's radius
-  eng_->k1_grid(batch_radius_, gk);
-  if (P <= kSmallWaveK1) {   // one wave per state
-    hipLaunchKernelGGL(k_candidates_wave, dim3((uint32_t)P), dim3(64), 0, st, gk, v, 1);
-  } else {
-    hipLaunchKernelGGL(k_candidates_lane, dim3(count_grid), dim3(256), 0, st, gk, v);
-    hipLaunchKernelGGL(k_candidates_wave, dim3(tgrid(2048)), dim3(64), 0, st, gk, v, 0);
-  }
-  toc(kKCandidates);
+  s.k1(v);
   tic(kKScan);
   hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
   hipLaunchKernelGGL(k_trans_apply_small, dim3(count_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
                      count_grid, w.tot64);
   toc(kKScan);
-  const bool balls = (mode_mask_ & g.ball_mask) != 0u;
-  // the short hand-over chain (k_routes_grp): with the route tables most small batches hand over
-  // nothing, and the five-tier chain's launches were a sixth of their engine time;
-  // RM_SMALL_SHORT_CHAIN=0 launches every tier (A/B)
-  const char* sc_env = std::getenv("RM_SMALL_SHORT_CHAIN");   // (read per run: tests switch it)
-  const bool short_chain = balls && !(sc_env && *sc_env == '0');
-  tic(kKRoutes);
-  if (balls) {
-    if (v.route_d) {
-      hipLaunchKernelGGL(k_routes_ball2<true>, dim3(item_grid), dim3(kK2Threads), 0, st, g, v, kNone);
-      hipLaunchKernelGGL(k_turn_walks, dim3(item_grid), dim3(kWalkThreads), 0, st, g, v, kNone);
-      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, v);
-    } else {
-      hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, v, kNone);
-    }
-    if (!short_chain) {
-      const uint32_t lg = (uint32_t)std::min<uint64_t>(lane_grid, kListedGrid);
-      if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-      else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-    }
-  } else {
-    if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
-    else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
-  }
-  if (!short_chain) hipLaunchKernelGGL(k_routes_reg2, dim3(tgrid(kReg2Grid)), dim3(256), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_grp, dim3(tgrid(kGrpGrid)), dim3(64), 0, st, g, v, short_chain ? 1 : 0);
-  if (!short_chain) hipLaunchKernelGGL(k_routes_wave_s, dim3(tgrid(kMidGrid)), dim3(64), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_wave, dim3(tgrid(1024)), dim3(64), 0, st, g, v, short_chain ? 1 : 0);
-  if (w.gsearch) hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-  toc(kKRoutes);
+  s.routes(v);
   tic(kKViterbi);
   launch_viterbi(T, st, v);
   toc(kKViterbi);
-  tic(kKPaths);
-  if (balls) {
-    hipLaunchKernelGGL(k_paths_ball, dim3(count_grid), dim3(256), 0, st, g, v);
-    if (!short_chain)
-      hipLaunchKernelGGL(k_paths_lane, dim3((uint32_t)std::min<uint64_t>(count_grid, kListedGrid)), dim3(256), 0, st, g, v, 1);
-  } else {
-    hipLaunchKernelGGL(k_paths_lane, dim3(count_grid), dim3(256), 0, st, g, v, 0);
-  }
-  if (!short_chain) hipLaunchKernelGGL(k_paths_reg2, dim3(tgrid(kReg2Grid)), dim3(256), 0, st, g, v);
-  hipLaunchKernelGGL(k_paths_grp, dim3(tgrid(kGrpGrid)), dim3(64), 0, st, g, v, short_chain ? 1 : 0);
-  if (!short_chain) hipLaunchKernelGGL(k_paths_wave_s, dim3(tgrid(kMidGrid)), dim3(64), 0, st, g, v);
-  hipLaunchKernelGGL(k_paths_wave, dim3(tgrid(1024)), dim3(64), 0, st, g, v, short_chain ? 1 : 0);
-  if (w.gsearch) hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-  toc(kKPaths);
+  s.paths(v);
   tic(kKSegments);
   hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
   hipLaunchKernelGGL(k_path_apply_small, dim3(sum_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
                      sum_grid, w.tot64, w.rec_slot);
-  if (rp.do_report && rp.zero_hist) zero_hist(rp);
-  hipLaunchKernelGGL(k_seg_wave, dim3(T), dim3(64), 0, st, g, v, (const uint32_t*)w.rec_slot, kNone, report_args(rp));
+  s.k4(rp, v, kNone);
   toc(kKSegments);
   // the reply's segments, compacted per trace on the device (get_segments then copies them down)
   constexpr uint32_t kSegWords = sizeof(SegmentRec) / 8;
@@ -6152,18 +6244,12 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
                        (unsigned long long*)((char*)dl_dev_ + offb));
     RM_HIP(hipMemcpyAsync(hoff_, d_off, (T + 1) * 4ull, hipMemcpyDeviceToHost, st));
   }
-  RM_HIP(hipGetLastError());
-  RM_HIP(hipMemcpyAsync(hctl_, w.ctl, kCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  RM_HIP(hipMemcpyAsync(htot, w.tot64, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  sync();
-  if ((hctl_[2] & kErrPathOverflow) || (!w.gsearch && (hctl_[9] | hctl_[10])) || htot[2] > v.seg_cap) return false;
-  n_trans_ = htot[0];
-  n_path_ = htot[2];
-  seg_used_ = htot[2];
-  has_report_ = rp.do_report != 0;
+  read_back(true);
+  if ((hctl_[kCtlErr] & kErrPathOverflow) || (!w.gsearch && (hctl_[kCtlWaveToGlobal] | hctl_[kCtlPathsWaveToGlobal])) ||
+      htot()[2] > v.seg_cap)
+    return false;
   seg_prefetched_ = prefetch;
-  err_bits_ = hctl_[2] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
-  if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
+  finish_run(rp);
   return true;
 }
 
@@ -6181,36 +6267,29 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   const uint64_t P = n_points_;
   Workspace& w = ws_;
   hipStream_t st = stream_;
-  unsigned long long* htot = reinterpret_cast<unsigned long long*>(hctl_ + 16);
   if (turn_mask_) ensure_turns();
+  Stages s{*this, g, {}};
   DevBatch v = make_view(w, in_, T, P);
-  v.route = w.route;
-  if (turn_mask_) { v.route_d = w.route_d; v.walk = w.walk; }
-  v.src_item = w.src_item;
-  v.rl_routes_a = w.rl_routes_a; v.rl_routes_b = w.rl_routes_b; v.rl_routes_0 = w.rl_routes_0;
-  v.rl_routes_c = w.rl_routes_c;
-  v.segs = w.segs; v.reps = w.reps; v.seg_cap = w.cap_segs;
+  s.attach_pools(v);
   const uint64_t src_cover = std::min<uint64_t>(w.cap_src, steady_src_ + steady_src_ / 8 + 4096);
   v.trans_cap = w.cap_trans;
   v.src_cap = src_cover;
-  v.gate = (w.gsearch ? 1u : 3u) | 4u;
+  v.gate = kGateRecords | (w.gsearch ? 0u : kGateGlobal) | kGateSteady;
   locality_used_ = false;
   const uint32_t count_grid = (uint32_t)((P + 255) / 256);
   const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);
-  const bool balls = (mode_mask_ & g.ball_mask) != 0u;
   // A stage's five hand-over tiers are empty launches (~4.7 us each on the in-order stream) when
   // its ball tier hands nothing over, so they are not launched once the matcher's last two runs
   // ended with that stage's lists empty.  The prediction is checked on the device every run: items
-  // handed over after all gate the later stages off (gate bits 8 and 16), and the host runs the
-  // batch again the ordinary way and launches the tiers until two clean runs have passed.
-  // RM_STEADY_TIERS=0 always launches them (A/B; read per run: tests switch it).
+  // handed over after all gate the later stages off (kGateRoutesTiers, kGatePathsTiers), and the
+  // host runs the batch again the ordinary way and launches the tiers until two clean runs have
+  // passed.  RM_STEADY_TIERS=0 always launches them (A/B; read per run: tests switch it).
   const char* tiers_env = std::getenv("RM_STEADY_TIERS");
-  const bool may_skip = balls && !(tiers_env && *tiers_env == '0');
+  const bool may_skip = route_balls(g) && !(tiers_env && *tiers_env == '0');
   const bool skip_routes = may_skip && clean_routes_ >= 2;
   const bool skip_paths = may_skip && clean_paths_ >= 2;
-  if (skip_paths) v.gate |= 16u;
-  DevBatch vk = v;   // the routes stage's own view: its ball tier is what counts ctl[1]
-  if (skip_routes) v.gate |= 8u;
+  if (skip_routes) v.gate |= kGateRoutesTiers;
+  if (skip_paths) v.gate |= kGatePathsTiers;
   ++run_stats_[0];
   if (skip_routes) ++run_stats_[2];
   if (skip_paths) ++run_stats_[3];
@@ -6218,21 +6297,28 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   // any grid is correct, and a list that grew runs on fewer blocks than it could): mostly empty
   // launches of 64 blocks instead of up to 4,096
   static const bool prev_grids = [] { const char* e = std::getenv("RM_STEADY_GRIDS"); return !(e && *e == '0'); }();   // A/B
-  const auto sgrid = [&](uint32_t full, int word, uint32_t per_block) {
+  const auto sgrid = [&](uint32_t full, CtlWord word, uint32_t per_block) {
     if (!prev_grids) return (uint32_t)(full == 2048u ? 2048u : tier_grid(P, full));
     const uint64_t want = 4ull * (((uint64_t)steady_ctl_[word] + per_block - 1) / per_block);
     return (uint32_t)std::min<uint64_t>(tier_grid(P, full), std::max<uint64_t>(64u, want));
   };
+  LaunchPlan& pl = s.pl;
+  pl.k1_wave_all = false;
+  pl.k1_wave_grid = sgrid(2048, kCtlK1LaneToWave, 1);
+  pl.n_src = kNone;
+  pl.src_cover = src_cover;
+  pl.short_chain = false;
+  pl.routes = {!skip_routes, sgrid(kListedGrid, kCtlBallToSearch, 256), sgrid(kReg2Grid, kCtlLaneToReg2, 256),
+               sgrid(kGrpGrid, kCtlReg2ToGroup, kWave / kGrpW), sgrid(kMidGrid, kCtlGroupToWave512, 1),
+               sgrid(1024, kCtlWave512ToWave4096, 1)};
+  pl.paths = {!skip_paths, sgrid(kListedGrid, kCtlPathsBallToSearch, 256), sgrid(kReg2Grid, kCtlPathsLaneToReg2, 256),
+              sgrid(kGrpGrid, kCtlPathsReg2ToGroup, kWave / kGrpW), sgrid(kMidGrid, kCtlPathsGroupToWave512, 1),
+              sgrid(1024, kCtlPathsWave512ToWave4096, 1)};
 
   tic(kKStates);
   hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
   toc(kKStates);
-  tic(kKCandidates);
-  DevGraph gk = g;
-  eng_->k1_grid(batch_radius_, gk);
-  hipLaunchKernelGGL(k_candidates_lane, dim3(count_grid), dim3(256), 0, st, gk, v);
-  hipLaunchKernelGGL(k_candidates_wave, dim3(sgrid(2048, 7, 1)), dim3(64), 0, st, gk, v, 0);
-  toc(kKCandidates);
+  s.k1(v);
   tic(kKScan);
   hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
   hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(count_grid) + 3) / 4), dim3(256), 0, st,
@@ -6240,80 +6326,30 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   hipLaunchKernelGGL(k_trans_apply_steady, dim3(count_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
                      (const unsigned long long*)w.scan_bkt, w.tot64);
   toc(kKScan);
-  const uint32_t item_grid = (uint32_t)((src_cover + kK2Items - 1) / kK2Items);
-  const uint32_t lane_grid = (uint32_t)((src_cover + 255) / 256);
-  tic(kKRoutes);
-  if (balls) {
-    if (v.route_d) {
-      hipLaunchKernelGGL(k_routes_ball2<true>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, kNone);
-      hipLaunchKernelGGL(k_turn_walks, dim3(item_grid), dim3(kWalkThreads), 0, st, g, vk, kNone);
-      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, vk);
-    } else {
-      hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, kNone);
-    }
-    if (!skip_routes) {
-      const uint32_t lg = std::min<uint32_t>(lane_grid, sgrid(kListedGrid, 1, 256));
-      if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-      else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-    }
-  } else {
-    if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
-    else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lane_grid), dim3(256), 0, st, g, v, kNone, 0);
-  }
-  if (!skip_routes) {
-    hipLaunchKernelGGL(k_routes_reg2, dim3(sgrid(kReg2Grid, 3, 256)), dim3(256), 0, st, g, v);
-    hipLaunchKernelGGL(k_routes_grp, dim3(sgrid(kGrpGrid, 5, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
-    hipLaunchKernelGGL(k_routes_wave_s, dim3(sgrid(kMidGrid, 11, 1)), dim3(64), 0, st, g, v);
-    hipLaunchKernelGGL(k_routes_wave, dim3(sgrid(1024, 13, 1)), dim3(64), 0, st, g, v, 0);
-  }
-  if (w.gsearch) hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-  toc(kKRoutes);
+  s.routes(v);
   tic(kKViterbi);
   launch_viterbi(T, st, v);
   toc(kKViterbi);
-  tic(kKPaths);
-  if (balls) {
-    hipLaunchKernelGGL(k_paths_ball, dim3(count_grid), dim3(256), 0, st, g, v);
-    if (!skip_paths)
-      hipLaunchKernelGGL(k_paths_lane, dim3(std::min<uint32_t>(count_grid, sgrid(kListedGrid, 8, 256))), dim3(256), 0, st, g, v, 1);
-  } else {
-    hipLaunchKernelGGL(k_paths_lane, dim3(count_grid), dim3(256), 0, st, g, v, 0);
-  }
-  if (!skip_paths) {
-    hipLaunchKernelGGL(k_paths_reg2, dim3(sgrid(kReg2Grid, 4, 256)), dim3(256), 0, st, g, v);
-    hipLaunchKernelGGL(k_paths_grp, dim3(sgrid(kGrpGrid, 6, kWave / kGrpW)), dim3(64), 0, st, g, v, 0);
-    hipLaunchKernelGGL(k_paths_wave_s, dim3(sgrid(kMidGrid, 12, 1)), dim3(64), 0, st, g, v);
-    hipLaunchKernelGGL(k_paths_wave, dim3(sgrid(1024, 14, 1)), dim3(64), 0, st, g, v, 0);
-  }
-  if (w.gsearch) hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-  toc(kKPaths);
+  s.paths(v);
   tic(kKSegments);
   hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
   hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(sum_grid) + 3) / 4), dim3(256), 0, st,
                      (const unsigned long long*)w.tot_part, sum_grid, w.scan_bkt);
   hipLaunchKernelGGL(k_path_apply_steady, dim3(sum_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
                      (const unsigned long long*)w.scan_bkt, w.tot64, w.rec_slot);
-  if (rp.do_report && rp.zero_hist) zero_hist(rp);
-  hipLaunchKernelGGL(k_seg_wave, dim3(T), dim3(64), 0, st, g, v, (const uint32_t*)w.rec_slot, kNone, report_args(rp));
+  s.k4(rp, v, kNone);
   toc(kKSegments);
-  RM_HIP(hipGetLastError());
-  RM_HIP(hipMemcpyAsync(hctl_, w.ctl, kCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  RM_HIP(hipMemcpyAsync(htot, w.tot64, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-  sync();
-  if (htot[0] > w.cap_trans || htot[1] > src_cover || (hctl_[2] & kErrPathOverflow) ||
-      (!w.gsearch && (hctl_[9] | hctl_[10])) || htot[2] > v.seg_cap || (skip_routes && hctl_[1]) ||
-      (skip_paths && hctl_[8])) {
+  read_back(true);
+  const unsigned long long* tot = htot();
+  if (tot[0] > w.cap_trans || tot[1] > src_cover || (hctl_[kCtlErr] & kErrPathOverflow) ||
+      (!w.gsearch && (hctl_[kCtlWaveToGlobal] | hctl_[kCtlPathsWaveToGlobal])) || tot[2] > v.seg_cap ||
+      (skip_routes && hctl_[kCtlBallToSearch]) || (skip_paths && hctl_[kCtlPathsBallToSearch])) {
     ++run_stats_[1];
     return false;
   }
-  n_trans_ = htot[0];
-  n_path_ = htot[2];
-  seg_used_ = htot[2];
-  steady_src_ = htot[1];
+  steady_src_ = tot[1];
   keep_ctl();
-  has_report_ = rp.do_report != 0;
-  err_bits_ = hctl_[2] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
-  if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
+  finish_run(rp);
   return true;
 }
 
@@ -6330,32 +6366,37 @@ void Matcher::run_device(const RunParams& rp) {
   if (turn_mask_) eng_->ensure_turn_rows(turn_mask_);
   const DevGraph g = eng_->dev_snapshot();
   if (!hctl_) RM_HIP(hipHostMalloc((void**)&hctl_, 32 * sizeof(uint32_t), hipHostMallocDefault));
-  unsigned long long* htot = reinterpret_cast<unsigned long long*>(hctl_ + 16);
   seg_prefetched_ = false;
   // (a forced locality order takes the ordinary path: the small one runs in slot order)
   if (P <= small_batch_points() && locality_ <= 0 && run_small(rp, g)) return;
+  // locality mode: 0 slot order, 1 K1 + K2 in locality order, 2 the path stage too; auto (-1): 2 on
+  // large graphs, 1 for sparsely sampled batches on small ones (measured: DESIGN.md §5 "Locality")
+  int lmode = locality_;
+  if (lmode < 0) lmode = eng_->locality_default() ? 2 : (batch_sparse_ ? 1 : 0);
+  if (eng_->locality_bits() == 0) lmode = 0;   // one region: nothing to order
   const char* steady_env = std::getenv("RM_STEADY");   // (read per run: tests switch it)
   const bool steady_on = !(steady_env && *steady_env == '0');
-  if (steady_on && steady_src_ && w.route && w.src_item && w.path_pool && w.segs && T > 0) {
-    int lm = locality_;
-    if (lm < 0) lm = eng_->locality_default() ? 2 : (batch_sparse_ ? 1 : 0);
-    if (eng_->locality_bits() == 0) lm = 0;
-    if (lm == 0 && run_steady(rp, g)) return;
+  if (steady_on && steady_src_ && w.route && w.src_item && w.path_pool && w.segs) {
+    if (lmode == 0 && run_steady(rp, g)) return;
     steady_src_ = 0;   // (re-armed by the ordinary run below)
   }
   // (k_states zeroes the control words and the per-trace error bits)
   DevBatch v = make_view(w, in_, T, P);
   const uint32_t count_grid = (uint32_t)((P + 255) / 256);
   const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);   // k_sum_u64: four counts per lane
+  static const bool k1_wave_all = [] { const char* e = std::getenv("RM_K1_WAVE_ALL"); return e && *e == '1'; }();
+  Stages s{*this, g, {}};
+  LaunchPlan& pl = s.pl;
+  pl.k1_wave_all = k1_wave_all;   // A/B: every state in the wave tier
+  pl.k1_wave_grid = k1_wave_all ? (uint32_t)std::min<uint64_t>(P, 1u << 20) : 2048u;
+  pl.short_chain = false;
+  // the search tiers' grids (grid-stride over lists the host does not read) shrink with the batch:
+  // a coalesced service batch of ~15 k points launches them mostly empty
+  pl.routes = pl.paths = tier_grids(P);
 
   tic(kKStates);
   hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
   toc(kKStates);
-  // mode: 0 slot order, 1 K1 + K2 in locality order, 2 the path stage too; auto (-1): 2 on large
-  // graphs, 1 for sparsely sampled batches on small ones (measured: DESIGN.md §5 "Locality")
-  int lmode = locality_;
-  if (lmode < 0) lmode = eng_->locality_default() ? 2 : (batch_sparse_ ? 1 : 0);
-  if (eng_->locality_bits() == 0) lmode = 0;   // one region: nothing to order
   locality_used_ = lmode > 0;
   if (locality_used_) {
     tic(kKLocality);
@@ -6370,17 +6411,7 @@ void Matcher::run_device(const RunParams& rp) {
     if (lmode >= 2) v.perm_paths = w.perm;
     toc(kKLocality);
   }
-  tic(kKCandidates);
-  DevGraph gk = g;   // K1's grid for the batch's radius
-  eng_->k1_grid(batch_radius_, gk);
-  static const bool k1_wave_all = [] { const char* e = std::getenv("RM_K1_WAVE_ALL"); return e && *e == '1'; }();
-  if (k1_wave_all) {   // A/B: every state in the wave tier
-    hipLaunchKernelGGL(k_candidates_wave, dim3((uint32_t)std::min<uint64_t>(P, 1u << 20)), dim3(64), 0, st, gk, v, 1);
-  } else {
-    hipLaunchKernelGGL(k_candidates_lane, dim3((uint32_t)((P + 255) / 256)), dim3(256), 0, st, gk, v);
-    hipLaunchKernelGGL(k_candidates_wave, dim3(2048), dim3(64), 0, st, gk, v, 0);
-  }
-  toc(kKCandidates);
+  s.k1(v);
   tic(kKScan);
   hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
   hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, count_grid, w.tot64);
@@ -6393,161 +6424,93 @@ void Matcher::run_device(const RunParams& rp) {
                        (const unsigned long long*)w.tot_part, (const uint32_t*)w.perm, w.src_off);
   }
   toc(kKScan);
-  RM_HIP(hipMemcpyAsync(htot, w.tot64, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  unsigned long long* tot = htot();
+  RM_HIP(hipMemcpyAsync(tot, w.tot64, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
-  const uint64_t total = htot[0];
-  const uint64_t n_src = htot[1];
+  const uint64_t total = tot[0];
+  const uint64_t n_src = tot[1];
   if (total >= kMaxTransitions) throw BatchTooLarge("batch too large (transitions >= 0xF0000000); split it");
-  uint64_t steady_next = n_src ? n_src : 1;   // a later batch may run steady (run_steady) from these pools
-  n_trans_ = total;
   ensure_trans(total, n_src);
-  v.route = w.route;
-  if (turn_mask_) {   // the transitions' distance terms with turn costs (rule 3b), read by K3
-    ensure_turns();
-    v.route_d = w.route_d;
-    v.walk = w.walk;
-  }
-  v.src_item = w.src_item;
-  v.rl_routes_a = w.rl_routes_a;
-  v.rl_routes_b = w.rl_routes_b;
-  v.rl_routes_0 = w.rl_routes_0;
-  v.rl_routes_c = w.rl_routes_c;
-
-  // the ball tiers run when some mode of the batch has route balls; items of a mode without
-  // them (or bounds above its radius) are handed to the search tiers
-  const bool balls = (mode_mask_ & g.ball_mask) != 0u;
-  tic(kKRoutes);
-  hipLaunchKernelGGL(k_src_items, dim3((uint32_t)((P + 255) / 256)), dim3(256), 0, st, v);
-  if (n_src && balls) {
-    if (v.route_d) {
-      hipLaunchKernelGGL(k_routes_ball2<true>, dim3((uint32_t)((n_src + kK2Items - 1) / kK2Items)), dim3(kK2Threads), 0, st,
-                         g, v, (uint32_t)n_src);
-      hipLaunchKernelGGL(k_turn_walks, dim3((uint32_t)((n_src + kK2Items - 1) / kK2Items)), dim3(kWalkThreads), 0, st, g, v,
-                         (uint32_t)n_src);
-      hipLaunchKernelGGL(k_turn_walks_marked, dim3(kWalkScanGrid), dim3(256), 0, st, g, v);
-    } else
-      hipLaunchKernelGGL(k_routes_ball2<false>, dim3((uint32_t)((n_src + kK2Items - 1) / kK2Items)), dim3(kK2Threads), 0, st,
-                         g, v, (uint32_t)n_src);
-    if (v.route_d)
-      hipLaunchKernelGGL(k_routes_lane<true>, dim3((uint32_t)std::min<uint64_t>((n_src + 255) / 256, kListedGrid)), dim3(256),
-                         0, st, g, v, 0u, 1);
-    else
-      hipLaunchKernelGGL(k_routes_lane<false>, dim3((uint32_t)std::min<uint64_t>((n_src + 255) / 256, kListedGrid)),
-                         dim3(256), 0, st, g, v, 0u, 1);
-  } else if (n_src) {
-    if (v.route_d)
-      hipLaunchKernelGGL(k_routes_lane<true>, dim3((uint32_t)((n_src + 255) / 256)), dim3(256), 0, st, g, v, (uint32_t)n_src, 0);
-    else
-      hipLaunchKernelGGL(k_routes_lane<false>, dim3((uint32_t)((n_src + 255) / 256)), dim3(256), 0, st, g, v, (uint32_t)n_src, 0);
-  }
-  // the search tiers' grids (grid-stride over lists the host does not read) shrink with the batch:
-  // a coalesced service batch of ~15 k points launches them mostly empty
-  const auto tgrid = [P](uint32_t full) { return tier_grid(P, full); };
-  hipLaunchKernelGGL(k_routes_reg2, dim3(tgrid(kReg2Grid)), dim3(256), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_grp, dim3(tgrid(kGrpGrid)), dim3(64), 0, st, g, v, 0);
-  hipLaunchKernelGGL(k_routes_wave_s, dim3(tgrid(kMidGrid)), dim3(64), 0, st, g, v);
-  hipLaunchKernelGGL(k_routes_wave, dim3(tgrid(1024)), dim3(64), 0, st, g, v, 0);
-  // the global tier runs in line once its scratch exists; before that, a hand-over seen at the
-  // path-stage read-back allocates it and re-runs K3 (rare: bounds of many kilometres)
+  if (turn_mask_) ensure_turns();
+  s.attach_pools(v);
+  pl.n_src = (uint32_t)n_src;
+  pl.src_cover = n_src;
+  s.routes(v);
+  // before the global tier's scratch exists, a hand-over seen at the path-stage read-back
+  // allocates it and re-runs K3 (rare: bounds of many kilometres)
   bool routes_global_done = w.gsearch != nullptr;
-  if (routes_global_done)
-    hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-  toc(kKRoutes);
   tic(kKViterbi);
   launch_viterbi(T, st, v);
   toc(kKViterbi);
-  for (int attempt = 0;; ++attempt) {
-    tic(kKPaths);
-    if (attempt) {   // the first attempt starts from the zeroed control words
-      RM_HIP(hipMemsetAsync(w.ctl + 8, 0, sizeof(uint32_t), st));    // path ball hand-overs
-      RM_HIP(hipMemsetAsync(w.ctl + 10, 0, sizeof(uint32_t), st));   // paths list C
-      RM_HIP(hipMemsetAsync(w.ctl + 12, 0, sizeof(uint32_t), st));   // paths list B2
-      RM_HIP(hipMemsetAsync(w.ctl + 14, 0, sizeof(uint32_t), st));   // paths list B3
-    }
-    if (balls) {
-      hipLaunchKernelGGL(k_paths_ball, dim3((uint32_t)((P + 255) / 256)), dim3(256), 0, st, g, v);
-      hipLaunchKernelGGL(k_paths_lane, dim3((uint32_t)std::min<uint64_t>((P + 255) / 256, kListedGrid)), dim3(256), 0,
-                         st, g, v, 1);
-    } else {
-      hipLaunchKernelGGL(k_paths_lane, dim3((uint32_t)((P + 255) / 256)), dim3(256), 0, st, g, v, 0);
-    }
-    hipLaunchKernelGGL(k_paths_reg2, dim3(tgrid(kReg2Grid)), dim3(256), 0, st, g, v);
-    hipLaunchKernelGGL(k_paths_grp, dim3(tgrid(kGrpGrid)), dim3(64), 0, st, g, v, 0);
-    hipLaunchKernelGGL(k_paths_wave_s, dim3(tgrid(kMidGrid)), dim3(64), 0, st, g, v);
-    hipLaunchKernelGGL(k_paths_wave, dim3(tgrid(1024)), dim3(64), 0, st, g, v, 0);
-    if (w.gsearch) hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-    toc(kKPaths);
-    // traversal records are laid out by a scan of path_cnt (0 for slots without a chosen transition)
-    tic(kKSegments);
+  const auto zero_ctl = [&](std::initializer_list<CtlWord> words) {
+    for (CtlWord c : words) RM_HIP(hipMemsetAsync(w.ctl + c, 0, sizeof(uint32_t), st));
+  };
+  const auto clear_path_overflow = [&] {
+    uint32_t flags = hctl_[kCtlErr] & ~kErrPathOverflow;
+    RM_HIP(hipMemcpyAsync(w.ctl + kCtlErr, &flags, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    RM_HIP(hipStreamSynchronize(st));
+  };
+  // traversal records are laid out by a scan of path_cnt (0 for slots without a chosen transition)
+  const auto scan_records = [&] {
     hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
     hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, sum_grid, w.tot64 + 2);
     hipLaunchKernelGGL(k_scan_apply4, dim3(sum_grid), dim3(256), 0, st, (const uint32_t*)w.path_cnt, P,
                        (const unsigned long long*)w.tot_part, w.trav_off);
-    toc(kKSegments);
-    RM_HIP(hipMemcpyAsync(htot + 2, w.tot64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  };
+  const auto read_records = [&] {
+    RM_HIP(hipMemcpyAsync(tot + 2, w.tot64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     read_ctl();
-    if (!routes_global_done && hctl_[9]) {
+  };
+  for (int attempt = 0;; ++attempt) {
+    if (attempt)   // the first attempt starts from the zeroed control words
+      zero_ctl({kCtlPathsBallToSearch, kCtlPathsWaveToGlobal, kCtlPathsGroupToWave512, kCtlPathsWave512ToWave4096});
+    s.paths(v);
+    tic(kKSegments);
+    scan_records();
+    toc(kKSegments);
+    read_records();
+    if (!routes_global_done && hctl_[kCtlWaveToGlobal]) {
       // routes outgrew the LDS wave tier: run them in the global tier, then K3 and paths again
       ensure_global_search();
       routes_global_done = true;
       hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
       launch_viterbi(T, st, v);
       RM_HIP(hipMemsetAsync(w.path_cnt, 0, P * sizeof(uint32_t), st));
-      for (int c : {0, 4, 6}) RM_HIP(hipMemsetAsync(w.ctl + c, 0, sizeof(uint32_t), st));
-      uint32_t flags = hctl_[2] & ~kErrPathOverflow;
-      RM_HIP(hipMemcpyAsync(w.ctl + 2, &flags, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-      RM_HIP(hipStreamSynchronize(st));
+      zero_ctl({kCtlPathUsed, kCtlPathsLaneToReg2, kCtlPathsReg2ToGroup});
+      clear_path_overflow();
       continue;
     }
-    if (!w.gsearch && hctl_[10]) {
+    if (!w.gsearch && hctl_[kCtlPathsWaveToGlobal]) {
       // chosen transitions whose path search outgrew the LDS wave tier
       ensure_global_search();
       hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
-      hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
-      hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, sum_grid, w.tot64 + 2);
-      hipLaunchKernelGGL(k_scan_apply4, dim3(sum_grid), dim3(256), 0, st, (const uint32_t*)w.path_cnt, P,
-                         (const unsigned long long*)w.tot_part, w.trav_off);
-      RM_HIP(hipMemcpyAsync(htot + 2, w.tot64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-      read_ctl();
+      scan_records();
+      read_records();
     }
-    if (!(hctl_[2] & kErrPathOverflow)) break;
+    if (!(hctl_[kCtlErr] & kErrPathOverflow)) break;
     if (attempt > 3) throw BatchTooLarge("path pool overflow persists");
-    ensure_path((uint64_t)hctl_[0]);
+    ensure_path((uint64_t)hctl_[kCtlPathUsed]);
     v.path_pool = w.path_pool; v.path_cap = w.cap_path;
-    RM_HIP(hipMemsetAsync(w.ctl, 0, sizeof(uint32_t), st));          // path_used
-    RM_HIP(hipMemsetAsync(w.ctl + 4, 0, sizeof(uint32_t), st));      // paths list A
-    RM_HIP(hipMemsetAsync(w.ctl + 6, 0, sizeof(uint32_t), st));      // paths list B
-    uint32_t flags = hctl_[2] & ~kErrPathOverflow;
-    RM_HIP(hipMemcpyAsync(w.ctl + 2, &flags, sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    RM_HIP(hipStreamSynchronize(st));
+    zero_ctl({kCtlPathUsed, kCtlPathsLaneToReg2, kCtlPathsReg2ToGroup});
+    clear_path_overflow();
   }
-  const uint64_t seg_total = htot[2];
+  const uint64_t seg_total = tot[2];
   if (seg_total >= kMaxRecords) throw BatchTooLarge("batch too large (path edges >= 1.7e9); split it");
-  n_path_ = seg_total;  // one traversal record (and at most one segment) per chosen path edge
   ensure_segs(seg_total);
-  v.segs = w.segs; v.reps = w.reps; v.seg_cap = w.cap_segs;
+  s.attach_pools(v);
   tic(kKSegments);
-  if (rp.do_report && rp.zero_hist) zero_hist(rp);
-  if (T) {
-    hipLaunchKernelGGL(k_rec_slot, dim3((uint32_t)((P + 255) / 256)), dim3(256), 0, st, v, w.rec_slot);
-    hipLaunchKernelGGL(k_seg_wave, dim3(T), dim3(64), 0, st, g, v, (const uint32_t*)w.rec_slot, (uint32_t)seg_total,
-                       report_args(rp));
-  }
+  s.k4(rp, v, (uint32_t)seg_total);
   toc(kKSegments);
-  RM_HIP(hipGetLastError());
-  RM_HIP(hipMemcpyAsync(hctl_, w.ctl, kCtlWords * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-  sync();
-  seg_used_ = seg_total;
-  has_report_ = rp.do_report != 0;
+  read_back(false);
   if (!locality_used_) {
-    steady_src_ = steady_next;
+    steady_src_ = n_src ? n_src : 1;   // a later batch may run steady (run_steady) from these pools
     keep_ctl();
   } else {
     count_clean(hctl_);   // (a run in locality order hands over what a steady run of the batch would)
   }
-  err_bits_ = hctl_[2] & (kErrCandOverflow | kErrSearchOverflow | kErrRounds);
-  if (err_bits_ && !isolate_) throw std::runtime_error(error_text(err_bits_));
+  finish_run(rp);
 }
+
 
 void Matcher::get_trace_errors(uint32_t* out) {
   sync();
@@ -6673,8 +6636,12 @@ void Matcher::keep_ctl() {
   count_clean(steady_ctl_);
 }
 void Matcher::count_clean(const uint32_t* c) {
-  clean_routes_ = (c[1] | c[3] | c[5] | c[11] | c[13]) ? 0u : std::min(clean_routes_ + 1u, 2u);
-  clean_paths_ = (c[8] | c[4] | c[6] | c[12] | c[14]) ? 0u : std::min(clean_paths_ + 1u, 2u);
+  const uint32_t routes = c[kCtlBallToSearch] | c[kCtlLaneToReg2] | c[kCtlReg2ToGroup] | c[kCtlGroupToWave512] |
+                          c[kCtlWave512ToWave4096];
+  const uint32_t paths = c[kCtlPathsBallToSearch] | c[kCtlPathsLaneToReg2] | c[kCtlPathsReg2ToGroup] |
+                         c[kCtlPathsGroupToWave512] | c[kCtlPathsWave512ToWave4096];
+  clean_routes_ = routes ? 0u : std::min(clean_routes_ + 1u, 2u);
+  clean_paths_ = paths ? 0u : std::min(clean_paths_ + 1u, 2u);
 }
 
 void Matcher::run_stats(uint64_t* out4) const {
@@ -6690,7 +6657,8 @@ void Matcher::ctl_words(uint32_t* out) {
 void Matcher::tier_counts(uint32_t* out4) {
   uint32_t c[kCtlWords];
   ctl_words(c);
-  out4[0] = c[3]; out4[1] = c[5]; out4[2] = c[4]; out4[3] = c[7];
+  out4[0] = c[kCtlLaneToReg2]; out4[1] = c[kCtlReg2ToGroup]; out4[2] = c[kCtlPathsLaneToReg2];
+  out4[3] = c[kCtlK1LaneToWave];
 }
 
 uint64_t Matcher::count_segments() {

@@ -128,6 +128,46 @@ extern const char* const kKernelNames[kNumKernels];
 // Device workspace of one batch.  All arrays are indexed by point slot p
 // (state s of trace k lives at slot trace_off[k] + s).
 constexpr int kCtlWords = 16;
+// The control words (Workspace::ctl, zeroed by k_states; Matcher::ctl_words returns them in this
+// order).  A hand-over count is named after the tier that writes it, as BatchMatcher.route_tiers():
+// it is the length of the list the next tier reads.
+enum CtlWord : int {
+  kCtlPathUsed = 0,             // path pool used
+  kCtlBallToSearch = 1,         // K2 ball tier -> search tiers (rl_routes_0)
+  kCtlErr = 2,                  // error flags (kErr*)
+  kCtlLaneToReg2 = 3,           // routes: lane tier -> reg2 (list A)
+  kCtlPathsLaneToReg2 = 4,      // paths: the same
+  kCtlReg2ToGroup = 5,          // routes: reg2 -> group tier (list B)
+  kCtlPathsReg2ToGroup = 6,     // paths: the same
+  kCtlK1LaneToWave = 7,         // K1 lane tier -> wave tier
+  kCtlPathsBallToSearch = 8,    // path ball tier -> search tiers (rl_routes_0 again)
+  kCtlWaveToGlobal = 9,         // routes: 4096-slot wave tier -> global-memory tier (list C)
+  kCtlPathsWaveToGlobal = 10,   // paths: the same
+  kCtlGroupToWave512 = 11,      // routes: group tier -> 512-slot wave tier
+  kCtlPathsGroupToWave512 = 12, // paths: the same
+  kCtlWave512ToWave4096 = 13,   // routes: 512-slot tier -> 4096-slot tier
+  kCtlPathsWave512ToWave4096 = 14,   // paths: the same
+  kCtlWalkOverflow = 15,        // a K2 block's walk list overflowed (k_turn_walks_marked reads them
+                                // all); K2's walked turn weights under RM_K2_STATS
+};
+static_assert(kCtlWalkOverflow + 1 == kCtlWords, "one name per control word");
+// Gate bits of DevBatch::gate: what a run without read-backs checks on the device instead (the host
+// checks the same after the run and runs a gated-off batch again the ordinary way).
+enum GateBit : uint32_t {
+  // K4, the report and the segment gather skip a run whose path pool overflowed or whose records
+  // exceed seg_cap (small_abort); set by every small and steady run
+  kGateRecords = 1u,
+  // ... and one that handed searches to the global-memory tier before its scratch exists
+  kGateGlobal = 2u,
+  // a steady run: every stage after the transition scan skips a batch with more transitions or K2
+  // sources than trans_cap / src_cap, the pools an earlier run left (steady_abort)
+  kGateSteady = 4u,
+  // a steady run that did not launch the routes stage's hand-over tiers: items handed over after
+  // all (kCtlBallToSearch) make K3 and everything after it skip
+  kGateRoutesTiers = 8u,
+  // likewise the path stage's tiers (kCtlPathsBallToSearch): K4 and the report skip
+  kGatePathsTiers = 16u,
+};
 constexpr int kInlinePath = 8;  // path edges stored inline per slot (no allocation)
 
 struct Workspace {
@@ -158,18 +198,15 @@ struct Workspace {
   uint32_t* trav_off = nullptr;     // first traversal record of each slot (scan of path_cnt)
   uint32_t* rec_slot = nullptr;     // K4: transition slot of each traversal record (k_rec_slot)
   ReportRec* reps = nullptr; uint32_t* rep_cnt = nullptr; ReportStats* stats = nullptr;
-  // control words (kCtlWords): [0] path pool used [1] K2 ball-tier hand-over list [2] error flags [3] routes list A [4] paths list A
-  // [5] routes list B [6] paths list B [7] candidates list (overflow lists of the lane tiers)
-  // [8] path ball-tier hand-overs [9] routes list C [10] paths list C (global-memory tier)
-  uint32_t* ctl = nullptr;
+  uint32_t* ctl = nullptr;   // the control words (CtlWord) and the hand-over lists they count
   uint32_t* rl_routes_a = nullptr; uint32_t* rl_routes_b = nullptr; uint32_t* rl_routes_0 = nullptr;
   uint32_t* rl_paths_a = nullptr; uint32_t* rl_paths_b = nullptr; uint32_t* rl_cand = nullptr;
-  // global-memory search tier: its hand-over lists (ctl[9] routes, ctl[10] paths) and scratch
+  // global-memory search tier: its hand-over lists (kCtlWaveToGlobal, kCtlPathsWaveToGlobal) and scratch
   uint32_t* rl_routes_c = nullptr; uint32_t* rl_paths_c = nullptr; void* gsearch = nullptr;
   uint32_t* trace_err = nullptr;            // per trace: error bits (kErr*) of that trace alone
   unsigned long long* tot64 = nullptr;      // u64 totals: [0] transitions [1] sources [2] path edges
   unsigned long long* scan_bkt = nullptr;   // a steady run's coarse scan buckets (rm_common.hpp scan_base_lane)
-  unsigned long long* tot_part = nullptr;   // per-block partial pairs of those totals (k_sum_parts folds them)
+  unsigned long long* tot_part = nullptr;   // per-block partial pairs of those totals (the scans fold them)
   // locality order (engine.hip k_loc_count / k_loc_scatter): the sorted state slots, each slot's
   // region bucket, the bucket cursors and the item counts in sorted order; allocated on the first
   // run that uses it (cap_sort slots)
@@ -236,7 +273,7 @@ struct StageBufs {  // grow-only device buffers of the windowing and tile stages
   ~StageBufs();
 };
 
-// error bits in ctl[2] (and, except the path pool, per trace in Workspace::trace_err)
+// error bits in ctl[kCtlErr] (and, except the path pool, per trace in Workspace::trace_err)
 constexpr uint32_t kErrCandOverflow = 1u, kErrSearchOverflow = 2u, kErrPathOverflow = 4u, kErrRounds = 8u;
 // message of the first error bit set in `bits` ("" for none)
 const char* error_text(uint32_t bits);
@@ -388,8 +425,16 @@ class Matcher {
   bool run_small(const RunParams& rp, const DevGraph& g);
   // large batches once a run has sized the pools: no read-back between the stages (run_steady)
   bool run_steady(const RunParams& rp, const DevGraph& g);
+  // the stage launches the three run paths share, written once (engine.hip: they take the kernels'
+  // view of the batch, a type of that file); what differs between the paths is a LaunchPlan
+  struct Stages;
+  void read_back(bool totals);
+  void finish_run(const RunParams& rp);
+  bool route_balls(const DevGraph& g) const;   // some mode of the batch has route balls
+  // the pinned mirror of Workspace::tot64, behind the control words
+  unsigned long long* htot() const { return reinterpret_cast<unsigned long long*>(hctl_ + kCtlWords); }
   uint64_t steady_src_ = 0;    // the last ordinary / steady run's K2 sources (0: no steady run yet)
-  uint32_t steady_ctl_[16] = {0};   // ... and its control words (the hand-over lists' lengths)
+  uint32_t steady_ctl_[kCtlWords] = {0};   // ... and its control words (the hand-over lists' lengths)
   uint32_t clean_routes_ = 0, clean_paths_ = 0;   // completed runs in a row (at most 2) with a stage's lists empty
   uint64_t run_stats_[4] = {0, 0, 0, 0};          // run_stats()
   void keep_ctl();

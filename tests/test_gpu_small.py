@@ -25,15 +25,18 @@ def _ref(g, tr, opts):
                                 np.zeros(T, np.uint32)))
 
 
-@pytest.mark.parametrize("turn", [0.0, 200.0])
-def test_small_and_ordinary_runs_agree(built_lib, small_world, monkeypatch, turn):
+@pytest.mark.parametrize("turn,radius", [(0.0, None), (200.0, None), (200.0, 0.0)], ids=["0.0", "200.0", "200.0-radius0"])
+def test_small_and_ordinary_runs_agree(built_lib, small_world, monkeypatch, turn, radius):
     """40 requests of 60 points (the Java batcher's size): every stage equals the oracle on the
-    small path and on the ordinary one (RM_SMALL_BATCH_POINTS=0), with and without turn costs."""
+    small path and on the ordinary one (RM_SMALL_BATCH_POINTS=0), with and without turn costs, and
+    with turn costs and ball radius 0 (no route balls: K2 runs entirely in the search tiers)."""
     g = graphfile.load(small_world)
     tr = world.generate_traces(small_world, n_traces=40, n_points=60, rate_s=1.0, noise_m=5.0, seed=301)
     opts = engine.default_options(1, turn_penalty_factor=turn)
     ref = _ref(g, tr, opts)
     eng = engine.Engine(small_world, 0)
+    if radius is not None:
+        eng.set_ball_radius(radius)
     bm = engine.BatchMatcher(eng)
     got = {}
     for limit in (None, "0", None):

@@ -48,17 +48,21 @@ def _run(bm, tr, opts, **rp):
 
 # 600 traces x 60 points = 36,000 slots = 141 blocks of 256: two full groups of 64 blocks, a
 # partial third group and a partial last block (the record scan: 36 blocks of 1,024, one group)
-@pytest.mark.parametrize("turn,locality", [(0.0, 0), (200.0, 0), (0.0, 2)])
-def test_scan_across_groups(built_lib, small_world, monkeypatch, turn, locality):
+@pytest.mark.parametrize("turn,locality,radius", [(0.0, 0, None), (200.0, 0, None), (0.0, 2, None), (200.0, 0, 0.0)],
+                         ids=["0.0-0", "200.0-0", "0.0-2", "200.0-0-radius0"])
+def test_scan_across_groups(built_lib, small_world, monkeypatch, turn, locality, radius):
     """One ordinary run and two steady runs on one matcher: every stage equals the oracle and the
     three runs' segments are the same bytes.  (With the locality order forced the runs stay on the
-    ordinary path, whose scans must agree as well.)"""
+    ordinary path, whose scans must agree as well.  With ball radius 0 K2 runs entirely in the search
+    tiers, with turn costs; the oracle does not depend on the radius.)"""
     monkeypatch.setenv("RM_SMALL_BATCH_POINTS", "0")
     tr = _batch(small_world, 600, 411)
     assert int(tr["trace_off"][-1]) == 36_000
     opts = engine.default_options(1, turn_penalty_factor=turn)
     ref = _ref(small_world, 411, tr, opts, turn)
     eng = engine.Engine(small_world, 0)
+    if radius is not None:
+        eng.set_ball_radius(radius)
     bm = engine.BatchMatcher(eng)
     if locality:
         bm.set_locality(locality)

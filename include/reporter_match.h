@@ -64,6 +64,24 @@ int rm_match_batch_packed(rm_matcher* m, const char* const* traces, size_t n, ch
  * fails the call, naming the trace.  Replies are released with rm_free. */
 int rm_match_points(rm_matcher* m, const char* trace_json, char** out_json);
 int rm_match_points_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs);
+/* Matched edges (DESIGN.md §3 rule 10): the directed edges the match drove, in order, with their
+ * times, and the matched polyline -- the "edges" and "shape" of Valhalla's trace_attributes.  Same
+ * request JSON as rm_match; the reply is {"segments":[...],"edges":[...],"shape":"..."} with the
+ * segments of rm_match for that request, byte for byte.  One entry per edge visit:
+ *   {"edge_id","way_id"[,"segment_id"],"begin_shape_index","end_shape_index","begin_trace_index",
+ *    "end_trace_index","length"[,"speed"],"start_time","end_time","source_percent_along",
+ *    "target_percent_along"[,"internal":true][,"discontinuity":true]}
+ * length: kilometres driven on the edge; speed: km/h, present when end_time > start_time;
+ * start_time / end_time: distance-interpolated epoch seconds; the two percent_along: the fractions
+ * of the edge at which the visit begins and ends; begin / end_shape_index: the visit's first and
+ * last vertex in "shape"; begin / end_trace_index: the input point of the matcher state at or
+ * before either end; segment_id: the edge's OSMLR segment, when it has one; discontinuity: the
+ * visit opens a new chain (the match broke before it).  shape: the encoded polyline of the matched
+ * geometry at precision 6 (lat then lon, each llround(v * 1e6)).  Both calls run their requests
+ * as one uncoalesced batch; any failing trace fails the call, naming the trace.  Replies are
+ * released with rm_free. */
+int rm_match_edges(rm_matcher* m, const char* trace_json, char** out_json);
+int rm_match_edges_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs);
 void rm_free(char* p);
 /* Host wall times (ms) of the matcher's last uncoalesced rm_match_batch: out[0] JSON parse
  * (single pass, up to 16 host threads), [1] staging into pinned host arrays, [2] engine run
@@ -298,6 +316,31 @@ typedef struct {
   uint32_t route_cm;   /* distance along the transition's route from the previous state; 0 for type 1 */
 } rm_matched_point;
 int rm_runner_get_matched_points(rm_runner* r, rm_matched_point* out);
+/* Matched edges of the last run / rerun (DESIGN.md §3 rule 10): one 64-byte record per edge visit
+ * -- a maximal run of a chain's traversal records on one directed edge that join end to begin, as
+ * the oracle's add_trav leaves them -- and one shape (f32 lon, lat pairs) per trace: per visit the
+ * road position of its begin (a chain's first visit only), the road's stored vertices strictly
+ * inside the part driven, in travel order, and the road position of its end.  A trace that failed
+ * under isolation has no visits and an empty shape.
+ * rm_runner_matched_edges runs the stage, over what the run left in HBM (a run launches nothing
+ * for it; no kernel id: rm_runner_matched_edges_time gives the device time of the last call in
+ * ms), and keeps the result on the device; out receives the visit count and the shape vertex
+ * count of the batch.  rm_runner_get_matched_edges downloads that result: edge_off and shape_off
+ * (n_traces + 1 each; trace k's visits are edges[edge_off[k] .. edge_off[k+1]), its vertices
+ * shape[2 * shape_off[k] .. 2 * shape_off[k+1])), edges (out[0] records), shape (2 * out[1] floats). */
+typedef struct {
+  uint32_t edge, way;               /* directed edge id, its way id */
+  uint32_t b_cm, e_cm;              /* the part driven, from the start of the directed edge */
+  double t_enter, t_exit;           /* distance-interpolated epoch times at b_cm and e_cm */
+  uint32_t begin_point, end_point;  /* point index within the trace of the state at / before either end */
+  uint32_t shape_begin, shape_end;  /* first and last vertex of the visit in the trace's shape */
+  uint32_t seg_dense, seg_off_cm;   /* dense OSMLR segment (0xFFFFFFFF: none), the edge's offset in it */
+  uint32_t flags;                   /* bit 0 internal, bit 1 has an OSMLR segment, bit 2 first visit of its chain */
+  uint32_t len_cm;                  /* length of the edge */
+} rm_matched_edge;
+int rm_runner_matched_edges(rm_runner* r, uint64_t out[2]);
+int rm_runner_get_matched_edges(rm_runner* r, uint32_t* edge_off, rm_matched_edge* edges, uint32_t* shape_off, float* shape);
+int rm_runner_matched_edges_time(rm_runner* r, double* ms);
 /* segments: 56-byte records (rm::SegmentRec); seg_off has n_traces+1 entries */
 int rm_runner_get_segments(rm_runner* r, uint32_t* seg_off, void* segs);
 /* reports: 48-byte records (rm::ReportRec); stats: 40-byte rm::ReportStats per trace */

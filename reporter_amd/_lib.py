@@ -75,6 +75,13 @@ class RmMatchedPoint(C.Structure):
                 ("off_cm", C.c_uint32), ("way", C.c_uint32), ("type", C.c_uint32), ("route_cm", C.c_uint32)]
 
 
+class RmMatchedEdge(C.Structure):
+    _fields_ = [("edge", C.c_uint32), ("way", C.c_uint32), ("b_cm", C.c_uint32), ("e_cm", C.c_uint32),
+                ("t_enter", C.c_double), ("t_exit", C.c_double), ("begin_point", C.c_uint32),
+                ("end_point", C.c_uint32), ("shape_begin", C.c_uint32), ("shape_end", C.c_uint32),
+                ("seg_dense", C.c_uint32), ("seg_off_cm", C.c_uint32), ("flags", C.c_uint32), ("len_cm", C.c_uint32)]
+
+
 class RmTileParams(C.Structure):
     _fields_ = [("quantisation", C.c_uint32), ("privacy", C.c_uint32), ("source", C.c_char_p), ("mode", C.c_char_p)]
 
@@ -96,6 +103,8 @@ PROTOTYPES = [
     ("rm_match_batch_packed", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P), C.POINTER(C.c_uint64)]),
     ("rm_match_points", C.c_int, [P, C.c_char_p, C.POINTER(P)]),
     ("rm_match_points_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P)]),
+    ("rm_match_edges", C.c_int, [P, C.c_char_p, C.POINTER(P)]),
+    ("rm_match_edges_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P)]),
     ("rm_free", None, [P]),
     ("rm_matcher_timing", C.c_int, [P, P]),
     ("rm_coalesce_stats", C.c_int, [C.POINTER(C.c_uint64)]),
@@ -144,6 +153,9 @@ PROTOTYPES = [
     ("rm_runner_get_viterbi", C.c_int, [P, P, P]),
     ("rm_runner_get_paths", C.c_int, [P, P, P, P, P]),
     ("rm_runner_get_matched_points", C.c_int, [P, P]),
+    ("rm_runner_matched_edges", C.c_int, [P, C.POINTER(C.c_uint64)]),
+    ("rm_runner_get_matched_edges", C.c_int, [P, P, P, P, P]),
+    ("rm_runner_matched_edges_time", C.c_int, [P, C.POINTER(C.c_double)]),
     ("rm_runner_get_segments", C.c_int, [P, P, P]),
     ("rm_runner_get_reports", C.c_int, [P, P, P, P]),
     ("rm_runner_set_timing", C.c_int, [P, C.c_int]),

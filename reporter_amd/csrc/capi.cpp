@@ -28,6 +28,7 @@
 #include "engine.hpp"
 #include "graph.hpp"
 #include "host_pool.hpp"
+#include "edges_json.hpp"
 #include "json.hpp"
 #include "osm_model.hpp"
 #include "serve_policy.hpp"
@@ -533,7 +534,7 @@ struct PointsIn {
 };
 
 void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** outs, const PackedOut* pk = nullptr,
-                       const PointsIn* pin = nullptr) {
+                       const PointsIn* pin = nullptr, bool with_edges = false) {
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   std::vector<uint32_t> terr(n, 0u);
@@ -548,6 +549,17 @@ void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** o
   if (pin) {   // the matched-points stage runs here, on request, over what the run left in HBM
     mp.resize(pin->off[n]);
     mt.matched_points(mp.data());
+  }
+  // ... and so does the matched-edges stage (rm_match_edges*)
+  std::vector<uint32_t> eoff, shoff;
+  std::vector<MatchedEdge> me;
+  std::vector<float> shape;
+  if (with_edges) {
+    uint64_t tot[2];
+    mt.matched_edges(tot);
+    eoff.resize(n + 1); shoff.resize(n + 1);
+    me.resize(tot[0]); shape.resize(2 * tot[1]);
+    mt.get_matched_edges(eoff.data(), me.data(), shoff.data(), shape.data());
   }
   m->ms[3] = ms_since(t3);
   const auto t4 = clk::now();
@@ -584,6 +596,11 @@ void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** o
           const uint32_t o = pin->off[i];
           tj::append_matched_points(mp.data() + o, pin->off[i + 1] - o, pin->lon + o, pin->lat + o,
                                     [&](uint32_t e) { return edges[e].len_cm; }, js);
+        }
+        if (with_edges) {
+          const std::vector<uint64_t>& seg_id = mt.engine().host().seg_id;
+          tj::append_matched_edges(me.data() + eoff[i], eoff[i + 1] - eoff[i], shape.data() + 2 * (size_t)shoff[i],
+                                   shoff[i + 1] - shoff[i], [&](uint32_t sd) { return seg_id[sd]; }, js);
         }
         outs[i] = dup_string(js);
       }
@@ -744,9 +761,10 @@ bool json_device_enabled() {
 // caller's output strings.  Any failing trace fails the call, naming the trace.
 // points: the replies also carry matched_points (rm_match_points*); the requests are then parsed
 // on the host, whose staging keeps the input points an unmatched entry reports.
+// edges: the replies also carry edges and shape (rm_match_edges*); parsed on the host likewise.
 void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs,
-                      const PackedOut* pk = nullptr, bool points = false) {
-  if (n && !points && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk)) return;
+                      const PackedOut* pk = nullptr, bool points = false, bool edges = false) {
+  if (n && !points && !edges && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk)) return;
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   const auto t0 = clk::now();
@@ -807,7 +825,7 @@ void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char**
   mt.run(hb, rp);
   m->ms[2] = ms_since(t2);
   const PointsIn pin{hs.lon, hs.lat, off.data()};
-  finish_json_batch(m, mt, n, nt, outs, pk, points ? &pin : nullptr);
+  finish_json_batch(m, mt, n, nt, outs, pk, points ? &pin : nullptr, edges);
   m->ms[5] = ms_since(t0);
 }
 
@@ -1017,6 +1035,28 @@ int rm_match_points(rm_matcher* m, const char* trace_json, char** out_json) {
   if (!out_json) return fail("out_json is NULL");
   *out_json = nullptr;
   return rm_match_points_batch(m, &trace_json, 1, out_json);
+}
+
+int rm_match_edges_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("matcher is NULL");
+    for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    if (n == 0) return;
+    for (size_t i = 0; i < n; ++i)
+      if (!traces[i]) throw std::runtime_error("trace string is NULL");
+    try {
+      match_json_batch(m, traces, n, outs, nullptr, false, true);   // uncoalesced, whatever n is
+    } catch (...) {
+      for (size_t i = 0; i < n; ++i) { std::free(outs[i]); outs[i] = nullptr; }
+      throw;
+    }
+  });
+}
+
+int rm_match_edges(rm_matcher* m, const char* trace_json, char** out_json) {
+  if (!out_json) return fail("out_json is NULL");
+  *out_json = nullptr;
+  return rm_match_edges_batch(m, &trace_json, 1, out_json);
 }
 
 int rm_match(rm_matcher* m, const char* trace_json, char** out_json) {
@@ -1416,6 +1456,16 @@ int rm_runner_get_paths(rm_runner* r, uint32_t* a, uint32_t* b, uint32_t* c, uin
 int rm_runner_get_matched_points(rm_runner* r, rm_matched_point* out) {
   static_assert(sizeof(rm_matched_point) == sizeof(MatchedPoint), "rm_matched_point is rm::MatchedPoint");
   return guarded([&] { r->m->matched_points(reinterpret_cast<MatchedPoint*>(out)); });
+}
+int rm_runner_matched_edges(rm_runner* r, uint64_t out[2]) {
+  return guarded([&] { r->m->matched_edges(out); });
+}
+int rm_runner_get_matched_edges(rm_runner* r, uint32_t* edge_off, rm_matched_edge* edges, uint32_t* shape_off, float* shape) {
+  static_assert(sizeof(rm_matched_edge) == sizeof(MatchedEdge), "rm_matched_edge is rm::MatchedEdge");
+  return guarded([&] { r->m->get_matched_edges(edge_off, reinterpret_cast<MatchedEdge*>(edges), shape_off, shape); });
+}
+int rm_runner_matched_edges_time(rm_runner* r, double* ms) {
+  return guarded([&] { *ms = r->m->matched_edges_ms(); });
 }
 int rm_runner_get_segments(rm_runner* r, uint32_t* off, void* segs) {
   return guarded([&] { r->m->get_segments(off, (SegmentRec*)segs); });

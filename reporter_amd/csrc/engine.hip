@@ -5415,6 +5415,7 @@ Matcher::~Matcher() {
   ws_.release();
   if (dl_dev_) (void)hipFree(dl_dev_);
   if (mp_dev_) (void)hipFree(mp_dev_);
+  free_matched_edges();
   if (dl_host_) (void)hipHostFree(dl_host_);
   for (void* q : {(void*)jdev_, jspan_, (void*)jflag_, jtsp_})
     if (q) (void)hipFree(q);

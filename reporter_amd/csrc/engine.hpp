@@ -348,6 +348,15 @@ class Matcher {
   // Matched points of the last run()/rerun (rule 9; points.hip): one record per input point in
   // batch point order (n_points()), computed on request from what the run left in HBM
   void matched_points(MatchedPoint* out);
+  // Matched edges of the last run()/rerun (rule 10; edges.hip): every edge visit of every chain
+  // with its times, and each trace's matched polyline, computed on request from what the run left
+  // in HBM and kept on the device.  out: visits, shape vertices (of the whole batch)
+  void matched_edges(uint64_t out[2]);
+  // the result of the last matched_edges(): edge_off / shape_off (n_traces + 1 each; trace k's
+  // visits and vertices), the visits, the vertices as (lon, lat) pairs
+  void get_matched_edges(uint32_t* edge_off, MatchedEdge* edges, uint32_t* shape_off, float* shape);
+  // device time (ms) of the last matched_edges(): HIP events round its launches
+  double matched_edges_ms() const { return me_ms_; }
   // accumulated kernel time (ms) per KernelId since the last reset
   void kernel_times(double* ms, uint64_t* launches);
   // overflow-list sizes of the last run: routes A, routes B, paths A, candidates
@@ -456,6 +465,16 @@ class Matcher {
   size_t dl_dev_bytes_ = 0, dl_host_bytes_ = 0;
   void* mp_dev_ = nullptr;     // grow-only device buffer of matched_points (mp_cap_ records)
   uint64_t mp_cap_ = 0;
+  // matched_edges: grow-only device buffers (the visits staged per trace, the per-trace counts /
+  // offsets / totals, the compacted visits, the shapes), its events and the last call's sizes
+  void* me_stage_ = nullptr; void* me_small_ = nullptr; void* me_edges_ = nullptr; void* me_shape_ = nullptr;
+  uint64_t me_stage_cap_ = 0, me_small_cap_ = 0, me_edges_cap_ = 0, me_shape_cap_ = 0;
+  hipEvent_t me_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint32_t me_traces_ = 0;
+  uint64_t me_n_ = 0, me_v_ = 0;
+  double me_ms_ = 0.0;
+  bool me_ran_ = false;
+  void free_matched_edges();
   hipStream_t stream_ = nullptr;
   Workspace ws_;
   uint32_t n_traces_ = 0;

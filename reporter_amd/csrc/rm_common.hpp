@@ -468,7 +468,21 @@ struct MatchedPoint {
 };
 static_assert(sizeof(MatchedPoint) == 32, "MatchedPoint is two dwordx4");
 
-constexpr int kHistBins = 16;           // 10 km/h bins, 0..160 (reporter_service.py:133)
+// One matched edge (DESIGN.md §3 rule 10): one visit of a directed edge by a matched chain, as
+// the oracle's add_trav leaves it.  Same layout as rm_matched_edge (reporter_match.h).
+struct MatchedEdge {
+  uint32_t edge, way;               // directed edge, edge_way[edge]
+  uint32_t b_cm, e_cm;              // the part driven, in directed-edge coordinates
+  double t_enter, t_exit;           // distance-interpolated epoch times at b_cm and e_cm
+  uint32_t begin_point, end_point;  // original point index (within the trace) of the state at / before either end
+  uint32_t shape_begin, shape_end;  // the visit's first and last vertex in the trace's shape
+  uint32_t seg_dense, seg_off_cm;   // edge_seg[edge] (kNone: none), edge_seg_off[edge]
+  uint32_t flags, len_cm;           // kEdge* below; the edge's length
+};
+static_assert(sizeof(MatchedEdge) == 64, "MatchedEdge is four dwordx4");
+constexpr uint32_t kEdgeInternal = 1u, kEdgeHasSegment = 2u, kEdgeChainFirst = 4u;
+
+constexpr int kHistBins = 16;          // 10 km/h bins, 0..160 (reporter_service.py:133)
 
 // ---- block bases of the steady step's scans (engine.hip k_trans_apply_steady / k_path_apply_steady) ----
 // A counting kernel leaves one pair of u64 partials per block (part[2 * block]); every kScanGroup

@@ -34,6 +34,14 @@ MATCHED_POINT_DTYPE = np.dtype([
     ("type", "<u4"), ("route_cm", "<u4")])
 assert MATCHED_POINT_DTYPE.itemsize == 32
 
+# one matched edge (rm_matched_edge): a visit of a directed edge by a matched chain; flags bit 0
+# internal, bit 1 the edge has an OSMLR segment, bit 2 first visit of its chain
+MATCHED_EDGE_DTYPE = np.dtype([
+    ("edge", "<u4"), ("way", "<u4"), ("b_cm", "<u4"), ("e_cm", "<u4"), ("t_enter", "<f8"), ("t_exit", "<f8"),
+    ("begin_point", "<u4"), ("end_point", "<u4"), ("shape_begin", "<u4"), ("shape_end", "<u4"),
+    ("seg_dense", "<u4"), ("seg_off_cm", "<u4"), ("flags", "<u4"), ("len_cm", "<u4")])
+assert MATCHED_EDGE_DTYPE.itemsize == 64
+
 OPTIONS_DTYPE = np.dtype([
     ("mode", "<i4"), ("sigma_z", "<f4"), ("beta", "<f4"), ("search_radius", "<f4"), ("gps_accuracy", "<f4"),
     ("breakage_distance", "<f4"), ("interpolation_distance", "<f4"), ("max_route_distance_factor", "<f4"),
@@ -348,6 +356,29 @@ class BatchMatcher:
         out = np.empty(self.sizes()["points"], MATCHED_POINT_DTYPE)
         _lib.check(_lib.lib().rm_runner_get_matched_points(self._h, out.ctypes.data))
         return out
+
+    def matched_edges(self):
+        """Every edge visit of the last run with its times, and each trace's matched polyline
+        (DESIGN.md §3 rule 10): (edge_off, edges, shape_off, shape).  Trace k's visits are
+        edges[edge_off[k]:edge_off[k+1]] (MATCHED_EDGE_DTYPE), its vertices
+        shape[shape_off[k]:shape_off[k+1]] ((lon, lat) rows, float32; a visit's shape_begin /
+        shape_end index them).  The stage runs on this call, not during run()."""
+        T = self.sizes()["traces"]
+        tot = (C.c_uint64 * 2)()
+        _lib.check(_lib.lib().rm_runner_matched_edges(self._h, tot))
+        edge_off = np.zeros(T + 1, np.uint32)
+        shape_off = np.zeros(T + 1, np.uint32)
+        edges = np.empty(max(int(tot[0]), 1), MATCHED_EDGE_DTYPE)
+        shape = np.empty((max(int(tot[1]), 1), 2), np.float32)
+        _lib.check(_lib.lib().rm_runner_get_matched_edges(self._h, edge_off.ctypes.data, edges.ctypes.data,
+                                                          shape_off.ctypes.data, shape.ctypes.data))
+        return edge_off, edges[: int(tot[0])], shape_off, shape[: int(tot[1])]
+
+    def matched_edges_ms(self):
+        """Device time (ms) of the last matched_edges(): HIP events round its launches."""
+        ms = C.c_double(0.0)
+        _lib.check(_lib.lib().rm_runner_matched_edges_time(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def reports(self):
         sz = self.sizes()

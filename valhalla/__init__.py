@@ -109,6 +109,29 @@ class SegmentMatcher(object):
             for i in range(n):
                 _lib.lib().rm_free(outs[i])
 
+    def MatchEdges(self, trace_json):
+        """Match plus the edges driven and the matched polyline: the same request in,
+        {"segments": [...], "edges": [...], "shape": "..."} out (rm_match_edges; one entry per edge
+        visit with its times, length and shape indices, and the shape encoded at precision 6, as
+        Valhalla's trace_attributes gives them)."""
+        return self.MatchEdgesMany([trace_json])[0]
+
+    def MatchEdgesMany(self, trace_jsons):
+        """MatchEdges for many requests in one uncoalesced GPU batch (rm_match_edges_batch)."""
+        n = len(trace_jsons)
+        if n == 0:
+            return []
+        arr = (C.c_char_p * n)(*[t.encode("utf-8") if isinstance(t, str) else t for t in trace_jsons])
+        outs = (C.c_void_p * n)()
+        rc = _lib.lib().rm_match_edges_batch(self._h, arr, n, outs)
+        if rc != 0:
+            raise RuntimeError(_lib.last_error())
+        try:
+            return [C.string_at(outs[i]).decode("utf-8") for i in range(n)]
+        finally:
+            for i in range(n):
+                _lib.lib().rm_free(outs[i])
+
     def last_timing(self):
         """Host wall ms of the last uncoalesced MatchMany: parse, stage, engine, download, format, total."""
         out = (C.c_double * 6)()

@@ -419,6 +419,33 @@ int rm_runner_run_points(rm_runner* r, const rm_points_desc* d, const rm_run_par
 int rm_runner_get_trace_uuid(rm_runner* r, uint32_t* uuid);
 /* the batch the last run matched: trace_off (n_traces+1), lon, lat, time, accuracy (n_points) */
 int rm_runner_get_batch(rm_runner* r, uint32_t* trace_off, float* lon, float* lat, double* time, float* accuracy);
+/* Trace-file text read on the device (DESIGN.md §3 rule 11): the parse half of the reference's
+ * download phase (py/simple_reporter.py:100-113), the re-read of its match phase (:137-140) and
+ * the streaming formatter's separated-value lines (Formatter.java:97-109).  One point per line,
+ * fields split at `sep` (one byte, no quoting), columns counted from 0; acc_col -1: no accuracy
+ * column (accuracy is then -1, absent).  time_format 0: decimal epoch seconds; 1: exactly 19 bytes
+ * "YYYY-MM-DD HH:MM:SS" in UTC (digits at the fourteen digit positions).  accuracy_cap > 0: accuracy
+ * is min(ceil(v), cap) (:112 uses 1000).  use_bbox: a point with lat < bbox[0] || lat > bbox[2] ||
+ * lon < bbox[1] || lon > bbox[3] is dropped (:105).  rm_default_line_format: ',' and the columns
+ * uuid 0, time 1, lat 2, lon 3, accuracy 4 of the trace files (:113), epoch seconds, no cap, no box. */
+typedef struct { uint8_t sep; int32_t uuid_col, time_col, lat_col, lon_col, acc_col, time_format, accuracy_cap, use_bbox; double bbox[4]; } rm_line_format;
+void rm_default_line_format(rm_line_format* f);
+/* The input: n_chunks byte ranges (one per file; a chunk without a final newline ends its last
+ * line), under 2^32 bytes together.  Every window takes opts[0]. */
+typedef struct { uint32_t n_chunks; const char* const* data; const uint64_t* len; rm_line_format fmt;
+                 double inactivity_sec; uint32_t n_opts; const rm_options* opts; } rm_lines_desc;
+/* A malformed line fails either call with "chunk <c> line <l>: <reason>" (both 1-based, the first
+ * bad line in input order).  Vehicle ids are numbered in first-seen order over the kept points. */
+int rm_runner_run_lines(rm_runner* r, const rm_lines_desc* d, const rm_run_params* p);   /* parse, ids, windows, match */
+int rm_runner_parse_lines(rm_runner* r, const rm_lines_desc* d);                          /* parse and ids only */
+/* out: lines, blank, outside the box, points, vehicles, lines read on the host, 1 when the ids were assigned on the host */
+int rm_runner_lines_info(rm_runner* r, uint64_t out[7]);
+int rm_runner_get_line_points(rm_runner* r, uint32_t* uuid, double* time, float* lon, float* lat, float* acc); /* input order */
+int rm_runner_get_vehicles(rm_runner* r, uint32_t* chunk, uint64_t* off, uint32_t* len);   /* name span per vehicle */
+int rm_runner_lines_time(rm_runner* r, double ms[4]);   /* upload, parse (+ host lines), ids, windows */
+/* host only, no GPU: the generic rule over the same input; arrays sized by a first call with NULLs */
+int rm_lines_parse_host(const rm_lines_desc* d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat,
+                        float* acc, uint32_t* chunk, uint64_t* off, uint32_t* len, char* err, size_t errlen);
 typedef struct {
   uint32_t quantisation;      /* --quantisation, default 3600 (:343) */
   uint32_t privacy;           /* --privacy, default 2 (:345) */

@@ -82,6 +82,17 @@ class RmMatchedEdge(C.Structure):
                 ("seg_dense", C.c_uint32), ("seg_off_cm", C.c_uint32), ("flags", C.c_uint32), ("len_cm", C.c_uint32)]
 
 
+class RmLineFormat(C.Structure):
+    _fields_ = [("sep", C.c_uint8), ("uuid_col", C.c_int32), ("time_col", C.c_int32), ("lat_col", C.c_int32),
+                ("lon_col", C.c_int32), ("acc_col", C.c_int32), ("time_format", C.c_int32), ("accuracy_cap", C.c_int32),
+                ("use_bbox", C.c_int32), ("bbox", C.c_double * 4)]
+
+
+class RmLinesDesc(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("data", C.c_void_p), ("len", C.c_void_p), ("fmt", RmLineFormat),
+                ("inactivity_sec", C.c_double), ("n_opts", C.c_uint32), ("opts", C.c_void_p)]
+
+
 class RmTileParams(C.Structure):
     _fields_ = [("quantisation", C.c_uint32), ("privacy", C.c_uint32), ("source", C.c_char_p), ("mode", C.c_char_p)]
 
@@ -172,6 +183,15 @@ PROTOTYPES = [
     ("rm_runner_run_points", C.c_int, [P, C.POINTER(RmPointsDesc), C.POINTER(RmRunParams)]),
     ("rm_runner_get_trace_uuid", C.c_int, [P, P]),
     ("rm_runner_get_batch", C.c_int, [P, P, P, P, P, P]),
+    ("rm_default_line_format", None, [C.POINTER(RmLineFormat)]),
+    ("rm_runner_run_lines", C.c_int, [P, C.POINTER(RmLinesDesc), C.POINTER(RmRunParams)]),
+    ("rm_runner_parse_lines", C.c_int, [P, C.POINTER(RmLinesDesc)]),
+    ("rm_runner_lines_info", C.c_int, [P, C.POINTER(C.c_uint64)]),
+    ("rm_runner_get_line_points", C.c_int, [P, P, P, P, P, P]),
+    ("rm_runner_get_vehicles", C.c_int, [P, P, P, P]),
+    ("rm_runner_lines_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_lines_parse_host", C.c_int, [C.POINTER(RmLinesDesc), C.POINTER(C.c_uint64), P, P, P, P, P, P, P, P, C.c_char_p,
+                                      C.c_size_t]),
     ("rm_default_tile_params", None, [C.POINTER(RmTileParams)]),
     ("rm_runner_tiles", C.c_int, [P, C.POINTER(RmTileParams), P, C.POINTER(P), C.POINTER(C.c_size_t)]),
     ("rm_comm_unique_id", C.c_int, [P]),

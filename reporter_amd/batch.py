@@ -15,6 +15,11 @@ Reference phases and what replaces them:
                       Match + report() per window                   -> the matcher kernels + k_report
                       valid-report filter, hour buckets, rows       -> rm_runner_tiles (rows)
   report()  :211-254  sort, privacy cull, CSV, upload               -> rm_runner_tiles (cull + CSV)
+Ingest: the files' lines are parsed and the vehicle ids numbered on the GPU as well
+(--ingest device, the default: rm_runner_run_lines); --ingest host keeps the interpreted loop
+(read_trace_files + dense_ids) in front of rm_runner_run_points.  --formatter takes one of the
+reference's separated-value formatter strings (Formatter.java:36-51), --bbox and --accuracy-cap
+the download phase's filter and cap (py/simple_reporter.py:105,112), so raw lines can be read too.
 Multi-GPU: trace files are block-split over ranks (simple_reporter.split, :70-79, the
 reference's process split); rows of every rank are all-gathered over RCCL and each rank
 writes the tile files it owns.  There is no CPU path: the library raises without a GPU.
@@ -87,13 +92,34 @@ def write_tiles(files, dest_dir):
             f.write(body)
 
 
+def read_chunks(paths):
+    """The files' bytes, one chunk per file (mapped, not copied, where the file is not empty)."""
+    import mmap
+    chunks = []
+    for p in paths:
+        with open(p, "rb") as f:
+            chunks.append(mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(f.fileno()).st_size else b"")
+    return chunks
+
+
 def run(trace_files, conf, dest_dir, mode="auto", report_levels=(0, 1), transition_levels=(0, 1), quantisation=3600,
-        inactivity=120, privacy=2, source="smpl_rprt", rank=0, world=1, device=0, comm=None):
+        inactivity=120, privacy=2, source="smpl_rprt", rank=0, world=1, device=0, comm=None, ingest="device", fmt=None,
+        bbox=None):
     from . import dist, engine
+    if ingest not in ("device", "host"):
+        raise ValueError("ingest is 'device' or 'host'")
     mine = dist.split(sorted(trace_files), world)[rank] if world > 1 else sorted(trace_files)
     opts, graph = options_from_config(conf, mode)
-    uuids, pts = read_trace_files(mine)
-    idx, names = dense_ids(uuids)
+    if ingest == "host":
+        if fmt is not None or bbox is not None:
+            raise ValueError("a line format or box needs ingest='device'")
+        uuids, pts = read_trace_files(mine)
+        idx, names = dense_ids(uuids)
+    else:
+        chunks = read_chunks(mine)
+        fmt = fmt or engine.LineFormat()
+        if bbox is not None:
+            fmt.bbox = tuple(float(x) for x in bbox)
     eng = engine.Engine(graph, device)
     with open(conf) as f:
         radius = json.load(f).get("reporter_amd", {}).get("ball_radius")
@@ -102,11 +128,17 @@ def run(trace_files, conf, dest_dir, mode="auto", report_levels=(0, 1), transiti
     bm = engine.BatchMatcher(eng)
     bm.set_isolation(True)   # a failing window is logged and skipped (py/simple_reporter.py:169-173)
     try:
-        bm.run_points(idx, pts["time"], pts["lon"], pts["lat"], pts["accuracy"], inactivity=inactivity, opts=opts,
-                      n_uuids=len(names), report_levels=report_levels, transition_levels=transition_levels)
+        if ingest == "host":
+            bm.run_points(idx, pts["time"], pts["lon"], pts["lat"], pts["accuracy"], inactivity=inactivity, opts=opts,
+                          n_uuids=len(names), report_levels=report_levels, transition_levels=transition_levels)
+        else:
+            bm.run_lines(chunks, fmt, inactivity=inactivity, opts=opts, report_levels=report_levels,
+                         transition_levels=transition_levels)
         errs = bm.trace_errors()
         if errs.any():
             owner = bm.trace_uuid()
+            if ingest == "device":
+                names = bm.vehicle_names(chunks)
             for k in np.nonzero(errs)[0]:
                 logging.error("%s window %d failed to match (error bits %d); skipped", names[owner[k]], k, int(errs[k]))
         files = bm.tiles(quantisation=quantisation, privacy=privacy, source=source, mode=mode, comm=comm)
@@ -129,6 +161,11 @@ def main(argv=None):
     ap.add_argument("--inactivity", type=int, default=120)
     ap.add_argument("--privacy", type=int, default=2)
     ap.add_argument("--source-id", default="smpl_rprt")
+    ap.add_argument("--ingest", choices=("device", "host"), default="device", help="where the trace lines are parsed")
+    ap.add_argument("--formatter", help="separated-value formatter string, e.g. ',sv,\\|,1,9,10,0,5,yyyy-MM-dd HH:mm:ss' "
+                    "(default: the trace files' uuid,time,lat,lon,accuracy)")
+    ap.add_argument("--bbox", help="min_lat,min_lon,max_lat,max_lon: points outside are dropped")
+    ap.add_argument("--accuracy-cap", type=int, default=0, help="cap on the accuracy column (0: none)")
     a = ap.parse_args(argv)
     files = []
     for root, _, fs in os.walk(a.trace_dir):
@@ -141,9 +178,17 @@ def main(argv=None):
         from . import dist
         comm = dist.Comm(rank, world, local)
     levels = lambda s: tuple(int(x) for x in s.split(",") if x != "")
+    fmt = None
+    if a.formatter or a.accuracy_cap:
+        from . import engine
+        fmt = engine.LineFormat.from_spec(a.formatter) if a.formatter else engine.LineFormat()
+        fmt.accuracy_cap = a.accuracy_cap
+    bbox = [float(x) for x in a.bbox.split(",")] if a.bbox else None
+    if bbox is not None and len(bbox) != 4:
+        ap.error("--bbox takes min_lat,min_lon,max_lat,max_lon")
     try:
         out = run(files, a.match_config, a.dest_dir, a.mode, levels(a.report_levels), levels(a.transition_levels),
-                  a.quantisation, a.inactivity, a.privacy, a.source_id, rank, world, local, comm)
+                  a.quantisation, a.inactivity, a.privacy, a.source_id, rank, world, local, comm, a.ingest, fmt, bbox)
     finally:
         if comm is not None:
             comm.close()

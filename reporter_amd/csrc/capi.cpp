@@ -1754,6 +1754,53 @@ int rm_runner_get_batch(rm_runner* r, uint32_t* off, float* lon, float* lat, dou
   return guarded([&] { r->m->get_batch(off, lon, lat, time, acc); });
 }
 
+// ---------------- trace-file text (lines.hip) ----------------
+static_assert(sizeof(rm_line_format) == sizeof(sv::Format), "rm_line_format is sv::Format");
+void rm_default_line_format(rm_line_format* f) {
+  const sv::Format d = sv::default_format();
+  std::memcpy(f, &d, sizeof d);
+}
+static LinesDesc to_lines(const rm_lines_desc* d) {
+  if (!d) throw std::runtime_error("lines descriptor is NULL");
+  LinesDesc ld;
+  ld.n_chunks = d->n_chunks; ld.data = d->data; ld.len = d->len;
+  std::memcpy(&ld.fmt, &d->fmt, sizeof ld.fmt);
+  ld.inactivity = d->inactivity_sec; ld.n_opts = d->n_opts; ld.opts = (const MatchOptions*)d->opts;
+  return ld;
+}
+int rm_runner_run_lines(rm_runner* r, const rm_lines_desc* d, const rm_run_params* p) {
+  return guarded([&] {
+    if (!r) throw std::runtime_error("runner is NULL");
+    r->m->run_lines(to_lines(d), to_rp(p));
+  });
+}
+int rm_runner_parse_lines(rm_runner* r, const rm_lines_desc* d) {
+  return guarded([&] {
+    if (!r) throw std::runtime_error("runner is NULL");
+    r->m->parse_lines(to_lines(d));
+  });
+}
+int rm_runner_lines_info(rm_runner* r, uint64_t out[7]) { return guarded([&] { r->m->lines_info(out); }); }
+int rm_runner_get_line_points(rm_runner* r, uint32_t* uuid, double* time, float* lon, float* lat, float* acc) {
+  return guarded([&] { r->m->get_line_points(uuid, time, lon, lat, acc); });
+}
+int rm_runner_get_vehicles(rm_runner* r, uint32_t* chunk, uint64_t* off, uint32_t* len) {
+  return guarded([&] { r->m->get_vehicles(chunk, off, len); });
+}
+int rm_runner_lines_time(rm_runner* r, double ms[4]) { return guarded([&] { r->m->lines_time(ms); }); }
+int rm_lines_parse_host(const rm_lines_desc* d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat,
+                        float* acc, uint32_t* chunk, uint64_t* off, uint32_t* len, char* err, size_t errlen) {
+  const int rc = guarded([&] {
+    if (!info) throw std::runtime_error("info is NULL");
+    lines_parse_host(to_lines(d), info, uuid, time, lon, lat, acc, chunk, off, len);
+  });
+  if (rc && err && errlen) {
+    std::strncpy(err, g_err.c_str(), errlen - 1);
+    err[errlen - 1] = 0;
+  }
+  return rc;
+}
+
 void rm_default_tile_params(rm_tile_params* p) {
   p->quantisation = 3600; p->privacy = 2; p->source = "smpl_rprt"; p->mode = "auto";
 }

@@ -19,6 +19,7 @@
 #include "graph.hpp"
 #include "rm_common.hpp"
 #include "serve_policy.hpp"
+#include "sv_lines.hpp"
 
 namespace rm {
 
@@ -233,6 +234,23 @@ struct PointsDesc {
   const uint32_t* uuid_opt = nullptr;  // per vehicle index into opts (NULL: all use opts[0])
 };
 
+// Raw trace-file text for Matcher::parse_lines / run_lines (lines.hip): one chunk per file, lines
+// in sv_lines.hpp's format; every window takes opts[0]
+struct LinesDesc {
+  uint32_t n_chunks = 0;
+  const char* const* data = nullptr;
+  const uint64_t* len = nullptr;
+  sv::Format fmt;
+  double inactivity = 120.0;
+  uint32_t n_opts = 0;
+  const MatchOptions* opts = nullptr;
+};
+struct LineState;   // lines.hip: the device buffers and the last call's results of the line reader
+// the generic rule over the same input on the host alone (no GPU); null arrays are not written,
+// info as Matcher::lines_info
+void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
+                      uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len);
+
 // Time-tile stage parameters (simple_reporter.py:176-196, 211-254; CLI defaults :343,345,346)
 struct TileParams {
   uint32_t quantisation = 3600;
@@ -388,6 +406,22 @@ class Matcher {
   // Raw point stream -> per-vehicle time sort and inactivity windows of >= 2 points on the
   // GPU (simple_reporter.py:137-164), then every matching stage over the windows.
   void run_points(const PointsDesc& pd, const RunParams& rp);
+  // The same from the points already in StageBufs (p_uuid, p_time, p_lon, p_lat, p_acc): everything
+  // from k_pt_keys on.  n_uopt: vehicles with an option index in p_uopt (0: all take opts[0]);
+  // windows_done: recorded once the windows are built, before the matcher runs
+  void run_points_device(uint64_t n, double tbase, double inactivity, const MatchOptions* opts, uint32_t n_opts,
+                         uint32_t n_uopt, const RunParams& rp, hipEvent_t windows_done = nullptr);
+  // Trace-file text -> points on the device (lines.hip; DESIGN.md §3 rule 11): lines parsed by
+  // k_line_parse (the generic host reader for lines outside the compact layout), the kept points
+  // packed in input order into StageBufs, vehicle ids numbered in first-seen order.  run_lines
+  // then windows and matches them as run_points does.  Throws "chunk <c> line <l>: <reason>".
+  void parse_lines(const LinesDesc& d);
+  void run_lines(const LinesDesc& d, const RunParams& rp);
+  // lines, blank, outside the box, points, vehicles, lines read on the host, 1: ids assigned on the host
+  void lines_info(uint64_t out[7]) const;
+  void get_line_points(uint32_t* uuid, double* time, float* lon, float* lat, float* acc);   // input order
+  void get_vehicles(uint32_t* chunk, uint64_t* off, uint32_t* len);   // name span per vehicle
+  void lines_time(double ms[4]) const;   // upload, parse (+ host lines), ids, windows
   // vehicle index of every window of the last run_points (n_traces entries)
   void get_trace_uuid(uint32_t* out);
   // the batch the last run matched (after run_points: the windows built on the device)
@@ -489,6 +523,7 @@ class Matcher {
   uint32_t err_bits_ = 0;
   uint32_t* hctl_ = nullptr;  // pinned host mirror of the control words
   StageBufs sb_;
+  std::shared_ptr<LineState> ls_;
   bool from_points_ = false;
   uint32_t mode_mask_ = 0;   // travel modes of the batch (bit per Mode): which route balls K2 needs
   uint32_t turn_mask_ = 0;   // modes of the batch with a turn_penalty_factor > 0: turn rows, route_d

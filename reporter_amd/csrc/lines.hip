@@ -1,0 +1,639 @@
+// lines.hip — the ingest stage of the batch pipeline on the device (DESIGN.md §3 rule 11): the text
+// of trace files (reference py/simple_reporter.py:100-113, :137-140; Formatter.java:97-109) becomes
+// the point arrays rm_runner_run_points starts from, with no interpreted loop per point.
+//
+//   upload      the chunks (one per file) laid end to end in one byte buffer, a '\n' inserted after
+//               a chunk that lacks one, 16 bytes of '\n' in front (byte 0 is a line start like any
+//               other) and zeros behind (a window may read past the end)
+//   k_line_count / scan   line starts per 4096-byte window -> each window's first line index
+//   k_line_parse          one wave per window: the window and the 256 bytes its lines can reach
+//               staged in LDS with 16-byte loads, ballots over consecutive 64-byte chunks list the
+//               line starts in order, lane j reads line j by sv::compact_line, 64 lines a round
+//   host lines  lines outside the compact layout are read by sv::generic_line on the host pool
+//               and patched into their slots; the first malformed line in input order fails the call
+//   compaction  k_line_stats flags the points (and counts the blank, outside and host lines, so the
+//               statuses come back only when there are host lines); scan over "is a point" -> the
+//               kept points in input order in StageBufs
+//   ids         stable sort of (hash, point), group starts + byte compare of neighbours, scan,
+//               sort of the groups by their first point -> first-seen rank per point (dense_ids'
+//               order); a hash collision sends the numbering to the host (same result)
+// Every output position comes from a scan or a stable sort: no atomics, the same result each call.
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <string_view>
+#include <unordered_map>
+
+#include "engine.hpp"
+#include "host_pool.hpp"
+
+namespace rm {
+
+namespace {
+
+constexpr uint32_t kLineWin = 4096;                               // bytes of text per wave
+constexpr uint32_t kLineFront = 16;                               // '\n' bytes in front of the text
+constexpr uint32_t kLineLds = kLineFront + kLineWin + sv::kMaxLine;   // a window's bytes in LDS
+constexpr uint64_t kLineTail = kLineWin + kLineLds;               // zero bytes kept behind the text
+constexpr uint32_t kLineRing = 128;                               // line starts listed ahead of a round
+static_assert(kLineLds % 16 == 0, "windows are staged with 16-byte loads");
+
+inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
+
+// bytes of w equal to '\n'
+__device__ __forceinline__ uint32_t newlines(uint32_t w) {
+  const uint32_t x = w ^ 0x0a0a0a0au;
+  const uint32_t t = (x & 0x7f7f7f7fu) + 0x7f7f7f7fu;
+  return (uint32_t)__popc(~(t | x | 0x7f7f7f7fu));
+}
+
+// line starts in window w: text positions p in [w * kLineWin, (w + 1) * kLineWin), p < N, whose
+// previous byte is '\n'.  Counted as the '\n' of the window's bytes, shifted by one at either end.
+__global__ void __launch_bounds__(64) k_line_count(const uint8_t* buf, uint64_t N, uint32_t* cnt) {
+  const uint64_t a = (uint64_t)blockIdx.x * kLineWin;
+  const uint4* src = reinterpret_cast<const uint4*>(buf + kLineFront + a);
+  uint32_t n = 0;
+  for (uint32_t r = 0; r < kLineWin / 16 / 64; ++r) {
+    const uint4 v = src[r * 64 + threadIdx.x];
+    n += newlines(v.x) + newlines(v.y) + newlines(v.z) + newlines(v.w);
+  }
+  for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
+  if (threadIdx.x == 0) {
+    n += buf[kLineFront + a - 1] == '\n';
+    n -= buf[kLineFront + a + kLineWin - 1] == '\n';
+    if (N >= a && N < a + kLineWin) --n;   // the text's last '\n' starts no line
+    cnt[blockIdx.x] = n;
+  }
+}
+
+struct LineArrays {   // one entry per line
+  uint8_t* status;
+  float* lat;
+  float* lon;
+  float* acc;
+  double* time;
+  uint32_t* id_off;   // the id's offset in the text; of a host line: the line's
+  uint32_t* id_len;
+  unsigned long long* hash;
+};
+
+__global__ void __launch_bounds__(64) k_line_parse(const uint8_t* buf, uint64_t N, const uint32_t* first,
+                                                   const uint32_t* cnt, uint32_t L, sv::Format fmt, LineArrays o,
+                                                   uint32_t* err) {
+  __shared__ uint4 win4[kLineLds / 16];
+  __shared__ uint16_t starts[kLineRing];
+  const uint8_t* win = reinterpret_cast<const uint8_t*>(win4);   // win[i]: text position a - kLineFront + i
+  const uint32_t lane = threadIdx.x;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const uint64_t a = (uint64_t)blockIdx.x * kLineWin;
+  for (uint32_t x = lane; x < kLineLds / 16; x += 64) win4[x] = reinterpret_cast<const uint4*>(buf + a)[x];
+  __syncthreads();
+  const uint32_t lim = N - a < (uint64_t)kLineWin ? (uint32_t)(N - a) : kLineWin;
+  const uint32_t base = first[blockIdx.x];
+  uint32_t head = 0, tail = 0;
+  auto round = [&](uint32_t nr) {   // lines head .. head + nr of the window, one per lane
+    __syncthreads();
+    const uint32_t k = base + head + lane;
+    if (lane < nr && k < L) {   // k < L always, unless the two kernels disagree (err below)
+      const uint32_t pos = starts[(head + lane) & (kLineRing - 1)];
+      sv::Line ln;
+      const uint32_t st = sv::compact_line(win + kLineFront + pos, fmt, ln);
+      o.status[k] = (uint8_t)st;
+      if (st == sv::kPoint) {
+        o.lat[k] = ln.lat;
+        o.lon[k] = ln.lon;
+        o.acc[k] = ln.acc;
+        o.time[k] = ln.time;
+        o.id_off[k] = (uint32_t)a + pos + ln.id_off;
+        o.id_len[k] = ln.id_len;
+        o.hash[k] = ln.hash;
+      } else if (st == sv::kHost) {
+        o.id_off[k] = (uint32_t)a + pos;
+      }
+    }
+    head += nr;
+  };
+  for (uint32_t c0 = 0; c0 < lim; c0 += 64) {
+    const uint32_t pos = c0 + lane;
+    const bool open = pos < lim && win[kLineFront + pos - 1] == '\n';
+    const unsigned long long m = __ballot(open);
+    if (open) starts[(tail + (uint32_t)__popcll(m & below)) & (kLineRing - 1)] = (uint16_t)pos;
+    tail += (uint32_t)__popcll(m);
+    if (tail - head >= 64u) round(64u);
+  }
+  if (tail > head) round(tail - head);
+  if (lane == 0 && tail != cnt[blockIdx.x]) err[0] = 1u;   // the two kernels disagree: the host throws
+}
+
+struct LinePatch {   // the host lines' results, one entry per host line
+  const uint32_t* line;
+  const uint8_t* status;
+  const float* lat;
+  const float* lon;
+  const float* acc;
+  const double* time;
+  const uint32_t* id_off;
+  const uint32_t* id_len;
+  const unsigned long long* hash;
+};
+
+__global__ void k_line_patch(uint32_t n, LinePatch p, LineArrays o) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t k = p.line[i];
+  o.status[k] = p.status[i];
+  o.lat[k] = p.lat[i];
+  o.lon[k] = p.lon[i];
+  o.acc[k] = p.acc[i];
+  o.time[k] = p.time[i];
+  o.id_off[k] = p.id_off[i];
+  o.id_len[k] = p.id_len[i];
+  o.hash[k] = p.hash[i];
+}
+
+// "is a point" per line for the compaction scan, and per block the blank, outside and host lines
+// (the host folds the at most 1024 triples)
+__global__ void __launch_bounds__(256) k_line_stats(uint64_t L, const uint8_t* status, uint32_t* flag, uint32_t* part) {
+  __shared__ uint32_t acc[4][3];
+  uint32_t nb = 0, no = 0, nh = 0;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < L; k += (uint64_t)gridDim.x * 256) {
+    const uint32_t st = status[k];
+    flag[k] = st == sv::kPoint ? 1u : 0u;
+    nb += st == sv::kBlank;
+    no += st == sv::kOutside;
+    nh += st == sv::kHost;
+  }
+  for (int o = 32; o > 0; o >>= 1) { nb += __shfl_xor(nb, o); no += __shfl_xor(no, o); nh += __shfl_xor(nh, o); }
+  if ((threadIdx.x & 63) == 0) { acc[threadIdx.x >> 6][0] = nb; acc[threadIdx.x >> 6][1] = no; acc[threadIdx.x >> 6][2] = nh; }
+  __syncthreads();
+  if (threadIdx.x < 3) part[3 * blockIdx.x + threadIdx.x] = acc[0][threadIdx.x] + acc[1][threadIdx.x] + acc[2][threadIdx.x] + acc[3][threadIdx.x];
+}
+
+// the kept points in input order: the point arrays, the id spans, the sort's (hash, point) pairs
+__global__ void k_line_compact(uint64_t L, LineArrays o, const uint32_t* flag, const uint32_t* pos, unsigned long long mask,
+                               double* p_time, float* p_lon, float* p_lat, float* p_acc, uint32_t* p_off, uint32_t* p_len,
+                               unsigned long long* key, uint32_t* val) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= L || !flag[k]) return;
+  const uint32_t d = pos[k];
+  p_time[d] = o.time[k];
+  p_lon[d] = o.lon[k];
+  p_lat[d] = o.lat[k];
+  p_acc[d] = o.acc[k];
+  p_off[d] = o.id_off[k];
+  p_len[d] = o.id_len[k];
+  key[d] = o.hash[k] & mask;
+  val[d] = d;
+}
+
+// sorted by hash (stable: by point within a hash): a group starts where the hash changes; inside
+// a group every point's id bytes must equal its neighbour's, else two ids share the hash
+__global__ void k_id_flags(uint64_t P, const unsigned long long* key, const uint32_t* pt, const uint32_t* p_off,
+                           const uint32_t* p_len, const uint8_t* text, uint32_t* flag, uint32_t* collide) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= P) return;
+  uint32_t f = 1;
+  if (k > 0 && key[k] == key[k - 1]) {
+    f = 0;
+    const uint32_t x = pt[k], y = pt[k - 1], n = p_len[x];
+    bool same = n == p_len[y];
+    const uint8_t* sx = text + p_off[x];
+    const uint8_t* sy = text + p_off[y];
+    for (uint32_t i = 0; same && i < n; ++i) same = sx[i] == sy[i];
+    if (!same) collide[0] = 1u;
+  }
+  flag[k] = f;
+}
+
+// group g's first point (the sort is stable, so it is the smallest), and each point's group
+__global__ void k_id_groups(uint64_t P, const uint32_t* flag, const uint32_t* gidx, const uint32_t* pt,
+                            unsigned long long* gfirst, uint32_t* gval, uint32_t* p_group, uint32_t* hctl) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= P) return;
+  const uint32_t g = gidx[k] + flag[k] - 1u;
+  p_group[pt[k]] = g;
+  if (flag[k]) { gfirst[g] = pt[k]; gval[g] = g; }
+  if (k + 1 == P) hctl[0] = g + 1u;
+}
+
+// groups sorted by first point: rank r is vehicle r, named by that point's id span
+__global__ void k_id_rank(uint32_t G, const unsigned long long* gfirst, const uint32_t* gval, const uint32_t* p_off,
+                          const uint32_t* p_len, uint32_t* rank, uint32_t* v_off, uint32_t* v_len) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= G) return;
+  const uint32_t p = (uint32_t)gfirst[r];
+  rank[gval[r]] = r;
+  v_off[r] = p_off[p];
+  v_len[r] = p_len[p];
+}
+
+__global__ void k_id_scatter(uint64_t P, const uint32_t* p_group, const uint32_t* rank, uint32_t* p_uuid) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < P) p_uuid[k] = rank[p_group[k]];
+}
+
+// per block the smallest and largest time; the host folds the (at most 1024) pairs
+__global__ void __launch_bounds__(256) k_time_span(uint64_t P, const double* time, double* part) {
+  __shared__ double lo[4], hi[4];
+  double a = time[0], b = a;
+  for (uint64_t k = (uint64_t)blockIdx.x * 256 + threadIdx.x; k < P; k += (uint64_t)gridDim.x * 256) {
+    const double t = time[k];
+    a = t < a ? t : a;
+    b = t > b ? t : b;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const double x = __shfl_xor(a, o), y = __shfl_xor(b, o);
+    a = x < a ? x : a;
+    b = y > b ? y : b;
+  }
+  if ((threadIdx.x & 63) == 0) { lo[threadIdx.x >> 6] = a; hi[threadIdx.x >> 6] = b; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) { a = lo[w] < a ? lo[w] : a; b = hi[w] > b ? hi[w] : b; }
+    part[2 * blockIdx.x] = a;
+    part[2 * blockIdx.x + 1] = b;
+  }
+}
+
+struct DevBuf {   // a grow-only device allocation
+  void* p = nullptr;
+  uint64_t bytes = 0;
+  void need(uint64_t n, hipStream_t st) {
+    if (n <= bytes && p) return;
+    if (p) { RM_HIP(hipStreamSynchronize(st)); (void)hipFree(p); p = nullptr; bytes = 0; }
+    const uint64_t c = n + n / 4 + 256;
+    RM_HIP(hipMalloc(&p, c));
+    bytes = c;
+  }
+  template <class T> T* as() const { return (T*)p; }
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+unsigned long long hash_mask() {   // RM_LINES_HASH_BITS (1-64, default 64), read at every call
+  long bits = 64;
+  if (const char* e = std::getenv("RM_LINES_HASH_BITS")) {
+    const long v = std::strtol(e, nullptr, 10);
+    if (v >= 1 && v <= 64) bits = v;
+  }
+  return bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
+}
+
+struct HostLine {
+  uint32_t line = 0, status = 0;
+  sv::Line v{};
+  const char* why = nullptr;
+};
+
+}  // namespace
+
+struct LineState {
+  DevBuf text, wcnt, wfirst, scan_tmp, status, lat, lon, acc, time, id_off, id_len, hash, flag, pos;
+  DevBuf p_off, p_len, v_off, v_len, patch, part, stats, derr;
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint32_t* hctl = nullptr;   // pinned read-back words
+  // the last call
+  std::vector<uint64_t> chunk_base;   // n_chunks + 1: where each chunk starts in the text
+  std::vector<uint32_t> veh_off, veh_len;
+  uint64_t info[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint64_t n_points = 0;
+  double tmin = 0.0, tmax = 0.0;
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  bool parsed = false;
+  ~LineState() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    if (hctl) (void)hipHostFree(hctl);
+  }
+  // the chunk holding text position `at`
+  uint32_t chunk_of(uint64_t at) const {
+    return (uint32_t)(std::upper_bound(chunk_base.begin(), chunk_base.end() - 1, at) - chunk_base.begin()) - 1u;
+  }
+};
+
+void Matcher::parse_lines(const LinesDesc& d) {
+  RM_HIP(hipSetDevice(eng_->device()));
+  if (!ls_) ls_ = std::make_shared<LineState>();
+  LineState& z = *ls_;
+  z.parsed = false;
+  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
+  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  hipStream_t st = stream_;
+  if (!z.hctl) {
+    RM_HIP(hipHostMalloc((void**)&z.hctl, 16 * sizeof(uint32_t), hipHostMallocDefault));
+    for (hipEvent_t& e : z.ev) RM_HIP(hipEventCreate(&e));
+  }
+  // ---- the text: chunks end to end, each ending in '\n'
+  z.chunk_base.assign(d.n_chunks + 1ull, 0);
+  uint64_t N = 0;
+  for (uint32_t c = 0; c < d.n_chunks; ++c) {
+    z.chunk_base[c] = N;
+    if (d.len[c] && !d.data[c]) throw std::runtime_error("line chunk is NULL");
+    N += d.len[c];
+    if (d.len[c] && d.data[c][d.len[c] - 1] != '\n') ++N;
+    if (N >= (1ull << 32)) throw std::runtime_error("line input too large (the chunks of one call must stay under 2^32 bytes)");
+  }
+  z.chunk_base[d.n_chunks] = N;
+  std::fill(z.info, z.info + 7, 0);
+  z.veh_off.clear();
+  z.veh_len.clear();
+  z.n_points = 0;
+  std::fill(z.ms, z.ms + 4, 0.0);
+  if (N == 0) { z.parsed = true; return; }
+  RM_HIP(hipEventRecord(z.ev[0], st));
+  z.text.need(kLineFront + N + kLineTail, st);
+  uint8_t* text = z.text.as<uint8_t>();
+  RM_HIP(hipMemsetAsync(text, '\n', kLineFront, st));
+  RM_HIP(hipMemsetAsync(text + kLineFront + N, 0, kLineTail, st));
+  for (uint32_t c = 0; c < d.n_chunks; ++c) {
+    if (!d.len[c]) continue;
+    uint8_t* at = text + kLineFront + z.chunk_base[c];
+    RM_HIP(hipMemcpyAsync(at, d.data[c], d.len[c], hipMemcpyHostToDevice, st));
+    if (d.data[c][d.len[c] - 1] != '\n') RM_HIP(hipMemsetAsync(at + d.len[c], '\n', 1, st));
+  }
+  RM_HIP(hipEventRecord(z.ev[1], st));
+  // ---- lines per window, each window's first line
+  const uint32_t nwin = (uint32_t)((N + kLineWin - 1) / kLineWin);
+  z.wcnt.need(nwin * 4ull, st);
+  z.wfirst.need(nwin * 4ull, st);
+  z.derr.need(8, st);
+  RM_HIP(hipMemsetAsync(z.derr.p, 0, 8, st));
+  hipLaunchKernelGGL(k_line_count, dim3(nwin), dim3(64), 0, st, text, N, z.wcnt.as<uint32_t>());
+  auto scan = [&](const uint32_t* in, uint32_t* out, uint64_t n) {
+    size_t need = 0;
+    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, (int)n, st));
+    z.scan_tmp.need(need, st);
+    need = z.scan_tmp.bytes;
+    RM_HIP(hipcub::DeviceScan::ExclusiveSum(z.scan_tmp.p, need, in, out, (int)n, st));
+  };
+  scan(z.wcnt.as<uint32_t>(), z.wfirst.as<uint32_t>(), nwin);
+  RM_HIP(hipMemcpyAsync(z.hctl + 0, z.wfirst.as<uint32_t>() + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipMemcpyAsync(z.hctl + 1, z.wcnt.as<uint32_t>() + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipStreamSynchronize(st));
+  const uint64_t L = (uint64_t)z.hctl[0] + z.hctl[1];
+  if (L == 0 || L >= 0x7fffffffull) throw std::runtime_error("line input: line count out of range");
+  // ---- every line read
+  z.status.need(L, st); z.lat.need(L * 4, st); z.lon.need(L * 4, st); z.acc.need(L * 4, st); z.time.need(L * 8, st);
+  z.id_off.need(L * 4, st); z.id_len.need(L * 4, st); z.hash.need(L * 8, st); z.flag.need(L * 4, st); z.pos.need(L * 4, st);
+  LineArrays la{z.status.as<uint8_t>(), z.lat.as<float>(), z.lon.as<float>(), z.acc.as<float>(), z.time.as<double>(),
+                z.id_off.as<uint32_t>(), z.id_len.as<uint32_t>(), z.hash.as<unsigned long long>()};
+  hipLaunchKernelGGL(k_line_parse, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
+                     (uint32_t)L, d.fmt, la, z.derr.as<uint32_t>());
+  RM_HIP(hipGetLastError());
+  // ---- "is a point" flags and the counts of the rest
+  const uint32_t sb = std::min<uint32_t>(1024u, grid(L));
+  z.stats.need(sb * 12ull, st);
+  std::vector<uint32_t> spart(3ull * sb);
+  uint64_t count[3] = {0, 0, 0};   // blank, outside, host
+  auto stats = [&] {
+    hipLaunchKernelGGL(k_line_stats, dim3(sb), dim3(256), 0, st, L, la.status, z.flag.as<uint32_t>(), z.stats.as<uint32_t>());
+    RM_HIP(hipMemcpyAsync(spart.data(), z.stats.p, sb * 12ull, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipMemcpyAsync(z.hctl + 2, z.derr.p, 4, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipStreamSynchronize(st));
+    count[0] = count[1] = count[2] = 0;
+    for (uint32_t b = 0; b < sb; ++b)
+      for (int i = 0; i < 3; ++i) count[i] += spart[3 * b + i];
+  };
+  stats();
+  if (z.hctl[2]) throw std::runtime_error("line reader: the count and parse kernels disagree on a window's lines");
+  // ---- host lines: the generic rule, patched into their slots
+  const uint32_t H = (uint32_t)count[2];
+  if (H) {
+    std::vector<uint8_t> status(L);
+    RM_HIP(hipMemcpy(status.data(), la.status, L, hipMemcpyDeviceToHost));
+    std::vector<HostLine> hl;
+    hl.reserve(H);
+    for (const uint8_t* p = status.data(), *e = p + L; (p = (const uint8_t*)std::memchr(p, (int)sv::kHost, (size_t)(e - p))); ++p) {
+      HostLine h;
+      h.line = (uint32_t)(p - status.data());
+      hl.push_back(h);
+    }
+    if (hl.size() != H) throw std::runtime_error("line reader: host line count changed");
+    std::vector<uint32_t> off(L);
+    RM_HIP(hipMemcpy(off.data(), la.id_off, L * 4, hipMemcpyDeviceToHost));
+    HostPool& pool = HostPool::get();
+    const size_t nt = std::max<size_t>(1, std::min<size_t>(pool.size(), H / 256u + 1u));
+    pool.run(nt, [&](size_t t) {
+      for (size_t i = H * t / nt, e = H * (t + 1) / nt; i < e; ++i) {
+        HostLine& h = hl[i];
+        const uint64_t at = off[h.line];
+        const uint32_t c = z.chunk_of(at);
+        const uint8_t* b = (const uint8_t*)d.data[c] + (at - z.chunk_base[c]);
+        const uint8_t* ce = (const uint8_t*)d.data[c] + d.len[c];
+        const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(ce - b));
+        h.status = sv::generic_line(b, nl ? nl : ce, d.fmt, h.v, &h.why);
+        h.v.id_off += (uint32_t)at;
+      }
+    });
+    for (const HostLine& h : hl) {   // in input order: the first bad line fails the call
+      if (h.status != sv::kBad) continue;
+      const uint64_t at = off[h.line];
+      const uint32_t c = z.chunk_of(at);
+      const char* b = d.data[c];
+      const uint64_t line = 1 + (uint64_t)std::count(b, b + (at - z.chunk_base[c]), '\n');
+      throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + h.why);
+    }
+    // one block: line, id_off, id_len, lat, lon, acc (u32 / f32), then time, hash, then status
+    const uint64_t Hp = (H + 1ull) & ~1ull;
+    std::vector<uint8_t> blk(Hp * 24 + Hp * 16 + Hp);
+    uint32_t* w = (uint32_t*)blk.data();
+    double* tm = (double*)(blk.data() + Hp * 24);
+    unsigned long long* hs = (unsigned long long*)(blk.data() + Hp * 32);
+    uint8_t* sp = blk.data() + Hp * 40;
+    for (uint32_t i = 0; i < H; ++i) {
+      const HostLine& h = hl[i];
+      w[i] = h.line; w[Hp + i] = h.v.id_off; w[2 * Hp + i] = h.v.id_len;
+      std::memcpy(&w[3 * Hp + i], &h.v.lat, 4); std::memcpy(&w[4 * Hp + i], &h.v.lon, 4); std::memcpy(&w[5 * Hp + i], &h.v.acc, 4);
+      tm[i] = h.v.time; hs[i] = h.v.hash; sp[i] = (uint8_t)h.status;
+    }
+    z.patch.need(blk.size(), st);
+    RM_HIP(hipMemcpy(z.patch.p, blk.data(), blk.size(), hipMemcpyHostToDevice));
+    const uint8_t* pb = z.patch.as<uint8_t>();
+    const uint32_t* pw = (const uint32_t*)pb;
+    LinePatch lp{pw, pb + Hp * 40, (const float*)(pw + 3 * Hp), (const float*)(pw + 4 * Hp), (const float*)(pw + 5 * Hp),
+                 (const double*)(pb + Hp * 24), pw + Hp, pw + 2 * Hp, (const unsigned long long*)(pb + Hp * 32)};
+    hipLaunchKernelGGL(k_line_patch, dim3(grid(H)), dim3(256), 0, st, H, lp, la);
+    stats();   // again, over the patched statuses
+    if (count[2]) throw std::runtime_error("line reader: a host line was left unread");
+  }
+  z.info[0] = L;
+  z.info[1] = count[0];
+  z.info[2] = count[1];
+  z.info[5] = H;
+  // ---- the kept points, in input order
+  scan(z.flag.as<uint32_t>(), z.pos.as<uint32_t>(), L);
+  RM_HIP(hipEventRecord(z.ev[2], st));
+  const uint64_t P = L - z.info[1] - z.info[2];
+  z.info[3] = P;
+  z.n_points = P;
+  if (P == 0) { RM_HIP(hipStreamSynchronize(st)); z.parsed = true; return; }
+  ensure_points(P, 0, 1);
+  StageBufs& s = sb_;
+  z.p_off.need(P * 4, st); z.p_len.need(P * 4, st);
+  const unsigned long long mask = hash_mask();
+  hipLaunchKernelGGL(k_line_compact, dim3(grid(L)), dim3(256), 0, st, L, la, z.flag.as<uint32_t>(), z.pos.as<uint32_t>(), mask,
+                     s.p_time, s.p_lon, s.p_lat, s.p_acc, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(), s.k0, s.v0);
+  // ---- the time span (the window sort's key base)
+  const uint32_t nb = std::min<uint32_t>(1024u, grid(P));
+  z.part.need(nb * 16ull, st);
+  hipLaunchKernelGGL(k_time_span, dim3(nb), dim3(256), 0, st, P, s.p_time, z.part.as<double>());
+  std::vector<double> part(2ull * nb);
+  RM_HIP(hipMemcpyAsync(part.data(), z.part.p, nb * 16ull, hipMemcpyDeviceToHost, st));
+  // ---- vehicle ids in first-seen order
+  size_t tmp = s.tmp_bytes;
+  int bits = 0;
+  while (bits < 64 && (mask >> bits)) ++bits;
+  RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)P, 0, bits, st));
+  hipLaunchKernelGGL(k_id_flags, dim3(grid(P)), dim3(256), 0, st, P, s.k1, s.v1, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(),
+                     text + kLineFront, s.flag, z.derr.as<uint32_t>() + 1);
+  tmp = s.tmp_bytes;
+  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.flag, s.idx, (int)P, st));
+  // k0 / v0 are free again: the groups' (first point, group) pairs; wstart: each point's group
+  hipLaunchKernelGGL(k_id_groups, dim3(grid(P)), dim3(256), 0, st, P, s.flag, s.idx, s.v1, s.k0, s.v0, s.wstart, z.hctl + 4);
+  RM_HIP(hipMemcpyAsync(z.hctl + 3, z.derr.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipStreamSynchronize(st));
+  z.tmin = part[0];
+  z.tmax = part[1];
+  for (uint32_t b = 1; b < nb; ++b) { z.tmin = std::min(z.tmin, part[2 * b]); z.tmax = std::max(z.tmax, part[2 * b + 1]); }
+  if (!z.hctl[3]) {
+    const uint32_t G = z.hctl[4];
+    z.v_off.need(G * 4ull, st); z.v_len.need(G * 4ull, st);
+    tmp = s.tmp_bytes;
+    RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)G, 0, 32, st));
+    hipLaunchKernelGGL(k_id_rank, dim3(grid(G)), dim3(256), 0, st, G, s.k1, s.v1, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(),
+                       s.wcnt, z.v_off.as<uint32_t>(), z.v_len.as<uint32_t>());
+    hipLaunchKernelGGL(k_id_scatter, dim3(grid(P)), dim3(256), 0, st, P, s.wstart, s.wcnt, s.p_uuid);
+    z.veh_off.resize(G);
+    z.veh_len.resize(G);
+    RM_HIP(hipMemcpyAsync(z.veh_off.data(), z.v_off.p, G * 4ull, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipMemcpyAsync(z.veh_len.data(), z.v_len.p, G * 4ull, hipMemcpyDeviceToHost, st));
+  } else {
+    // two ids share a hash: number them on the host from their bytes (the same numbering)
+    std::vector<uint32_t> off(P), len(P), id(P);
+    RM_HIP(hipMemcpy(off.data(), z.p_off.p, P * 4, hipMemcpyDeviceToHost));
+    RM_HIP(hipMemcpy(len.data(), z.p_len.p, P * 4, hipMemcpyDeviceToHost));
+    std::unordered_map<std::string_view, uint32_t> table;
+    uint32_t c = 0;
+    for (uint64_t k = 0; k < P; ++k) {
+      while (off[k] >= z.chunk_base[c + 1]) ++c;   // points are in input order
+      const std::string_view name(d.data[c] + (off[k] - z.chunk_base[c]), len[k]);
+      const auto it = table.emplace(name, (uint32_t)table.size());
+      if (it.second) { z.veh_off.push_back(off[k]); z.veh_len.push_back(len[k]); }
+      id[k] = it.first->second;
+    }
+    RM_HIP(hipMemcpy(s.p_uuid, id.data(), P * 4, hipMemcpyHostToDevice));
+    z.info[6] = 1;
+  }
+  RM_HIP(hipEventRecord(z.ev[3], st));
+  RM_HIP(hipStreamSynchronize(st));
+  z.info[4] = z.veh_off.size();
+  z.parsed = true;
+}
+
+void Matcher::run_lines(const LinesDesc& d, const RunParams& rp) {
+  if (d.n_opts == 0 || !d.opts) throw std::runtime_error("line batch needs at least one option set");
+  scan_options(d.opts, 1);   // every window takes opts[0]
+  parse_lines(d);
+  LineState& z = *ls_;
+  from_points_ = true;
+  const uint64_t n = z.n_points;
+  if (n == 0) { n_traces_ = 0; n_points_ = 0; n_trans_ = 0; n_path_ = 0; seg_used_ = 0; return; }
+  const double tbase = std::floor(z.tmin);
+  if (std::floor(z.tmax) - tbase >= 4294967295.0) throw std::runtime_error("point times span more than 2^32 s");
+  run_points_device(n, tbase, d.inactivity, d.opts, 1, 0, rp, z.ev[4]);
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, z.ev[3], z.ev[4]) == hipSuccess) z.ms[3] = ms;
+}
+
+void Matcher::lines_info(uint64_t out[7]) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  std::copy(ls_->info, ls_->info + 7, out);
+}
+
+void Matcher::lines_time(double ms[4]) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  LineState& z = *ls_;
+  for (int k = 0; k < 3; ++k) {
+    float t = 0.f;
+    if (z.n_points && hipEventElapsedTime(&t, z.ev[k], z.ev[k + 1]) == hipSuccess) z.ms[k] = t;
+  }
+  std::copy(z.ms, z.ms + 4, ms);
+}
+
+void Matcher::get_line_points(uint32_t* uuid, double* time, float* lon, float* lat, float* acc) {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  const uint64_t P = ls_->n_points;
+  if (!P) return;
+  RM_HIP(hipSetDevice(eng_->device()));
+  RM_HIP(hipStreamSynchronize(stream_));
+  const StageBufs& s = sb_;
+  RM_HIP(hipMemcpy(uuid, s.p_uuid, P * 4, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(time, s.p_time, P * 8, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(lon, s.p_lon, P * 4, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(lat, s.p_lat, P * 4, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(acc, s.p_acc, P * 4, hipMemcpyDeviceToHost));
+}
+
+void Matcher::get_vehicles(uint32_t* chunk, uint64_t* off, uint32_t* len) {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  const LineState& z = *ls_;
+  for (size_t v = 0; v < z.veh_off.size(); ++v) {
+    const uint32_t c = z.chunk_of(z.veh_off[v]);
+    chunk[v] = c;
+    off[v] = z.veh_off[v] - z.chunk_base[c];
+    len[v] = z.veh_len[v];
+  }
+}
+
+// The generic rule over the same input, on the host alone (rm_lines_parse_host): every array may be
+// null (a first call sizes them from info[3] points and info[4] vehicles)
+void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
+                      uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len) {
+  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
+  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  std::fill(info, info + 7, 0);
+  std::unordered_map<std::string_view, uint32_t> table;
+  uint64_t P = 0;
+  for (uint32_t c = 0; c < d.n_chunks; ++c) {
+    const uint8_t* b = (const uint8_t*)d.data[c];
+    const uint8_t* const b0 = b;
+    const uint8_t* const e = b + d.len[c];
+    uint64_t line = 0;
+    while (b < e) {
+      const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(e - b));
+      const uint8_t* le = nl ? nl : e;
+      ++line;
+      sv::Line v{};
+      const char* why = nullptr;
+      const uint32_t st = sv::generic_line(b, le, d.fmt, v, &why);
+      if (st == sv::kBad) throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + why);
+      ++info[0];
+      info[1] += st == sv::kBlank;
+      info[2] += st == sv::kOutside;
+      if (st == sv::kPoint) {
+        const uint8_t* id = b + v.id_off;
+        const auto it = table.emplace(std::string_view((const char*)id, v.id_len), (uint32_t)table.size());
+        if (it.second) {
+          const size_t r = table.size() - 1;
+          if (v_chunk) v_chunk[r] = c;
+          if (v_off) v_off[r] = (uint64_t)(id - b0);
+          if (v_len) v_len[r] = v.id_len;
+        }
+        if (uuid) uuid[P] = it.first->second;
+        if (time) time[P] = v.time;
+        if (lon) lon[P] = v.lon;
+        if (lat) lat[P] = v.lat;
+        if (acc) acc[P] = v.acc;
+        ++P;
+      }
+      b = nl ? nl + 1 : e;
+    }
+  }
+  info[3] = P;
+  info[4] = table.size();
+}
+
+}  // namespace rm

@@ -387,10 +387,17 @@ void Matcher::run_points(const PointsDesc& pd, const RunParams& rp) {
     RM_HIP(hipMemcpy(s.p_acc, neg.data(), n * 4, hipMemcpyHostToDevice));
   }
   if (pd.uuid_opt) RM_HIP(hipMemcpyAsync(s.p_uopt, pd.uuid_opt, pd.n_uuids * 4ull, hipMemcpyHostToDevice, st));
+  run_points_device(n, tbase, pd.inactivity, pd.opts, pd.n_opts, pd.uuid_opt ? pd.n_uuids : 0u, rp);
+}
+
+void Matcher::run_points_device(uint64_t n, double tbase, double inactivity, const MatchOptions* opts, uint32_t n_opts,
+                                uint32_t n_uopt, const RunParams& rp, hipEvent_t windows_done) {
+  StageBufs& s = sb_;
+  hipStream_t st = stream_;
   hipLaunchKernelGGL(k_pt_keys, dim3(grid(n)), dim3(256), 0, st, n, s.p_uuid, s.p_time, tbase, s.k0, s.v0);
   size_t tmp = s.tmp_bytes;
   RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)n, 0, 64, st));
-  hipLaunchKernelGGL(k_win_flags, dim3(grid(n)), dim3(256), 0, st, n, s.k1, s.v1, s.p_time, pd.inactivity, s.flag);
+  hipLaunchKernelGGL(k_win_flags, dim3(grid(n)), dim3(256), 0, st, n, s.k1, s.v1, s.p_time, inactivity, s.flag);
   tmp = s.tmp_bytes;
   RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.flag, s.idx, (int)n, st));
   hipLaunchKernelGGL(k_win_starts, dim3(grid(n)), dim3(256), 0, st, n, s.flag, s.idx, s.wstart, s.hctl);
@@ -411,15 +418,16 @@ void Matcher::run_points(const PointsDesc& pd, const RunParams& rp) {
   n_traces_ = T;
   n_points_ = P;
   if (T == 0) { n_trans_ = 0; n_path_ = 0; seg_used_ = 0; has_report_ = false; return; }
-  ensure(P, T, pd.n_opts);
+  ensure(P, T, n_opts);
   use_ws_inputs();
   Workspace& w = ws_;
-  RM_HIP(hipMemcpyAsync(w.opts, pd.opts, pd.n_opts * sizeof(MatchOptions), hipMemcpyHostToDevice, st));
+  RM_HIP(hipMemcpyAsync(w.opts, opts, n_opts * sizeof(MatchOptions), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_win_gather, dim3(grid(n)), dim3(256), 0, st, n, s.k1, s.v1, s.idx, s.flag, s.wstart, s.wflag, s.wofs,
-                     s.widx, s.p_time, s.p_lon, s.p_lat, s.p_acc, s.p_uopt, pd.uuid_opt ? pd.n_uuids : 0u, w.time,
+                     s.widx, s.p_time, s.p_lon, s.p_lat, s.p_acc, s.p_uopt, n_uopt, w.time,
                      w.lon, w.lat, w.acc, w.trace_off, w.trace_opt, s.trace_uuid);
   const uint32_t Pu = (uint32_t)P;
   RM_HIP(hipMemcpyAsync(w.trace_off + T, &Pu, 4, hipMemcpyHostToDevice, st));
+  if (windows_done) RM_HIP(hipEventRecord(windows_done, st));
   RM_HIP(hipStreamSynchronize(st));
   run_device(rp);
 }

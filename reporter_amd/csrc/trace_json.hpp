@@ -108,6 +108,13 @@ class Reader {
     throw std::runtime_error(err);
   }
 
+  // the correctly rounded double of one number token in JSON's grammar (s[n] is a NUL), by the
+  // conversion every request number takes; the separated-value reader (sv_lines.hpp) shares it
+  static double number_value(const char* s, size_t n) {
+    Reader r(s, n, nullptr);
+    return r.number();
+  }
+
  private:
   static constexpr int kNumOpt = 9;
   static constexpr const char* kOptNames[kNumOpt] = {"sigma_z", "beta", "search_radius", "gps_accuracy",

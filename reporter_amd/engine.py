@@ -148,6 +148,112 @@ def _c(a, dt):
     return np.ascontiguousarray(a, dtype=dt)
 
 
+LINES_INFO = ("lines", "blank", "outside", "points", "vehicles", "host_lines", "ids_on_host")
+DATE_PATTERN = "yyyy-MM-dd HH:mm:ss"
+
+
+class LineFormat:
+    """Layout of separated-value trace lines (rm_line_format).  The default is the trace files'
+    ``uuid,time,lat,lon,accuracy`` (reference py/simple_reporter.py:113)."""
+
+    def __init__(self, sep=b",", uuid_col=0, time_col=1, lat_col=2, lon_col=3, acc_col=4, time_format=0, accuracy_cap=0,
+                 bbox=None):
+        sep = sep.encode() if isinstance(sep, str) else bytes(sep)
+        if len(sep) != 1:
+            raise ValueError("the separator must be one byte")
+        if bbox is not None and len(bbox) != 4:
+            raise ValueError("bbox is min_lat, min_lon, max_lat, max_lon")
+        self.sep, self.uuid_col, self.time_col, self.lat_col, self.lon_col = sep, int(uuid_col), int(time_col), int(lat_col), int(lon_col)
+        self.acc_col, self.time_format, self.accuracy_cap = int(acc_col), int(time_format), int(accuracy_cap)
+        self.bbox = None if bbox is None else tuple(float(x) for x in bbox)
+
+    @classmethod
+    def from_spec(cls, spec, **kw):
+        """A formatter string of the reference (Formatter.java:36-51), e.g.
+        ``,sv,\\|,1,9,10,0,5,yyyy-MM-dd HH:mm:ss``: the first character splits the rest into type,
+        separator (one byte, optionally backslash-escaped), the uuid, lat, lon, time and accuracy
+        columns, and an optional date pattern (only yyyy-MM-dd HH:mm:ss)."""
+        if len(spec) < 2:
+            raise ValueError("empty formatter spec")
+        args = spec[1:].split(spec[0])
+        if args[0] == "json":
+            raise ValueError("json formatters are not read here (separated values only)")
+        if args[0] != "sv":
+            raise ValueError("unsupported raw format parser: %r" % args[0])
+        if len(args) < 7:
+            raise ValueError("sv formatter needs separator, uuid, lat, lon, time and accuracy columns")
+        sep = args[1][1:] if len(args[1]) == 2 and args[1][0] == "\\" else args[1]
+        if len(sep.encode()) != 1:
+            raise ValueError("the separator must be one byte")
+        try:
+            uuid, lat, lon, tm, acc = (int(a) for a in args[2:7])
+        except ValueError:
+            raise ValueError("sv formatter columns must be integers")
+        pattern = args[7] if len(args) > 7 else None
+        if pattern not in (None, DATE_PATTERN):
+            raise ValueError("only the date pattern %r is read" % DATE_PATTERN)
+        return cls(sep, uuid, tm, lat, lon, acc, 1 if pattern else 0, **kw)
+
+    def _c(self):
+        f = _lib.RmLineFormat()
+        _lib.lib().rm_default_line_format(C.byref(f))
+        f.sep = self.sep[0]
+        f.uuid_col, f.time_col, f.lat_col, f.lon_col, f.acc_col = self.uuid_col, self.time_col, self.lat_col, self.lon_col, self.acc_col
+        f.time_format, f.accuracy_cap = self.time_format, self.accuracy_cap
+        f.use_bbox = 0 if self.bbox is None else 1
+        for k in range(4):
+            f.bbox[k] = 0.0 if self.bbox is None else self.bbox[k]
+        return f
+
+
+def _chunk_views(chunks):
+    """uint8 views of the chunks (no copy of bytes, memoryview or mmap objects)."""
+    out = []
+    for ch in chunks:
+        a = _c(ch, np.uint8).reshape(-1) if isinstance(ch, np.ndarray) else np.frombuffer(ch, np.uint8)
+        out.append(a)
+    return out
+
+
+def _lines_desc(chunks, fmt, inactivity, opts):
+    views = _chunk_views(chunks)
+    n = len(views)
+    data = (C.c_void_p * max(n, 1))(*[v.ctypes.data if len(v) else None for v in views])
+    lens = (C.c_uint64 * max(n, 1))(*[len(v) for v in views])
+    opts = default_options(1) if opts is None else _c(opts, OPTIONS_DTYPE)
+    d = _lib.RmLinesDesc(n, C.cast(data, C.c_void_p), C.cast(lens, C.c_void_p), (fmt or LineFormat())._c(),
+                         float(inactivity), len(opts), opts.ctypes.data)
+    return d, (views, data, lens, opts)
+
+
+def _names(chunks, chunk, off, ln):
+    views = _chunk_views(chunks)
+    return [views[int(c)][int(o):int(o) + int(n)].tobytes().decode("utf-8", "replace") for c, o, n in zip(chunk, off, ln)]
+
+
+def parse_lines_host(chunks, fmt=None):
+    """The generic line rule over `chunks` on the host (no GPU): dict(uuid, time, lon, lat,
+    accuracy, names, info), the points in input order and the vehicles in first-seen order."""
+    d, keep = _lines_desc(chunks, fmt, 120.0, None)
+    info = (C.c_uint64 * 7)()
+    err = C.create_string_buffer(512)
+    L = _lib.lib()
+    if L.rm_lines_parse_host(C.byref(d), info, None, None, None, None, None, None, None, None, err, 512) != 0:
+        raise _lib.RmError(err.value.decode("utf-8", "replace"))
+    n, nv = int(info[3]), int(info[4])
+    uuid = np.empty(n, np.uint32)
+    time = np.empty(n, np.float64)
+    lon, lat, acc = (np.empty(n, np.float32) for _ in range(3))
+    chunk = np.empty(nv, np.uint32)
+    off = np.empty(nv, np.uint64)
+    ln = np.empty(nv, np.uint32)
+    if L.rm_lines_parse_host(C.byref(d), info, uuid.ctypes.data, time.ctypes.data, lon.ctypes.data, lat.ctypes.data,
+                             acc.ctypes.data, chunk.ctypes.data, off.ctypes.data, ln.ctypes.data, err, 512) != 0:
+        raise _lib.RmError(err.value.decode("utf-8", "replace"))
+    return dict(uuid=uuid, time=time, lon=lon, lat=lat, accuracy=acc, names=_names(chunks, chunk, off, ln),
+                info=dict(zip(LINES_INFO, (int(x) for x in info))))
+
+
 class BatchMatcher:
     """One HIP stream + device workspace; runs whole batches of traces."""
 
@@ -226,6 +332,55 @@ class BatchMatcher:
         rp = self.run_params(**rp_kw)
         _lib.check(_lib.lib().rm_runner_run_points(self._h, C.byref(d), C.byref(rp)))
         return self
+
+    def run_lines(self, chunks, fmt=None, inactivity=120.0, opts=None, **rp_kw):
+        """Trace-file text (one chunk per file: bytes, memoryview, mmap or uint8 arrays) -> lines
+        parsed, vehicle ids numbered in first-seen order, inactivity windows and every matching
+        stage, all on the device (DESIGN.md rule 11).  Every window takes opts[0].  A malformed
+        line raises RuntimeError "chunk <c> line <l>: <reason>"."""
+        d, keep = _lines_desc(chunks, fmt, inactivity, opts)
+        self._keep = keep
+        rp = self.run_params(**rp_kw)
+        _lib.check(_lib.lib().rm_runner_run_lines(self._h, C.byref(d), C.byref(rp)))
+        return self
+
+    def parse_lines(self, chunks, fmt=None):
+        """The parse and id stages of run_lines alone; returns the kept points in input order:
+        dict(uuid, time, lon, lat, accuracy)."""
+        d, keep = _lines_desc(chunks, fmt, 120.0, None)
+        self._keep = keep
+        _lib.check(_lib.lib().rm_runner_parse_lines(self._h, C.byref(d)))
+        return self.line_points()
+
+    def line_points(self):
+        """The points of the last run_lines / parse_lines, in input order."""
+        n = self.lines_info()["points"]
+        uuid = np.empty(n, np.uint32)
+        time = np.empty(n, np.float64)
+        lon, lat, acc = (np.empty(n, np.float32) for _ in range(3))
+        _lib.check(_lib.lib().rm_runner_get_line_points(self._h, uuid.ctypes.data, time.ctypes.data, lon.ctypes.data,
+                                                        lat.ctypes.data, acc.ctypes.data))
+        return dict(uuid=uuid, time=time, lon=lon, lat=lat, accuracy=acc)
+
+    def lines_info(self):
+        out = (C.c_uint64 * 7)()
+        _lib.check(_lib.lib().rm_runner_lines_info(self._h, out))
+        return dict(zip(LINES_INFO, (int(x) for x in out)))
+
+    def vehicle_names(self, chunks):
+        """Vehicle id strings of the last run_lines / parse_lines over `chunks`, by vehicle index."""
+        n = self.lines_info()["vehicles"]
+        chunk = np.empty(n, np.uint32)
+        off = np.empty(n, np.uint64)
+        ln = np.empty(n, np.uint32)
+        _lib.check(_lib.lib().rm_runner_get_vehicles(self._h, chunk.ctypes.data, off.ctypes.data, ln.ctypes.data))
+        return _names(chunks, chunk, off, ln)
+
+    def lines_ms(self):
+        """Times (ms) of the last run_lines' parts: upload, parse (+ host lines), ids, windows."""
+        out = (C.c_double * 4)()
+        _lib.check(_lib.lib().rm_runner_lines_time(self._h, out))
+        return dict(zip(("upload", "parse", "ids", "windows"), (float(x) for x in out)))
 
     def trace_uuid(self):
         """Vehicle index of every matched window of the last run_points."""

@@ -456,6 +456,79 @@ void rm_default_tile_params(rm_tile_params* p);
 /* blob is library-allocated (free with rm_free); comm may be NULL */
 int rm_runner_tiles(rm_runner* r, const rm_tile_params* p, rm_comm* comm, char** blob, size_t* len);
 
+/* ---------------- vehicle sessions (reference BatchingProcessor.java, Batch.java) ----------------
+ * The streaming topology's batcher kept in HBM beside a runner (DESIGN.md §3 rule 12): per vehicle
+ * the points in arrival order, the running maximum distance from the first point and the stream
+ * time of the last arrival.  rm_session_push appends a micro-batch of arrivals and, wherever the
+ * reference's rule triggers (>= report_dist_m from the first point, >= report_count points,
+ * >= report_time_s between the first and the last), matches the vehicle's list as one trace on the
+ * runner, runs report() over it, trims the list to shape_used (clears it when the reply has none,
+ * or when the match failed) and searches on; rm_session_punctuate evicts the vehicles whose last
+ * arrival is more than session_gap_ms old, reporting what they hold with thresholds (0, 2, 0).
+ * The forwarded reports of a call (Segment.valid(), Segment.java:38-40) come back ordered by the
+ * arrival that triggered them, so the same arrivals cut into pushes of any sizes give the same
+ * concatenated output.  The runner's batch is replaced by each round's windows; one runner serves
+ * one session at a time (the session keeps what it needs of the runner alive, so either may be
+ * destroyed first).  run.do_report is forced on and run.zero_hist off: hist_dev / dur_dev
+ * accumulate over the calls. */
+typedef struct rm_session rm_session;
+typedef struct {
+  double report_dist_m;          /* 500 (BatchingProcessor.java:28) */
+  uint32_t report_count;         /* 10  (:27) */
+  uint32_t max_vehicle_points;   /* 0: unbounded, as the reference; above 0, a list that reaches it on an
+                                    arrival that does not trigger is cleared (a window record with err
+                                    0x80000000 and no match) */
+  double report_time_s;          /* 60  (:26) */
+  int64_t session_gap_ms;        /* 60000 (:29) */
+  rm_options opt;                /* one option set for every vehicle (Batch.java:58-60) */
+  rm_run_params run;             /* threshold, level masks, hist_dev / dur_dev */
+} rm_session_params;
+void rm_default_session_params(rm_session_params* p);
+typedef struct {
+  uint64_t n;
+  const uint32_t* vehicle;       /* dense vehicle index per arrival (< n_vehicles) */
+  const double* time;            /* epoch seconds */
+  const float* lon;
+  const float* lat;
+  const float* accuracy;         /* may be NULL: absent (-1) */
+  const int64_t* stamp_ms;       /* stream time of each arrival (context.timestamp()) */
+} rm_session_points;
+typedef struct {                 /* rm::ReportRec and where it came from */
+  uint64_t id, next_id;
+  double t0, t1;
+  int32_t length, queue_length;
+  uint32_t seg_dense, pad;
+  uint32_t vehicle, window;      /* window: index into the same call's rm_session_get_windows */
+} rm_session_report;
+typedef struct {
+  uint32_t vehicle;
+  uint32_t arrival;              /* index in the push of the arrival that triggered (punctuate: the vehicle) */
+  uint32_t n_points;
+  int32_t shape_used;            /* -1 when absent */
+  uint32_t n_reports;            /* before the forwarding filter */
+  uint32_t err;                  /* the window's error bits (rm_runner_trace_errors); 0x80000000: cleared at
+                                    max_vehicle_points */
+} rm_session_window;
+rm_session* rm_session_create(rm_runner* r, uint32_t n_vehicles, const rm_session_params* p);   /* NULL on error */
+void rm_session_destroy(rm_session* s);
+/* out: [0] arrivals evaluated (those that found a list to join) [1] triggers [2] trims (shape_used
+ * present) [3] lists cleared by an absent shape_used [4] failed windows [5] forwarded reports
+ * [6] invalid reports [7] match rounds.  A vehicle index out of range or a NaN time fails the call
+ * and leaves the session as it was. */
+int rm_session_push(rm_session* s, const rm_session_points* pts, uint64_t out[8]);
+int rm_session_punctuate(rm_session* s, int64_t timestamp_ms, uint64_t out[8]);
+/* The last call's forwarded reports / window records, ordered by triggering arrival (reports in
+ * report() order inside a window).  *n receives the count; out may be NULL (count only). */
+int rm_session_get_reports(rm_session* s, rm_session_report* out, uint64_t* n);
+int rm_session_get_windows(rm_session* s, rm_session_window* out, uint64_t* n);
+/* The store: per vehicle cnt, max_sep, last_update (n_vehicles each; the latter two are 0 for an
+ * empty vehicle) and the kept points packed in vehicle order (*n_points of them).  Any array may
+ * be NULL. */
+int rm_session_get_store(rm_session* s, uint32_t* cnt, float* max_sep, int64_t* last_update, float* lon, float* lat,
+                         double* time, float* accuracy, uint64_t* n_points);
+/* device time (ms, HIP events) of the last call: upload, append, trigger, match, trim */
+int rm_session_time(rm_session* s, double ms[5]);
+
 /* ---------------- RCCL over xGMI (multi-GPU histogram exchange) ----------------
  * One process per GPU.  Replaces the reference's keyed Kafka repartition of
  * "id next_id" reports (BatchingProcessor.java:126) with one all-reduce of the

@@ -97,6 +97,16 @@ class RmTileParams(C.Structure):
     _fields_ = [("quantisation", C.c_uint32), ("privacy", C.c_uint32), ("source", C.c_char_p), ("mode", C.c_char_p)]
 
 
+class RmSessionParams(C.Structure):
+    _fields_ = [("report_dist_m", C.c_double), ("report_count", C.c_uint32), ("max_vehicle_points", C.c_uint32),
+                ("report_time_s", C.c_double), ("session_gap_ms", C.c_int64), ("opt", RmOptions), ("run", RmRunParams)]
+
+
+class RmSessionPoints(C.Structure):
+    _fields_ = [("n", C.c_uint64), ("vehicle", C.c_void_p), ("time", C.c_void_p), ("lon", C.c_void_p),
+                ("lat", C.c_void_p), ("accuracy", C.c_void_p), ("stamp_ms", C.c_void_p)]
+
+
 P = C.c_void_p
 U32P = C.POINTER(C.c_uint32)
 
@@ -194,6 +204,15 @@ PROTOTYPES = [
                                       C.c_size_t]),
     ("rm_default_tile_params", None, [C.POINTER(RmTileParams)]),
     ("rm_runner_tiles", C.c_int, [P, C.POINTER(RmTileParams), P, C.POINTER(P), C.POINTER(C.c_size_t)]),
+    ("rm_default_session_params", None, [C.POINTER(RmSessionParams)]),
+    ("rm_session_create", P, [P, C.c_uint32, C.POINTER(RmSessionParams)]),
+    ("rm_session_destroy", None, [P]),
+    ("rm_session_push", C.c_int, [P, C.POINTER(RmSessionPoints), C.POINTER(C.c_uint64)]),
+    ("rm_session_punctuate", C.c_int, [P, C.c_int64, C.POINTER(C.c_uint64)]),
+    ("rm_session_get_reports", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
+    ("rm_session_get_windows", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
+    ("rm_session_get_store", C.c_int, [P, P, P, P, P, P, P, P, C.POINTER(C.c_uint64)]),
+    ("rm_session_time", C.c_int, [P, C.POINTER(C.c_double)]),
     ("rm_comm_unique_id", C.c_int, [P]),
     ("rm_comm_init", P, [C.c_int, C.c_int, P, C.c_int]),
     ("rm_comm_destroy", None, [P]),

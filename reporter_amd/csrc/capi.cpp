@@ -835,7 +835,7 @@ struct rm_engine {
 };
 struct rm_runner {
   std::shared_ptr<Engine> e;
-  std::unique_ptr<Matcher> m;
+  std::shared_ptr<Matcher> m;   // shared with the runner's sessions, which may outlive the handle
 };
 
 extern "C" {
@@ -1831,6 +1831,94 @@ int rm_runner_tiles(rm_runner* r, const rm_tile_params* p, rm_comm* comm, char**
     b[out.size()] = 0;
     *blob = b;
     *len = out.size();
+  });
+}
+
+}  // extern "C"
+
+// ---------------- vehicle sessions (sessions.hip) ----------------
+struct rm_session {   // (destroyed in reverse order: the session, then its matcher, then the engine)
+  std::shared_ptr<Engine> e;
+  std::shared_ptr<Matcher> m;
+  std::unique_ptr<Session> s;
+};
+static_assert(sizeof(rm_session_report) == sizeof(SessionReport), "rm_session_report is rm::SessionReport");
+static_assert(sizeof(rm_session_report) == 56, "rm_session_report layout");
+static_assert(sizeof(rm_session_window) == sizeof(SessionWindow), "rm_session_window is rm::SessionWindow");
+static_assert(sizeof(rm_session_params) == 112 && sizeof(rm_session_points) == 56, "session descriptors' layout");
+
+extern "C" {
+
+void rm_default_session_params(rm_session_params* p) {
+  const SessionParams d;
+  p->report_dist_m = d.report_dist_m; p->report_count = d.report_count; p->max_vehicle_points = d.max_vehicle_points;
+  p->report_time_s = d.report_time_s; p->session_gap_ms = d.session_gap_ms;
+  rm_default_options(&p->opt);
+  rm_default_run_params(&p->run);
+}
+
+rm_session* rm_session_create(rm_runner* r, uint32_t n_vehicles, const rm_session_params* p) {
+  rm_session* out = nullptr;
+  guarded([&] {
+    if (!r) throw std::runtime_error("runner is NULL");
+    SessionParams sp;
+    if (p) {
+      sp.report_dist_m = p->report_dist_m; sp.report_count = p->report_count; sp.max_vehicle_points = p->max_vehicle_points;
+      sp.report_time_s = p->report_time_s; sp.session_gap_ms = p->session_gap_ms;
+      std::memcpy(&sp.opt, &p->opt, sizeof sp.opt);
+      sp.run = to_rp(&p->run);
+    }
+    auto s = std::make_unique<rm_session>();
+    s->e = r->e;
+    s->m = r->m;
+    s->s = std::make_unique<Session>(r->m.get(), n_vehicles, sp);
+    out = s.release();
+  });
+  return out;
+}
+void rm_session_destroy(rm_session* s) { delete s; }
+
+int rm_session_push(rm_session* s, const rm_session_points* pts, uint64_t out[8]) {
+  return guarded([&] {
+    if (!s || !pts) throw std::runtime_error("session or points is NULL");
+    SessionPoints sp;
+    sp.n = pts->n; sp.vehicle = pts->vehicle; sp.time = pts->time; sp.lon = pts->lon; sp.lat = pts->lat;
+    sp.accuracy = pts->accuracy; sp.stamp_ms = pts->stamp_ms;
+    s->s->push(sp, out);
+  });
+}
+int rm_session_punctuate(rm_session* s, int64_t timestamp_ms, uint64_t out[8]) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("session is NULL");
+    s->s->punctuate(timestamp_ms, out);
+  });
+}
+int rm_session_get_reports(rm_session* s, rm_session_report* out, uint64_t* n) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("session is NULL");
+    if (n) *n = s->s->n_reports();
+    if (out) s->s->get_reports(reinterpret_cast<SessionReport*>(out));
+  });
+}
+int rm_session_get_windows(rm_session* s, rm_session_window* out, uint64_t* n) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("session is NULL");
+    if (n) *n = s->s->n_windows();
+    if (out) s->s->get_windows(reinterpret_cast<SessionWindow*>(out));
+  });
+}
+int rm_session_get_store(rm_session* s, uint32_t* cnt, float* max_sep, int64_t* last_update, float* lon, float* lat,
+                         double* time, float* accuracy, uint64_t* n_points) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("session is NULL");
+    const uint64_t n = s->s->get_store(cnt, max_sep, last_update, lon, lat, time, accuracy);
+    if (n_points) *n_points = n;
+  });
+}
+int rm_session_time(rm_session* s, double ms[5]) {
+  return guarded([&] {
+    if (!s || !ms) throw std::runtime_error("session or ms is NULL");
+    s->s->times(ms);
   });
 }
 

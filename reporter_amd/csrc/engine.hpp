@@ -297,6 +297,69 @@ constexpr uint32_t kErrCandOverflow = 1u, kErrSearchOverflow = 2u, kErrPathOverf
 const char* error_text(uint32_t bits);
 
 class Engine;
+class Matcher;
+
+// Vehicle sessions (DESIGN.md §3 rule 12; sessions.hip): the streaming batcher of the reference
+// (BatchingProcessor.java, Batch.java) kept in HBM beside a matcher.  Same layouts as
+// rm_session_params' scalar part, rm_session_report and rm_session_window (reporter_match.h).
+struct SessionParams {
+  double report_dist_m = 500.0;     // BatchingProcessor.java:28
+  uint32_t report_count = 10;       // :27
+  double report_time_s = 60.0;      // :26
+  int64_t session_gap_ms = 60000;   // :29
+  uint32_t max_vehicle_points = 0;  // 0: unbounded (the reference)
+  MatchOptions opt = default_options();
+  RunParams run;
+};
+struct SessionPoints {
+  uint64_t n = 0;
+  const uint32_t* vehicle = nullptr;
+  const double* time = nullptr;
+  const float* lon = nullptr;
+  const float* lat = nullptr;
+  const float* accuracy = nullptr;     // may be null: -1, absent
+  const int64_t* stamp_ms = nullptr;   // stream time of each arrival
+};
+struct SessionReport {
+  ReportRec r;
+  uint32_t vehicle, window;   // window: index into the call's window records
+};
+static_assert(sizeof(SessionReport) == 56, "SessionReport is rm_session_report");
+constexpr uint32_t kSessCapped = 0x80000000u;   // SessionWindow::err: cleared at max_vehicle_points, not matched
+struct SessionWindow {
+  uint32_t vehicle, arrival, n_points;   // arrival: index in the push of the triggering point (punctuate: the vehicle)
+  int32_t shape_used;                    // -1 when absent
+  uint32_t n_reports, err;               // reports before the forwarding filter; the trace's error bits
+};
+static_assert(sizeof(SessionWindow) == 24, "SessionWindow is rm_session_window");
+
+class Session {
+ public:
+  Session(Matcher* m, uint32_t n_vehicles, const SessionParams& sp);
+  ~Session();
+  Session(const Session&) = delete;
+  Session& operator=(const Session&) = delete;
+  // out: arrivals evaluated, triggers, trims, cleared by an absent shape_used, failed windows,
+  // forwarded reports, invalid reports, rounds
+  void push(const SessionPoints& pts, uint64_t out[8]);
+  void punctuate(int64_t timestamp_ms, uint64_t out[8]);
+  uint64_t n_reports() const;   // of the last call
+  uint64_t n_windows() const;
+  void get_reports(SessionReport* out);
+  void get_windows(SessionWindow* out);
+  // the store packed by vehicle: cnt, max_sep, last_update (n_vehicles each) and the kept points
+  // (sum of cnt; null arrays are not written); returns the point count
+  uint64_t get_store(uint32_t* cnt, float* max_sep, int64_t* last_update, float* lon, float* lat, double* time, float* acc);
+  void times(double ms[5]) const;   // upload, append, trigger, match, trim of the last call
+  uint32_t n_vehicles() const;
+
+ private:
+  struct Impl;
+  Impl* p_;
+  void match_round(uint32_t T, uint64_t P, bool evict);
+  void rounds(bool evict, uint64_t out[8]);
+  void finish_call(uint64_t out[8]);
+};
 
 // report() (reference py/reporter_service.py:79-179) on the device over host-supplied segment
 // lists: trace k's segments are segs[seg_off[k] .. seg_off[k+1]); reports come back compacted
@@ -321,6 +384,7 @@ class Matcher {
   ~Matcher();
   Matcher(const Matcher&) = delete;
   Matcher& operator=(const Matcher&) = delete;
+  friend class Session;
 
   // Upload a batch and run every stage on this matcher's stream; returns when the run's control
   // words are back (a large batch also reads its transition and path totals back between the

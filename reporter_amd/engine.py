@@ -589,6 +589,122 @@ class BatchMatcher:
         return {names[i]: (float(ms[i]), int(la[i])) for i in range(n)}
 
 
+SESSION_REPORT_DTYPE = np.dtype(REPORT_DTYPE.descr + [("vehicle", "<u4"), ("window", "<u4")])
+assert SESSION_REPORT_DTYPE.itemsize == 56
+
+SESSION_WINDOW_DTYPE = np.dtype([
+    ("vehicle", "<u4"), ("arrival", "<u4"), ("n_points", "<u4"), ("shape_used", "<i4"), ("n_reports", "<u4"),
+    ("err", "<u4")])
+assert SESSION_WINDOW_DTYPE.itemsize == 24
+
+SESSION_CAPPED = 0x80000000   # SESSION_WINDOW_DTYPE err: cleared at max_vehicle_points, not matched
+SESSION_COUNTS = ("arrivals", "triggers", "trims", "cleared", "failed", "forwarded", "invalid", "rounds")
+
+
+class VehicleSessions:
+    """The streaming batcher of the reference (BatchingProcessor.java, Batch.java) kept on the GPU
+    beside a BatchMatcher (rm_session_*; DESIGN.md §3 rule 12).  push() takes arrivals as arrays,
+    punctuate() evicts stale vehicles; reports() / windows() give the last call's output ordered by
+    triggering arrival.  The matcher's batch is replaced by each round's windows."""
+
+    def __init__(self, batch_matcher, n_vehicles, report_dist_m=None, report_count=None, report_time_s=None,
+                 session_gap_ms=None, max_vehicle_points=0, opts=None, **rp_kw):
+        self.matcher = batch_matcher
+        self.n_vehicles = int(n_vehicles)
+        p = _lib.RmSessionParams()
+        _lib.lib().rm_default_session_params(C.byref(p))
+        if report_dist_m is not None:
+            p.report_dist_m = float(report_dist_m)
+        if report_count is not None:
+            p.report_count = int(report_count)
+        if report_time_s is not None:
+            p.report_time_s = float(report_time_s)
+        if session_gap_ms is not None:
+            p.session_gap_ms = int(session_gap_ms)
+        p.max_vehicle_points = int(max_vehicle_points)
+        if opts is not None:
+            o = _c(opts, OPTIONS_DTYPE)
+            if len(o) != 1:
+                raise ValueError("a session takes one option set")
+            for name, _ in _lib.RmOptions._fields_:
+                setattr(p.opt, name, o[name][0].item())
+        p.run = BatchMatcher.run_params(**rp_kw)
+        self._h = _lib.lib().rm_session_create(batch_matcher._h, self.n_vehicles, C.byref(p))
+        if not self._h:
+            raise _lib.RmError(_lib.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().rm_session_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def push(self, vehicle, time, lon, lat, accuracy=None, stamp_ms=0):
+        """Append arrivals (in arrival order) and run every trigger they cause; returns the call's
+        counts (SESSION_COUNTS).  stamp_ms: the stream time of each arrival, or one for all."""
+        vehicle = _c(vehicle, np.uint32)
+        n = len(vehicle)
+        time = _c(time, np.float64)
+        lon = _c(lon, np.float32)
+        lat = _c(lat, np.float32)
+        accuracy = None if accuracy is None else _c(accuracy, np.float32)
+        stamp = _c(np.full(n, stamp_ms, np.int64) if np.ndim(stamp_ms) == 0 else stamp_ms, np.int64)
+        if not (len(time) == len(lon) == len(lat) == len(stamp) == n) or (accuracy is not None and len(accuracy) != n):
+            raise ValueError("arrival arrays must have equal lengths")
+        d = _lib.RmSessionPoints(n, vehicle.ctypes.data, time.ctypes.data, lon.ctypes.data, lat.ctypes.data,
+                                 accuracy.ctypes.data if accuracy is not None else None, stamp.ctypes.data)
+        out = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().rm_session_push(self._h, C.byref(d), out))
+        return dict(zip(SESSION_COUNTS, (int(x) for x in out)))
+
+    def punctuate(self, timestamp_ms):
+        out = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().rm_session_punctuate(self._h, int(timestamp_ms), out))
+        return dict(zip(SESSION_COUNTS, (int(x) for x in out)))
+
+    def reports(self):
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().rm_session_get_reports(self._h, None, C.byref(n)))
+        a = np.empty(max(n.value, 1), SESSION_REPORT_DTYPE)
+        _lib.check(_lib.lib().rm_session_get_reports(self._h, a.ctypes.data, C.byref(n)))
+        return a[: n.value]
+
+    def windows(self):
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().rm_session_get_windows(self._h, None, C.byref(n)))
+        a = np.empty(max(n.value, 1), SESSION_WINDOW_DTYPE)
+        _lib.check(_lib.lib().rm_session_get_windows(self._h, a.ctypes.data, C.byref(n)))
+        return a[: n.value]
+
+    def store(self):
+        """Per vehicle cnt, max_sep, last_update and the kept points packed in vehicle order
+        (vehicle v's are [off[v], off[v + 1]))."""
+        V = self.n_vehicles
+        cnt = np.zeros(V, np.uint32)
+        sep = np.zeros(V, np.float32)
+        upd = np.zeros(V, np.int64)
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().rm_session_get_store(self._h, cnt.ctypes.data, None, None, None, None, None, None, C.byref(n)))
+        m = max(int(n.value), 1)
+        lon, lat, acc = np.zeros(m, np.float32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        time = np.zeros(m, np.float64)
+        _lib.check(_lib.lib().rm_session_get_store(self._h, cnt.ctypes.data, sep.ctypes.data, upd.ctypes.data, lon.ctypes.data,
+                                                   lat.ctypes.data, time.ctypes.data, acc.ctypes.data, C.byref(n)))
+        k = int(n.value)
+        off = np.zeros(V + 1, np.uint64)
+        np.cumsum(cnt, out=off[1:])
+        return {"cnt": cnt, "max_sep": sep, "last_update": upd, "off": off, "lon": lon[:k], "lat": lat[:k],
+                "time": time[:k], "accuracy": acc[:k]}
+
+    def ms(self):
+        """Device ms of the last call: upload, append, trigger, match, trim."""
+        t = (C.c_double * 5)()
+        _lib.check(_lib.lib().rm_session_time(self._h, t))
+        return dict(zip(("upload", "append", "trigger", "match", "trim"), (float(x) for x in t)))
+
+
 def split_by_points(trace_off, parts):
     """Trace index cuts [0, ..., T] of `parts` contiguous ranges with about equal point counts
     (a cut where the running point count crosses k * P / parts); empty ranges are dropped."""

@@ -9,7 +9,8 @@
 //   k_states          one wave per trace: interpolation rule -> state layers
 //   k_loc_*           locality order (large graphs): state slots counted into 64 x 64 Morton regions
 //   k_candidates_lane K1, one lane per state: cell-major 32-byte records, per-road minima in
-//                     registers, top 16 by (sq, road); k_candidates_wave takes the overflow
+//                     registers, top 16 by (sq, road); descriptors built a lane per candidate from
+//                     the wave's LDS stage; k_candidates_wave takes the overflow
 //   k_trans_count     pair constants + counts; k_scan_* lay out routes and K2 items
 //   k_routes_ball2    K2, block-expanded: one lane per transition, two route-ball probes per
 //                     target; search tiers (lane / reg2 / wave LDS / global) for the hand-overs
@@ -479,6 +480,30 @@ __device__ __forceinline__ uint32_t time_ms_dev(uint32_t d_cm, uint32_t dkph) {
   return (uint32_t)((double)(d_cm * 360u) / (double)D);
 }
 
+// How the lane tier writes its descriptors.  1: the wave's candidates are staged in LDS and
+// built a lane per candidate by one rolled body.  0: a lane per state, slots unrolled in groups
+// of four (the form before; kept for A/Bs).  2: diagnostic only, writes cand_n and no
+// descriptors (wrong results: it sizes the epilogue's share of the kernel).
+#ifndef RM_K1_EPILOGUE
+#define RM_K1_EPILOGUE 1
+#endif
+
+// time_ms_dev for a whole wave: the u64 division a road beyond 119 km needs is out of line
+// behind a wave-uniform test, so the body that calls this carries no 64-bit division.  Same bits.
+__device__ __noinline__ uint32_t time_ms_far(uint32_t d_cm, uint32_t dkph) { return time_ms(d_cm, dkph); }
+__device__ __forceinline__ uint32_t time_ms_wave(uint32_t d_cm, uint32_t dkph) {
+#if RM_K1_EPILOGUE == 1
+  const uint32_t D = dkph ? dkph : 1u;
+  uint32_t t = (uint32_t)((double)(d_cm * 360u) / (double)D);
+  if (__ballot(d_cm > 11930464u) != 0ull) {
+    if (d_cm > 11930464u) t = time_ms_far(d_cm, dkph);
+  }
+  return t;
+#else
+  return time_ms_dev(d_cm, dkph);
+#endif
+}
+
 // candidate descriptor of (road, s) for a travel mode: everything the route and path
 // kernels need about a candidate in two dwordx4 (no dependent graph loads there)
 __device__ __forceinline__ void desc_from_rec(const uint4& a, const uint4& c, uint32_t road, uint32_t s, int mode,
@@ -490,7 +515,8 @@ __device__ __forceinline__ void desc_from_rec(const uint4& a, const uint4& c, ui
   if (c.x != kNone && edge_ok(c.z, acc) && spr == 0u) spr = 1u;
   d0 = make_uint4(road, s, a.z, spf | (spr << 16));
   // d1 = {node0, node1, time_ms(s) entering forward from node0, time_ms(L - s) entering reverse from node1}
-  d1 = make_uint4(a.x, a.y, spf ? time_ms_dev(s, spf) : 0xffffffffu, spr ? time_ms_dev(a.z - s, spr) : 0xffffffffu);
+  const uint32_t tf = time_ms_wave(s, spf), tr = time_ms_wave(a.z - s, spr);   // (speed 0: unused)
+  d1 = make_uint4(a.x, a.y, spf ? tf : 0xffffffffu, spr ? tr : 0xffffffffu);
 }
 
 __device__ __forceinline__ void make_desc(const DevGraph& g, uint32_t road, uint32_t s, int mode, uint4& d0,
@@ -512,6 +538,12 @@ __device__ __forceinline__ void put_cand(const DevGraph& g, const DevBatch& b, u
 // Unrolled loops over the per-lane slot arrays stop as soon as no active lane needs the
 // slot (a scalar branch on a ballot) instead of always walking all kMaxCand slots.
 #define K1_UNIFORM_STOP(c) (__ballot(c) == 0ull)
+
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // K1 lane tier: one lane per state.  Cell items are read as cell-major 32-byte records
 // (both shape vertices + road + access bits), so a test is two dwordx4 loads with no
@@ -535,14 +567,35 @@ static_assert(kK1Slots % 4 == 0 && kK1Slots <= kMaxCand, "K1 slots");
 #ifndef RM_K1_WPE
 #define RM_K1_WPE 1
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_WPE))) k_candidates_lane(DevGraph g, DevBatch b) {
-  uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (b.perm) {   // locality order: each XCD walks one contiguous range of the sorted states
-    const uint64_t r = (uint64_t)xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
-    if (r >= b.P) return;
-    p = b.perm[r];
-  }
-  if (p >= b.P) return;
+// records of the LDS stage of one wave (16 bytes each); a wave holding more flushes in passes
+#ifndef RM_K1_STAGE
+#define RM_K1_STAGE 384
+#endif
+constexpr int kK1Stage = RM_K1_STAGE;
+static_assert(kK1Stage >= 1, "K1 stage");
+// 1: the cooperative epilogue streams its descriptors out with nontemporal stores (0: plain, for A/Bs)
+#ifndef RM_K1_NT
+#define RM_K1_NT 1
+#endif
+// 1: one walk over the slots per hit item (update or insert) instead of a find walk and an insert
+// walk.  Off: it takes 148 VGPRs, three waves per SIMD, and measured slower
+#ifndef RM_K1_ONESCAN
+#define RM_K1_ONESCAN 0
+#endif
+
+// the state slot of the thread (b.P and above: none)
+__device__ __forceinline__ uint64_t k1_slot(const DevBatch& b) {
+  if (!b.perm) return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // locality order: each XCD walks one contiguous range of the sorted states
+  const uint64_t r = (uint64_t)xcd_block(blockIdx.x, gridDim.x) * blockDim.x + threadIdx.x;
+  return r < b.P ? (uint64_t)b.perm[r] : b.P;
+}
+
+// The per-road minima of state slot p in the lane's registers (n = 0: none, or not a state slot).
+// ovf: more than kK1Slots roads inside the radius (the wave tier's work).
+__device__ __forceinline__ void k1_gather(const DevGraph& g, const DevBatch& b, uint64_t p, uint32_t (&rroad)[kK1Slots],
+                                          uint32_t (&rs)[kK1Slots], unsigned long long (&rbest)[kK1Slots], uint32_t& n,
+                                          bool& ovf) {
   const uint32_t k = b.slot_trace[p];
   const uint32_t o = b.trace_off[k];
   const uint32_t s = (uint32_t)(p - o);
@@ -561,10 +614,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
   const double fx1 = floor(((double)(lon + qlon) - g.lon0) / g.dlon);
   const double fy0 = floor(((double)(lat - qlat) - g.lat0) / g.dlat);
   const double fy1 = floor(((double)(lat + qlat) - g.lat0) / g.dlat);
-  uint32_t rroad[kK1Slots], rs[kK1Slots];
-  unsigned long long rbest[kK1Slots];
-  uint32_t n = 0;
-  bool ovf = false;
   if (!(fx1 < 0 || fy1 < 0 || fx0 > (double)(g.ncx - 1) || fy0 > (double)(g.ncy - 1))) {
     const uint32_t x0 = fx0 < 0 ? 0u : (uint32_t)fx0, y0 = fy0 < 0 ? 0u : (uint32_t)fy0;
     const uint32_t x1 = fx1 > (double)(g.ncx - 1) ? g.ncx - 1 : (uint32_t)fx1;
@@ -616,6 +665,25 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
           const uint32_t road = r1[y].z & 0x1fffffffu;
           const unsigned long long key = ((unsigned long long)__float_as_uint(sq) << 32) | r1[y].w;
           bool found = false;
+#if RM_K1_ONESCAN
+          // slots fill in order, so one walk does both: update the road's slot where it is found
+          // among the first n, else take slot n (every earlier slot has been compared by then)
+#pragma unroll
+          for (int x = 0; x < kK1Slots; ++x) {
+            if (K1_UNIFORM_STOP(x <= (int)n)) break;
+            if (x < (int)n) {
+              if (rroad[x] == road) {
+                found = true;
+                if (key < rbest[x]) { rbest[x] = key; rs[x] = sc; }
+              }
+            } else if (x == (int)n && !found) {
+              rroad[x] = road; rbest[x] = key; rs[x] = sc;
+            }
+          }
+          if (found) continue;
+          if (n >= (uint32_t)kK1Slots) { ovf = true; break; }
+          ++n;
+#else
 #pragma unroll
           for (int x = 0; x < kK1Slots; ++x) {
             if (K1_UNIFORM_STOP(x < (int)n)) break;   // no active lane holds slot x yet
@@ -632,18 +700,110 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
             if (x == (int)n) { rroad[x] = road; rbest[x] = key; rs[x] = sc; }
           }
           ++n;
+#endif
         }
       }
     }
   }
+}
+
+// one staged candidate: {road, s, sq bits, owner lane | rank << 8 | mode << 16}
+struct K1Stage {
+  uint4 rec[4][kK1Stage];
+  uint64_t p[4][kWave];   // the state slot of each lane (the locality order permutes them)
+};
+
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_WPE))) k_candidates_lane(DevGraph g, DevBatch b) {
+  uint32_t rroad[kK1Slots], rs[kK1Slots];
+  unsigned long long rbest[kK1Slots];
+  uint32_t n = 0;
+  bool ovf = false;
+  // no lane leaves early: the wave builds its descriptors together
+  {
+    const uint64_t p = k1_slot(b);
+    if (p < b.P) k1_gather(g, b, p, rroad, rs, rbest, n, ovf);
+  }
+  // (the slot and its mode are read again here: two registers fewer across the item loop)
+  const uint64_t p = k1_slot(b);
+  const bool live = p < b.P && (uint32_t)(p - b.trace_off[b.slot_trace[p]]) < b.n_states[b.slot_trace[p]];
+  const int mode = live ? b.opts[b.trace_opt[b.slot_trace[p]]].mode : 0;
   if (ovf) {
     const uint32_t q = atomicAdd(&b.ctl[kCtlK1LaneToWave], 1u);
     b.rl_cand[q] = (uint32_t)p;
-    return;
+    n = 0;
   }
+#if RM_K1_EPILOGUE == 1
+  // rank by (sq, road): both fit one u64 key (sq >= 0, so its bits order as the value).  Roads
+  // differ between slots, so of a pair exactly one is below the other: one compare ranks both
+  uint32_t rank[kK1Slots];
+#pragma unroll
+  for (int x = 0; x < kK1Slots; ++x) rank[x] = 0;
+#pragma unroll
+  for (int z = 1; z < kK1Slots; ++z) {
+    if (K1_UNIFORM_STOP(z < (int)n)) break;
+    if (z < (int)n) {   // (then every x < z is a slot of the lane too)
+      const unsigned long long kz = ((rbest[z] >> 32) << 32) | rroad[z];
+#pragma unroll
+      for (int x = 0; x < z; ++x) {
+        const bool c = kz < (((rbest[x] >> 32) << 32) | rroad[x]);
+        rank[x] += c ? 1u : 0u;
+        rank[z] += c ? 0u : 1u;
+      }
+    }
+  }
+  // the wave's candidates, owner after owner, staged in its own LDS region and then built a lane
+  // per candidate: 64 busy lanes a round and one copy of the descriptor code
+  __shared__ K1Stage sm;
+  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x >> 6;
+  uint32_t incl = n;
+#pragma unroll
+  for (int d = 1; d < kWave; d <<= 1) {
+    const uint32_t u = __shfl_up(incl, d, kWave);
+    if (lane >= d) incl += u;
+  }
+  const uint32_t tot = (uint32_t)__shfl((int)incl, kWave - 1, kWave);
+  const uint32_t first = incl - n;
+  sm.p[wv][lane] = p;
+  const uint32_t tag = (uint32_t)lane | ((uint32_t)mode << 16);
+  for (uint32_t f0 = 0; f0 < tot; f0 += (uint32_t)kK1Stage) {   // (wave-uniform) flush passes
+#pragma unroll
+    for (int x = 0; x < kK1Slots; ++x) {
+      if (K1_UNIFORM_STOP(x < (int)n)) break;
+      const uint32_t f = first + (uint32_t)x - f0;   // (wraps below the pass: fails the test)
+      if (x < (int)n && f < (uint32_t)kK1Stage)
+        sm.rec[wv][f] = make_uint4(rroad[x], rs[x], (uint32_t)(rbest[x] >> 32), tag | (rank[x] << 8));
+    }
+    wave_sync();
+    const uint32_t cnt = min(tot - f0, (uint32_t)kK1Stage);
+#pragma unroll 1
+    for (uint32_t i = (uint32_t)lane; i < cnt; i += kWave) {
+      const uint4 c = sm.rec[wv][i];
+      const uint4 ra = g.road_rec[2 * (uint64_t)c.x], rc = g.road_rec[2 * (uint64_t)c.x + 1];
+      const int cm = (int)(c.w >> 16);
+      uint4 d0, d1;
+      desc_from_rec(ra, rc, c.x, c.y, cm, mode_access(cm), d0, d1);
+      const uint64_t at = sm.p[wv][c.w & 63u] * kMaxCand + ((c.w >> 8) & 15u);
+#if RM_K1_NT
+      typedef uint32_t K1V4 __attribute__((ext_vector_type(4)));
+      __builtin_nontemporal_store((K1V4){d0.x, d0.y, d0.z, d0.w}, (K1V4*)&b.cand_desc[2 * at]);
+      __builtin_nontemporal_store((K1V4){d1.x, d1.y, d1.z, d1.w}, (K1V4*)&b.cand_desc[2 * at + 1]);
+      __builtin_nontemporal_store(c.z, (uint32_t*)&b.cand_sq[at]);
+#else
+      b.cand_desc[2 * at] = d0;
+      b.cand_desc[2 * at + 1] = d1;
+      b.cand_sq[at] = __uint_as_float(c.z);
+#endif
+    }
+    wave_sync();   // the next pass overwrites the stage
+  }
+  if (live && !ovf) b.cand_n[p] = (uint8_t)n;
+#elif RM_K1_EPILOGUE == 2
+  if (live && !ovf) b.cand_n[p] = (uint8_t)n;
+#else
+  if (!live || ovf) return;
   // rank by (sq, road); descriptors are written four at a time after their road records
   // have all arrived (a store between two loads would serialise them: shared vmcnt)
-  const uint32_t cacc = mode_access(op.mode);
+  const uint32_t cacc = mode_access(mode);
 #pragma unroll
   for (int x0 = 0; x0 < kK1Slots; x0 += 4) {
     if (K1_UNIFORM_STOP(x0 < (int)n)) break;
@@ -670,7 +830,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
         rank += ((((rbest[z] >> 32) << 32) | rroad[z]) < kx) ? 1u : 0u;
       }
       uint4 d0, d1;
-      desc_from_rec(ra[y], rc[y], rroad[x], rs[x], op.mode, cacc, d0, d1);
+      desc_from_rec(ra[y], rc[y], rroad[x], rs[x], mode, cacc, d0, d1);
       const uint64_t at = p * kMaxCand + rank;
       b.cand_desc[2 * at] = d0;
       b.cand_desc[2 * at + 1] = d1;
@@ -678,6 +838,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
     }
   }
   b.cand_n[p] = (uint8_t)n;
+#endif
 }
 
 // wave tier of K1: states whose radius holds more roads than the lane tier keeps
@@ -1377,12 +1538,6 @@ struct SearchTargets {
   uint32_t n;          // how many (<= 64)
   uint32_t delta;      // cm, kNone: every frontier node every round
 };
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // The LDS search runs with W lanes per search: W = 64, one search per wave (a one-wave block:
 // __syncthreads), or W = 16, four searches per wave (each group of 16 lanes on its own LDS

@@ -529,6 +529,37 @@ int rm_session_get_store(rm_session* s, uint32_t* cnt, float* max_sep, int64_t* 
 /* device time (ms, HIP events) of the last call: upload, append, trigger, match, trim */
 int rm_session_time(rm_session* s, double ms[5]);
 
+/* ---------------- tile store (reference AnonymisingProcessor.java, TimeQuantisedTile.java) ----------------
+ * The streaming topology's anonymiser kept in HBM (DESIGN.md §3 rule 13).  rm_tilestore_add is
+ * process(): every segment that passes Segment.valid() adds one row to each time-quantised tile
+ * (trunc(t0) / quantisation .. trunc(t1) / quantisation, id & 0x1FFFFFF) it touches, in arrival
+ * order; rm_tilestore_add_session takes a session's forwarded reports straight from its device
+ * buffer.  rm_tilestore_flush is punctuate(): every tile sorted stably by (id, next_id) as
+ * integers, culled by clean() with the privacy count, and written as the CSV body the datastore
+ * ingests -- sort, cull and text on the GPU -- after which the store is empty.  The blob holds
+ * "name\0body\0" per file, files ordered by (time range start, tile id); name is
+ * "<start>_<start + quantisation - 1>/<level>/<tile index>", body the column header and one
+ * "\n"-led row per segment (no trailing newline).  The random file name under the tile directory
+ * and the sinks stay with the caller.  A store has its own stream and serves one calling thread at
+ * a time; it may be fed from any number of sessions on its device, one call after another.
+ * Stated limits: an id or next_id above 2^63 - 1, a non-finite time or t1 >= 2^53, or a segment
+ * spanning more than 65,536 buckets fails the add call and leaves the store as it was; a source
+ * longer than 64 bytes, a mode longer than 16, or either with ',' or a newline fails creation, as
+ * do quantisation < 60 and privacy < 1 (AnonymisingProcessor.java:73-80). */
+typedef struct rm_tilestore rm_tilestore;
+typedef struct { uint64_t id, next_id; double t0, t1; int32_t length, queue_length; } rm_tile_segment;
+rm_tilestore* rm_tilestore_create(int device, const rm_tile_params* p, uint64_t initial_rows);   /* NULL on error */
+void rm_tilestore_destroy(rm_tilestore* t);
+/* out: [0] segments kept [1] segments skipped as !valid() [2] rows appended [3] rows held */
+int rm_tilestore_add(rm_tilestore* t, const rm_tile_segment* segs, uint64_t n, uint64_t out[4]);
+/* the session's last push / punctuate; a session on another device than the store fails */
+int rm_tilestore_add_session(rm_tilestore* t, rm_session* s, uint64_t out[4]);
+/* blob is library-allocated (free with rm_free).
+ * out: [0] rows in [1] rows kept [2] tiles held [3] files written [4] blob bytes */
+int rm_tilestore_flush(rm_tilestore* t, char** blob, size_t* len, uint64_t out[5]);
+/* device time (ms, HIP events) of the last call: upload, expand, sort, cull, text, download */
+int rm_tilestore_time(rm_tilestore* t, double ms[6]);
+
 /* ---------------- RCCL over xGMI (multi-GPU histogram exchange) ----------------
  * One process per GPU.  Replaces the reference's keyed Kafka repartition of
  * "id next_id" reports (BatchingProcessor.java:126) with one all-reduce of the

@@ -213,6 +213,12 @@ PROTOTYPES = [
     ("rm_session_get_windows", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
     ("rm_session_get_store", C.c_int, [P, P, P, P, P, P, P, P, C.POINTER(C.c_uint64)]),
     ("rm_session_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_tilestore_create", P, [C.c_int, C.POINTER(RmTileParams), C.c_uint64]),
+    ("rm_tilestore_destroy", None, [P]),
+    ("rm_tilestore_add", C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_add_session", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_flush", C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_time", C.c_int, [P, C.POINTER(C.c_double)]),
     ("rm_comm_unique_id", C.c_int, [P]),
     ("rm_comm_init", P, [C.c_int, C.c_int, P, C.c_int]),
     ("rm_comm_destroy", None, [P]),

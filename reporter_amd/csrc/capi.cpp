@@ -1924,6 +1924,64 @@ int rm_session_time(rm_session* s, double ms[5]) {
 
 }  // extern "C"
 
+// ---------------- tile store (tilestore.hip) ----------------
+struct rm_tilestore {
+  std::unique_ptr<TileStore> t;
+};
+static_assert(sizeof(rm_tile_segment) == sizeof(TileSegment), "rm_tile_segment is rm::TileSegment");
+
+extern "C" {
+
+rm_tilestore* rm_tilestore_create(int device, const rm_tile_params* p, uint64_t initial_rows) {
+  rm_tilestore* out = nullptr;
+  guarded([&] {
+    if (!p) throw std::runtime_error("tile params is NULL");
+    TileParams tp;
+    tp.quantisation = p->quantisation;
+    tp.privacy = p->privacy;
+    tp.source = p->source ? p->source : "";
+    std::string mode = p->mode ? p->mode : "auto";
+    for (char& ch : mode) ch = (char)std::toupper((unsigned char)ch);   // AnonymisingProcessor.java:81
+    tp.mode = mode;
+    auto t = std::make_unique<rm_tilestore>();
+    t->t = std::make_unique<TileStore>(device, tp, initial_rows);
+    out = t.release();
+  });
+  return out;
+}
+void rm_tilestore_destroy(rm_tilestore* t) { delete t; }
+
+int rm_tilestore_add(rm_tilestore* t, const rm_tile_segment* segs, uint64_t n, uint64_t out[4]) {
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    t->t->add(reinterpret_cast<const TileSegment*>(segs), n, out);
+  });
+}
+int rm_tilestore_add_session(rm_tilestore* t, rm_session* s, uint64_t out[4]) {
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    if (!s) throw std::runtime_error("session is NULL");
+    t->t->add_session(*s->s, out);
+  });
+}
+int rm_tilestore_flush(rm_tilestore* t, char** blob, size_t* len, uint64_t out[5]) {
+  if (!blob || !len) return fail("blob/len is NULL");
+  *blob = nullptr;
+  *len = 0;
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    t->t->flush(blob, len, out);
+  });
+}
+int rm_tilestore_time(rm_tilestore* t, double ms[6]) {
+  return guarded([&] {
+    if (!t || !ms) throw std::runtime_error("tile store or ms is NULL");
+    t->t->times(ms);
+  });
+}
+
+}  // extern "C"
+
 namespace {
 }  // namespace
 

@@ -352,6 +352,10 @@ class Session {
   uint64_t get_store(uint32_t* cnt, float* max_sep, int64_t* last_update, float* lon, float* lat, double* time, float* acc);
   void times(double ms[5]) const;   // upload, append, trigger, match, trim of the last call
   uint32_t n_vehicles() const;
+  // for a TileStore fed device-to-device: the session's GPU and the last call's forwarded
+  // reports in HBM (n_reports() of them, complete when the call has returned)
+  int device() const;
+  const SessionReport* reports_device() const;
 
  private:
   struct Impl;
@@ -359,6 +363,39 @@ class Session {
   void match_round(uint32_t T, uint64_t P, bool evict);
   void rounds(bool evict, uint64_t out[8]);
   void finish_call(uint64_t out[8]);
+};
+
+// The tile store (DESIGN.md §3 rule 13; tilestore.hip): the reference's streaming anonymiser
+// (AnonymisingProcessor.java, TimeQuantisedTile.java, Segment.java:38-74) kept and flushed in HBM.
+// TileSegment has the layout of rm_tile_segment (reporter_match.h) and of ReportRec's first 40 bytes.
+struct TileSegment {
+  uint64_t id, next_id;
+  double t0, t1;
+  int32_t length, queue_length;
+};
+static_assert(sizeof(TileSegment) == 40, "TileSegment is rm_tile_segment");
+class TileStore {
+ public:
+  // tp.mode as printed (upper-cased by the caller); initial_rows: the first capacity (it doubles)
+  TileStore(int device, const TileParams& tp, uint64_t initial_rows);
+  ~TileStore();
+  TileStore(const TileStore&) = delete;
+  TileStore& operator=(const TileStore&) = delete;
+  // out: segments kept, segments skipped as !valid(), rows appended, rows held.  A segment
+  // outside rule 13's stated limits fails the call and leaves the store as it was.
+  void add(const TileSegment* segs, uint64_t n, uint64_t out[4]);
+  void add_session(Session& s, uint64_t out[4]);   // the session's last push / punctuate
+  // punctuate: *blob is malloc'd ("name\0body\0" per file, files by (start, tile id)); out: rows
+  // in, rows kept, tiles held, files written, blob bytes.  The store is empty afterwards.
+  void flush(char** blob, size_t* len, uint64_t out[5]);
+  void times(double ms[6]) const;   // upload, expand, sort, cull, text, download of the last call
+  int device() const;
+  uint64_t rows_held() const;
+  uint64_t capacity() const;
+
+ private:
+  struct Impl;
+  Impl* p_;
 };
 
 // report() (reference py/reporter_service.py:79-179) on the device over host-supplied segment

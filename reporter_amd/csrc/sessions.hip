@@ -594,6 +594,8 @@ Session::~Session() {
 }
 
 uint32_t Session::n_vehicles() const { return p_->nV; }
+int Session::device() const { return p_->m->eng_->device(); }
+const SessionReport* Session::reports_device() const { return p_->rep_s; }
 uint64_t Session::n_reports() const { return p_->n_rep; }
 uint64_t Session::n_windows() const { return p_->n_win; }
 void Session::times(double ms[5]) const { for (int i = 0; i < 5; ++i) ms[i] = p_->ms[i]; }

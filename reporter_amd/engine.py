@@ -705,6 +705,75 @@ class VehicleSessions:
         return dict(zip(("upload", "append", "trigger", "match", "trim"), (float(x) for x in t)))
 
 
+TILE_SEGMENT_DTYPE = np.dtype([
+    ("id", "<u8"), ("next_id", "<u8"), ("t0", "<f8"), ("t1", "<f8"), ("length", "<i4"), ("queue_length", "<i4")])
+assert TILE_SEGMENT_DTYPE.itemsize == 40
+TILE_ADD_COUNTS = ("kept", "skipped", "rows", "held")
+TILE_FLUSH_COUNTS = ("rows_in", "rows_kept", "tiles", "files", "bytes")
+
+
+class TileStore:
+    """The streaming anonymiser of the reference (AnonymisingProcessor.java) kept on the GPU
+    (rm_tilestore_*; DESIGN.md §3 rule 13).  add() / add_session() are process(): segment pairs
+    drop into every time-quantised tile they touch; flush() is punctuate(): every tile sorted,
+    culled by the privacy count and written as the datastore's CSV body, all on the device."""
+
+    def __init__(self, device=0, quantisation=3600, privacy=2, source="smpl_rprt", mode="auto", initial_rows=1 << 16):
+        enc = lambda x: x if isinstance(x, bytes) else str(x).encode()
+        tp = _lib.RmTileParams(int(quantisation), int(privacy), enc(source), enc(mode))
+        self._h = _lib.lib().rm_tilestore_create(int(device), C.byref(tp), int(initial_rows))
+        if not self._h:
+            raise _lib.RmError(_lib.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().rm_tilestore_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def add(self, id, next_id, t0, t1, length, queue_length):
+        """Segments as arrays, in arrival order; returns the call's counts (TILE_ADD_COUNTS)."""
+        n = len(id)
+        cols = (_c(id, np.uint64), _c(next_id, np.uint64), _c(t0, np.float64), _c(t1, np.float64), _c(length, np.int32),
+                _c(queue_length, np.int32))
+        if any(len(x) != n for x in cols):
+            raise ValueError("segment arrays must have equal lengths")
+        a = np.empty(max(n, 1), TILE_SEGMENT_DTYPE)
+        for name, x in zip(TILE_SEGMENT_DTYPE.names, cols):
+            a[name][:n] = x
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rm_tilestore_add(self._h, a.ctypes.data, n, out))
+        return dict(zip(TILE_ADD_COUNTS, (int(x) for x in out)))
+
+    def add_session(self, vehicle_sessions):
+        """The forwarded reports of the session's last push / punctuate, device to device."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rm_tilestore_add_session(self._h, getattr(vehicle_sessions, "_h", None), out))
+        return dict(zip(TILE_ADD_COUNTS, (int(x) for x in out)))
+
+    def flush(self):
+        """(files, counts): an ordered dict name -> body bytes and TILE_FLUSH_COUNTS; empties the store."""
+        blob = C.c_void_p()
+        n = C.c_size_t()
+        out = (C.c_uint64 * 5)()
+        _lib.check(_lib.lib().rm_tilestore_flush(self._h, C.byref(blob), C.byref(n), out))
+        try:
+            raw = C.string_at(blob.value, n.value) if n.value else b""
+        finally:
+            _lib.lib().rm_free(blob)
+        parts = raw.split(b"\0")
+        files = {parts[i].decode(): parts[i + 1] for i in range(0, len(parts) - 1, 2)}
+        return files, dict(zip(TILE_FLUSH_COUNTS, (int(x) for x in out)))
+
+    def ms(self):
+        """Device ms of the last call: upload, expand, sort, cull, text, download."""
+        t = (C.c_double * 6)()
+        _lib.check(_lib.lib().rm_tilestore_time(self._h, t))
+        return dict(zip(("upload", "expand", "sort", "cull", "text", "download"), (float(x) for x in t)))
+
+
 def split_by_points(trace_off, parts):
     """Trace index cuts [0, ..., T] of `parts` contiguous ranges with about equal point counts
     (a cut where the running point count crosses k * P / parts); empty ranges are dropped."""

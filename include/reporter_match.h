@@ -529,6 +529,59 @@ int rm_session_get_store(rm_session* s, uint32_t* cnt, float* max_sep, int64_t* 
 /* device time (ms, HIP events) of the last call: upload, append, trigger, match, trim */
 int rm_session_time(rm_session* s, double ms[5]);
 
+/* ---------------- stream messages (reference KeyedFormattingProcessor.java, Formatter.java) ----------------
+ * The streaming topology's first processor on the device (DESIGN.md §3 rule 14): raw messages, one
+ * per line, become vehicle keys and points and go into a session without leaving HBM.
+ * kind 0: separated values, `line` as rm_runner_parse_lines reads it.  kind 1: one JSON object per
+ * line; of `line` the time_format, accuracy_cap, use_bbox and bbox apply; key[0..4] name the id,
+ * lat, lon, time and accuracy members (NUL-terminated, at most 31 bytes, no '"', '\' or byte below
+ * 0x20, all different; an empty accuracy key: no accuracy, the value is -1).  lat, lon and accuracy
+ * are numbers or strings holding one, the time (format 0) an integer number or string, (format 1)
+ * a 19-byte string, the id a string without an escape or an integer number token. */
+typedef struct { int32_t kind; int32_t pad; rm_line_format line; char key[5][32]; } rm_message_format;
+void rm_default_message_format(rm_message_format* f);   /* kind 0, the default line format, the keys
+                                                           id, latitude, longitude, timestamp, accuracy */
+/* chunks as in rm_lines_desc.  strict 1: the first malformed message in input order fails the call
+ * with "chunk <c> line <l>: <reason>"; 0 (the stream's behaviour, KeyedFormattingProcessor.java:33-41):
+ * it is dropped and counted.  has_stamp 1: every message carries stamp_ms as its stream time; 0: each
+ * carries (int64)(time * 1000) of its own. */
+typedef struct { uint32_t n_chunks; const char* const* data; const uint64_t* len; rm_message_format fmt;
+                 int32_t strict; int32_t has_stamp; int64_t stamp_ms; } rm_messages_desc;
+/* The vehicle directory: id bytes -> a dense index that holds for the whole stream, first-seen
+ * order over the kept points of all calls, kept in HBM.  NULL on error. */
+typedef struct rm_directory rm_directory;
+rm_directory* rm_directory_create(int device, uint32_t max_vehicles);
+void rm_directory_destroy(rm_directory* d);
+int rm_directory_size(rm_directory* d, uint32_t* n);
+/* vehicles [first, first + n): off (n + 1 entries, from 0) into bytes; either may be NULL;
+ * *n_bytes receives the bytes of the range (a first call sizes `bytes`) */
+int rm_directory_names(rm_directory* d, uint32_t first, uint32_t n, uint64_t* off, char* bytes, uint64_t* n_bytes);
+/* Upload the text, read the messages, number the vehicles through the directory and push the
+ * points into the session, all on the session's GPU.  out: as rm_session_push.  info: as
+ * rm_runner_lines_info ([4]: the call's distinct vehicles), then [7] the dropped messages.  The
+ * directory's max_vehicles must not exceed the session's n_vehicles, and both must be on one
+ * device.  A malformed message of a strict call, a call that would pass max_vehicles ("directory
+ * full") and one whose points do not fit the session's store fail before anything is written and
+ * leave the directory and the session as they were.  A failure behind the keying (a HIP error, or
+ * HBM running out while the session appends) leaves the session as rm_session_push does and the
+ * call's new ids in the directory: they keep their indices when the messages are sent again. */
+int rm_session_push_messages(rm_session* s, rm_directory* dir, const rm_messages_desc* d, uint64_t out[8], uint64_t info[8]);
+/* the first (at most 64) dropped messages of the last rm_session_push_messages, in input order:
+ * chunk and line (1-based), and the reasons as NUL-terminated strings laid end to end in `reasons`
+ * (reasons_len bytes; 64 * 64 suffice).  *n receives how many are listed. */
+int rm_session_dropped_messages(rm_session* s, uint32_t* n, uint32_t chunk[64], uint64_t line[64], char* reasons, size_t reasons_len);
+/* host only, no GPU: the generic rule over the same input, vehicles numbered per call; arrays sized
+ * by a first call with NULLs (info[3] points, info[4] vehicles); drop_* as rm_session_dropped_messages */
+int rm_messages_parse_host(const rm_messages_desc* d, uint64_t info[8], uint32_t* uuid, double* time, float* lon, float* lat,
+                           float* acc, uint32_t* chunk, uint64_t* off, uint32_t* len, uint32_t* n_drop, uint32_t drop_chunk[64],
+                           uint64_t drop_line[64], char* reasons, size_t reasons_len, char* err, size_t errlen);
+/* the smallest and the largest time (epoch seconds) among the points the last
+ * rm_session_push_messages kept; *n_points 0: none, t is not written */
+int rm_session_messages_span(rm_session* s, double t[2], uint64_t* n_points);
+/* device time (ms, HIP events) of the last rm_session_push_messages: upload, parse (+ host lines),
+ * ids, directory, then rm_session_time's five */
+int rm_session_messages_time(rm_session* s, double ms[9]);
+
 /* ---------------- tile store (reference AnonymisingProcessor.java, TimeQuantisedTile.java) ----------------
  * The streaming topology's anonymiser kept in HBM (DESIGN.md §3 rule 13).  rm_tilestore_add is
  * process(): every segment that passes Segment.valid() adds one row to each time-quantised tile

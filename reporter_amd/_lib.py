@@ -107,6 +107,15 @@ class RmSessionPoints(C.Structure):
                 ("lat", C.c_void_p), ("accuracy", C.c_void_p), ("stamp_ms", C.c_void_p)]
 
 
+class RmMessageFormat(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("pad", C.c_int32), ("line", RmLineFormat), ("key", (C.c_char * 32) * 5)]
+
+
+class RmMessagesDesc(C.Structure):
+    _fields_ = [("n_chunks", C.c_uint32), ("data", C.c_void_p), ("len", C.c_void_p), ("fmt", RmMessageFormat),
+                ("strict", C.c_int32), ("has_stamp", C.c_int32), ("stamp_ms", C.c_int64)]
+
+
 P = C.c_void_p
 U32P = C.POINTER(C.c_uint32)
 
@@ -213,6 +222,17 @@ PROTOTYPES = [
     ("rm_session_get_windows", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
     ("rm_session_get_store", C.c_int, [P, P, P, P, P, P, P, P, C.POINTER(C.c_uint64)]),
     ("rm_session_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_default_message_format", None, [C.POINTER(RmMessageFormat)]),
+    ("rm_directory_create", P, [C.c_int, C.c_uint32]),
+    ("rm_directory_destroy", None, [P]),
+    ("rm_directory_size", C.c_int, [P, C.POINTER(C.c_uint32)]),
+    ("rm_directory_names", C.c_int, [P, C.c_uint32, C.c_uint32, P, P, C.POINTER(C.c_uint64)]),
+    ("rm_session_push_messages", C.c_int, [P, P, C.POINTER(RmMessagesDesc), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rm_session_dropped_messages", C.c_int, [P, C.POINTER(C.c_uint32), P, P, P, C.c_size_t]),
+    ("rm_messages_parse_host", C.c_int, [C.POINTER(RmMessagesDesc), C.POINTER(C.c_uint64), P, P, P, P, P, P, P, P,
+                                         C.POINTER(C.c_uint32), P, P, P, C.c_size_t, C.c_char_p, C.c_size_t]),
+    ("rm_session_messages_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_session_messages_span", C.c_int, [P, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     ("rm_tilestore_create", P, [C.c_int, C.POINTER(RmTileParams), C.c_uint64]),
     ("rm_tilestore_destroy", None, [P]),
     ("rm_tilestore_add", C.c_int, [P, P, C.c_uint64, C.POINTER(C.c_uint64)]),

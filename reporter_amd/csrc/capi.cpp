@@ -1841,6 +1841,7 @@ struct rm_session {   // (destroyed in reverse order: the session, then its matc
   std::shared_ptr<Engine> e;
   std::shared_ptr<Matcher> m;
   std::unique_ptr<Session> s;
+  double dir_ms = 0.0;   // the directory's device time in the last rm_session_push_messages
 };
 static_assert(sizeof(rm_session_report) == sizeof(SessionReport), "rm_session_report is rm::SessionReport");
 static_assert(sizeof(rm_session_report) == 56, "rm_session_report layout");
@@ -1919,6 +1920,135 @@ int rm_session_time(rm_session* s, double ms[5]) {
   return guarded([&] {
     if (!s || !ms) throw std::runtime_error("session or ms is NULL");
     s->s->times(ms);
+  });
+}
+
+}  // extern "C"
+
+// ---------------- stream messages (lines.hip, directory.hip) ----------------
+struct rm_directory {
+  std::unique_ptr<Directory> d;
+};
+static_assert(sizeof(rm_message_format) == sizeof(msg::Format), "rm_message_format is msg::Format");
+static_assert(sizeof(rm_message_format) == 240 && sizeof(rm_messages_desc) == 280, "message descriptors' layout");
+
+static MessagesDesc to_messages(const rm_messages_desc* d) {
+  if (!d) throw std::runtime_error("messages descriptor is NULL");
+  MessagesDesc md;
+  md.n_chunks = d->n_chunks; md.data = d->data; md.len = d->len;
+  std::memcpy(&md.fmt, &d->fmt, sizeof md.fmt);
+  md.strict = d->strict; md.has_stamp = d->has_stamp; md.stamp_ms = d->stamp_ms;
+  return md;
+}
+// the listed drops into the C arrays; the reasons NUL-terminated, end to end
+static void put_dropped(const std::vector<DroppedMessage>& dr, uint32_t* n, uint32_t* chunk, uint64_t* line, char* reasons,
+                        size_t reasons_len) {
+  size_t at = 0;
+  uint32_t k = 0;
+  for (; k < dr.size() && k < 64u; ++k) {
+    const size_t w = std::strlen(dr[k].why) + 1;
+    if (reasons && at + w > reasons_len) break;
+    if (chunk) chunk[k] = dr[k].chunk;
+    if (line) line[k] = dr[k].line;
+    if (reasons) std::memcpy(reasons + at, dr[k].why, w);
+    at += w;
+  }
+  if (n) *n = k;
+}
+
+extern "C" {
+
+void rm_default_message_format(rm_message_format* f) {
+  const msg::Format d = msg::default_format();
+  std::memcpy(f, &d, sizeof d);
+}
+
+rm_directory* rm_directory_create(int device, uint32_t max_vehicles) {
+  rm_directory* out = nullptr;
+  guarded([&] {
+    auto d = std::make_unique<rm_directory>();
+    d->d = std::make_unique<Directory>(device, max_vehicles);
+    out = d.release();
+  });
+  return out;
+}
+void rm_directory_destroy(rm_directory* d) { delete d; }
+int rm_directory_size(rm_directory* d, uint32_t* n) {
+  return guarded([&] {
+    if (!d || !n) throw std::runtime_error("directory or n is NULL");
+    *n = d->d->size();
+  });
+}
+int rm_directory_names(rm_directory* d, uint32_t first, uint32_t n, uint64_t* off, char* bytes, uint64_t* n_bytes) {
+  return guarded([&] {
+    if (!d) throw std::runtime_error("directory is NULL");
+    const uint64_t b = d->d->names(first, n, off, bytes);
+    if (n_bytes) *n_bytes = b;
+  });
+}
+
+int rm_session_push_messages(rm_session* s, rm_directory* dir, const rm_messages_desc* d, uint64_t out[8], uint64_t info[8]) {
+  return guarded([&] {
+    if (!s || !dir) throw std::runtime_error("session or directory is NULL");
+    if (dir->d->device() != s->s->device()) throw std::runtime_error("the directory is on another device than the session");
+    if (dir->d->max_vehicles() > s->s->n_vehicles())
+      throw std::runtime_error("the directory's max_vehicles exceeds the session's n_vehicles");
+    const MessagesDesc md = to_messages(d);
+    Matcher& m = *s->m;
+    m.parse_messages(md);
+    s->s->check_room(m.line_groups().n_points);   // before the directory is written: a push that cannot fit keys nothing
+    dir->d->assign(m);
+    s->dir_ms = dir->d->last_ms();
+    const LineGroups g = m.line_groups();
+    s->s->push_device(g.n_points, g.p_uuid, g.p_time, g.p_lon, g.p_lat, g.p_acc, nullptr, md.has_stamp != 0, md.stamp_ms, out);
+    if (info) {
+      m.lines_info(info);
+      info[7] = m.dropped_messages(nullptr);
+    }
+  });
+}
+
+int rm_session_dropped_messages(rm_session* s, uint32_t* n, uint32_t chunk[64], uint64_t line[64], char* reasons, size_t reasons_len) {
+  return guarded([&] {
+    if (!s) throw std::runtime_error("session is NULL");
+    std::vector<DroppedMessage> dr;
+    s->m->dropped_messages(&dr);
+    put_dropped(dr, n, chunk, line, reasons, reasons_len);
+  });
+}
+
+int rm_messages_parse_host(const rm_messages_desc* d, uint64_t info[8], uint32_t* uuid, double* time, float* lon, float* lat,
+                           float* acc, uint32_t* chunk, uint64_t* off, uint32_t* len, uint32_t* n_drop, uint32_t drop_chunk[64],
+                           uint64_t drop_line[64], char* reasons, size_t reasons_len, char* err, size_t errlen) {
+  const int rc = guarded([&] {
+    if (!info) throw std::runtime_error("info is NULL");
+    std::vector<DroppedMessage> dr;
+    messages_parse_host(to_messages(d), info, uuid, time, lon, lat, acc, chunk, off, len, &dr);
+    put_dropped(dr, n_drop, drop_chunk, drop_line, reasons, reasons_len);
+  });
+  if (rc && err && errlen) {
+    std::strncpy(err, g_err.c_str(), errlen - 1);
+    err[errlen - 1] = 0;
+  }
+  return rc;
+}
+
+int rm_session_messages_span(rm_session* s, double t[2], uint64_t* n_points) {
+  return guarded([&] {
+    if (!s || !t || !n_points) throw std::runtime_error("session, t or n_points is NULL");
+    uint64_t info[7];
+    s->m->lines_info(info);
+    *n_points = s->m->line_time_span(t) ? info[3] : 0;
+  });
+}
+
+int rm_session_messages_time(rm_session* s, double ms[9]) {
+  return guarded([&] {
+    if (!s || !ms) throw std::runtime_error("session or ms is NULL");
+    double lt[4] = {0, 0, 0, 0};
+    s->m->lines_time(lt);
+    ms[0] = lt[0]; ms[1] = lt[1]; ms[2] = lt[2]; ms[3] = s->dir_ms;
+    s->s->times(ms + 4);
   });
 }
 

@@ -18,6 +18,7 @@
 #include "balls.hpp"
 #include "graph.hpp"
 #include "rm_common.hpp"
+#include "msg_lines.hpp"
 #include "serve_policy.hpp"
 #include "sv_lines.hpp"
 
@@ -251,6 +252,42 @@ struct LineState;   // lines.hip: the device buffers and the last call's results
 void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
                       uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len);
 
+// Raw stream messages for Matcher::parse_messages (lines.hip; DESIGN.md §3 rule 14): chunks as in
+// LinesDesc, one message per line, either kind of msg::Format
+struct MessagesDesc {
+  uint32_t n_chunks = 0;
+  const char* const* data = nullptr;
+  const uint64_t* len = nullptr;
+  msg::Format fmt;
+  int strict = 0;          // 1: the first malformed line fails the call; 0: it is dropped and counted
+  int has_stamp = 0;       // 1: every message carries stamp_ms; 0: (int64)(time * 1000) of its own
+  int64_t stamp_ms = 0;
+};
+struct DroppedMessage {
+  uint32_t chunk;          // both 1-based
+  uint64_t line;
+  const char* why;
+};
+// what the line reader left on the device for the directory and the session: the kept points in
+// input order, numbered per call in first-seen order, and each number's name span in the text
+struct LineGroups {
+  uint64_t n_points = 0;
+  uint32_t n_groups = 0;
+  const uint8_t* text = nullptr;
+  const uint32_t* v_off = nullptr;
+  const uint32_t* v_len = nullptr;
+  uint32_t* p_uuid = nullptr;
+  const double* p_time = nullptr;
+  const float* p_lon = nullptr;
+  const float* p_lat = nullptr;
+  const float* p_acc = nullptr;
+  unsigned long long hash_mask = ~0ull;   // RM_LINES_HASH_BITS
+};
+// the generic rule over the same input on the host alone (no GPU); null arrays are not written;
+// info: Matcher::lines_info's seven and the dropped messages
+void messages_parse_host(const MessagesDesc& d, uint64_t info[8], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
+                         uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len, std::vector<DroppedMessage>* dropped);
+
 // Time-tile stage parameters (simple_reporter.py:176-196, 211-254; CLI defaults :343,345,346)
 struct TileParams {
   uint32_t quantisation = 3600;
@@ -342,7 +379,15 @@ class Session {
   // out: arrivals evaluated, triggers, trims, cleared by an absent shape_used, failed windows,
   // forwarded reports, invalid reports, rounds
   void push(const SessionPoints& pts, uint64_t out[8]);
+  // push() from where its staging ends: n arrivals already in HBM on the session's GPU (d_acc may
+  // be null).  d_stamp null: every arrival carries `stamp` when has_stamp, else (int64)(time * 1000)
+  // of its own.  The arrays are read before the first match round and may lie in the runner's
+  // stage buffers.
+  void push_device(uint64_t n, const uint32_t* d_vehicle, const double* d_time, const float* d_lon, const float* d_lat,
+                   const float* d_acc, const long long* d_stamp, bool has_stamp, int64_t stamp, uint64_t out[8]);
   void punctuate(int64_t timestamp_ms, uint64_t out[8]);
+  // throws what a push of n arrivals would throw for lack of room, before anything is changed
+  void check_room(uint64_t n) const;
   uint64_t n_reports() const;   // of the last call
   uint64_t n_windows() const;
   void get_reports(SessionReport* out);
@@ -363,6 +408,33 @@ class Session {
   void match_round(uint32_t T, uint64_t P, bool evict);
   void rounds(bool evict, uint64_t out[8]);
   void finish_call(uint64_t out[8]);
+  void append(uint64_t n, const uint32_t* d_veh, const double* d_time, const float* d_lon, const float* d_lat, const float* d_acc,
+              const long long* d_stamp, uint64_t out[8]);
+};
+
+// The vehicle directory (DESIGN.md §3 rule 14; directory.hip): the map from id bytes to a dense
+// index that lasts across calls, kept in HBM as an open-addressed table and an arena of names.
+class Directory {
+ public:
+  Directory(int device, uint32_t max_vehicles);
+  ~Directory();
+  Directory(const Directory&) = delete;
+  Directory& operator=(const Directory&) = delete;
+  // Give every kept point of the matcher's last parse its directory index (in g.p_uuid, which
+  // holds the per-call number on entry), new ids numbered in first-seen order behind the known
+  // ones.  Throws "directory full", before anything is written, when they would pass max_vehicles.
+  void assign(Matcher& m);
+  uint32_t size() const;
+  uint32_t max_vehicles() const;
+  int device() const;
+  // vehicles [first, first + n): off (n + 1 entries, from 0) into `bytes`; null arrays are not
+  // written; returns the bytes of the range
+  uint64_t names(uint32_t first, uint32_t n, uint64_t* off, char* bytes);
+  double last_ms() const;   // device time of the last assign
+
+ private:
+  struct Impl;
+  Impl* p_;
 };
 
 // The tile store (DESIGN.md §3 rule 13; tilestore.hip): the reference's streaming anonymiser
@@ -518,6 +590,13 @@ class Matcher {
   // then windows and matches them as run_points does.  Throws "chunk <c> line <l>: <reason>".
   void parse_lines(const LinesDesc& d);
   void run_lines(const LinesDesc& d, const RunParams& rp);
+  // Stream messages -> points on the device (DESIGN.md §3 rule 14): parse_lines with either kind
+  // of message and, when !d.strict, malformed lines dropped and counted instead of thrown
+  void parse_messages(const MessagesDesc& d);
+  uint64_t dropped_messages(std::vector<DroppedMessage>* first) const;   // of the last parse (first: at most 64)
+  LineGroups line_groups() const;                                          // of the last parse
+  bool line_time_span(double t[2]) const;   // smallest and largest time of its kept points (false: none)
+  int device() const;
   // lines, blank, outside the box, points, vehicles, lines read on the host, 1: ids assigned on the host
   void lines_info(uint64_t out[7]) const;
   void get_line_points(uint32_t* uuid, double* time, float* lon, float* lat, float* acc);   // input order
@@ -533,6 +612,7 @@ class Matcher {
   std::string tiles(const TileParams& tp, struct TileComm* comm = nullptr);
 
  private:
+  void parse_text(const MessagesDesc& d);
   void ensure(uint64_t points, uint32_t traces, uint32_t nopts);
   void check_batch(uint32_t T, const uint32_t* trace_off, const MatchOptions* opts, uint32_t n_opts,
                    const uint32_t* trace_opt);

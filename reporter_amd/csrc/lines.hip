@@ -18,6 +18,12 @@
 //               sort of the groups by their first point -> first-seen rank per point (dense_ids'
 //               order); a hash collision sends the numbering to the host (same result)
 // Every output position comes from a scan or a stable sort: no atomics, the same result each call.
+//
+// Stream messages (rule 14) take the same road: parse_messages reads either kind of msg::Format --
+// k_line_parse<1> calls msg::compact_json for JSON lines, the host's generic reader is
+// msg::generic_message -- and a tolerant call drops malformed lines (patched to "bad": no point),
+// counts them and lists the first 64.  The directory (directory.hip) then turns the per-call vehicle
+// numbers left here into indices that hold for the whole stream.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -40,6 +46,7 @@ constexpr uint32_t kLineFront = 16;                               // '\n' bytes 
 constexpr uint32_t kLineLds = kLineFront + kLineWin + sv::kMaxLine;   // a window's bytes in LDS
 constexpr uint64_t kLineTail = kLineWin + kLineLds;               // zero bytes kept behind the text
 constexpr uint32_t kLineRing = 128;                               // line starts listed ahead of a round
+constexpr size_t kMaxDropped = 64;                                // dropped messages a tolerant call lists
 static_assert(kLineLds % 16 == 0, "windows are staged with 16-byte loads");
 
 inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
@@ -81,8 +88,13 @@ struct LineArrays {   // one entry per line
   unsigned long long* hash;
 };
 
+// KIND 0: separated values (rule 11); KIND 1: JSON messages (rule 14), whose five keys arrive by
+// value in `keys` (KIND 0 takes an empty struct there: its code and arguments are what they were)
+struct NoKeys {};
+template <int KIND>
 __global__ void __launch_bounds__(64) k_line_parse(const uint8_t* buf, uint64_t N, const uint32_t* first,
-                                                   const uint32_t* cnt, uint32_t L, sv::Format fmt, LineArrays o,
+                                                   const uint32_t* cnt, uint32_t L, sv::Format fmt,
+                                                   std::conditional_t<KIND == 1, msg::Keys, NoKeys> keys, LineArrays o,
                                                    uint32_t* err) {
   __shared__ uint4 win4[kLineLds / 16];
   __shared__ uint16_t starts[kLineRing];
@@ -101,7 +113,9 @@ __global__ void __launch_bounds__(64) k_line_parse(const uint8_t* buf, uint64_t 
     if (lane < nr && k < L) {   // k < L always, unless the two kernels disagree (err below)
       const uint32_t pos = starts[(head + lane) & (kLineRing - 1)];
       sv::Line ln;
-      const uint32_t st = sv::compact_line(win + kLineFront + pos, fmt, ln);
+      uint32_t st;
+      if constexpr (KIND == 1) st = msg::compact_json(win + kLineFront + pos, fmt, keys, ln);
+      else st = sv::compact_line(win + kLineFront + pos, fmt, ln);
       o.status[k] = (uint8_t)st;
       if (st == sv::kPoint) {
         o.lat[k] = ln.lat;
@@ -299,6 +313,9 @@ struct LineState {
   std::vector<uint64_t> chunk_base;   // n_chunks + 1: where each chunk starts in the text
   std::vector<uint32_t> veh_off, veh_len;
   uint64_t info[7] = {0, 0, 0, 0, 0, 0, 0};
+  uint64_t n_dropped = 0;                 // malformed lines of a tolerant call
+  std::vector<DroppedMessage> dropped;    // the first 64 of them, in input order
+  uint32_t n_groups = 0;                  // v_off / v_len entries on the device
   uint64_t n_points = 0;
   double tmin = 0.0, tmax = 0.0;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -315,12 +332,33 @@ struct LineState {
 };
 
 void Matcher::parse_lines(const LinesDesc& d) {
+  if (ls_) ls_->parsed = false;
+  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
+  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  MessagesDesc md;
+  md.n_chunks = d.n_chunks; md.data = d.data; md.len = d.len;
+  std::memset(&md.fmt, 0, sizeof md.fmt);
+  md.fmt.line = d.fmt;
+  md.strict = 1;
+  parse_text(md);
+}
+
+void Matcher::parse_messages(const MessagesDesc& d) {
+  if (ls_) ls_->parsed = false;
+  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("message chunks are NULL");
+  if (const char* e = msg::format_error(d.fmt); *e) throw std::runtime_error(std::string("message format: ") + e);
+  parse_text(d);
+}
+
+// rule 11 (d.fmt.kind 0) and rule 14 over the chunks: the kept points in StageBufs, numbered per call
+void Matcher::parse_text(const MessagesDesc& d) {
   RM_HIP(hipSetDevice(eng_->device()));
   if (!ls_) ls_ = std::make_shared<LineState>();
   LineState& z = *ls_;
   z.parsed = false;
-  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
-  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  z.n_dropped = 0;
+  z.dropped.clear();
+  z.n_groups = 0;
   hipStream_t st = stream_;
   if (!z.hctl) {
     RM_HIP(hipHostMalloc((void**)&z.hctl, 16 * sizeof(uint32_t), hipHostMallocDefault));
@@ -380,8 +418,13 @@ void Matcher::parse_lines(const LinesDesc& d) {
   z.id_off.need(L * 4, st); z.id_len.need(L * 4, st); z.hash.need(L * 8, st); z.flag.need(L * 4, st); z.pos.need(L * 4, st);
   LineArrays la{z.status.as<uint8_t>(), z.lat.as<float>(), z.lon.as<float>(), z.acc.as<float>(), z.time.as<double>(),
                 z.id_off.as<uint32_t>(), z.id_len.as<uint32_t>(), z.hash.as<unsigned long long>()};
-  hipLaunchKernelGGL(k_line_parse, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
-                     (uint32_t)L, d.fmt, la, z.derr.as<uint32_t>());
+  const msg::Keys keys = msg::make_keys(d.fmt);
+  if (d.fmt.kind == 1)
+    hipLaunchKernelGGL(k_line_parse<1>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
+                       (uint32_t)L, d.fmt.line, keys, la, z.derr.as<uint32_t>());
+  else
+    hipLaunchKernelGGL(k_line_parse<0>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
+                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr.as<uint32_t>());
   RM_HIP(hipGetLastError());
   // ---- "is a point" flags and the counts of the rest
   const uint32_t sb = std::min<uint32_t>(1024u, grid(L));
@@ -424,17 +467,20 @@ void Matcher::parse_lines(const LinesDesc& d) {
         const uint8_t* b = (const uint8_t*)d.data[c] + (at - z.chunk_base[c]);
         const uint8_t* ce = (const uint8_t*)d.data[c] + d.len[c];
         const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(ce - b));
-        h.status = sv::generic_line(b, nl ? nl : ce, d.fmt, h.v, &h.why);
+        h.status = msg::generic_message(b, nl ? nl : ce, d.fmt, h.v, &h.why);
         h.v.id_off += (uint32_t)at;
       }
     });
-    for (const HostLine& h : hl) {   // in input order: the first bad line fails the call
+    for (const HostLine& h : hl) {   // in input order: the first bad line fails a strict call
       if (h.status != sv::kBad) continue;
+      ++z.n_dropped;
+      if (!d.strict && z.dropped.size() >= kMaxDropped) continue;
       const uint64_t at = off[h.line];
       const uint32_t c = z.chunk_of(at);
       const char* b = d.data[c];
       const uint64_t line = 1 + (uint64_t)std::count(b, b + (at - z.chunk_base[c]), '\n');
-      throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + h.why);
+      if (d.strict) throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + h.why);
+      z.dropped.push_back(DroppedMessage{c + 1, line, h.why});   // (its slot is patched to kBad: no point)
     }
     // one block: line, id_off, id_len, lat, lon, acc (u32 / f32), then time, hash, then status
     const uint64_t Hp = (H + 1ull) & ~1ull;
@@ -466,7 +512,7 @@ void Matcher::parse_lines(const LinesDesc& d) {
   // ---- the kept points, in input order
   scan(z.flag.as<uint32_t>(), z.pos.as<uint32_t>(), L);
   RM_HIP(hipEventRecord(z.ev[2], st));
-  const uint64_t P = L - z.info[1] - z.info[2];
+  const uint64_t P = L - z.info[1] - z.info[2] - z.n_dropped;
   z.info[3] = P;
   z.n_points = P;
   if (P == 0) { RM_HIP(hipStreamSynchronize(st)); z.parsed = true; return; }
@@ -526,11 +572,46 @@ void Matcher::parse_lines(const LinesDesc& d) {
     }
     RM_HIP(hipMemcpy(s.p_uuid, id.data(), P * 4, hipMemcpyHostToDevice));
     z.info[6] = 1;
+    // (the name spans on the device too, as the other branch leaves them: the directory reads them)
+    const uint64_t G = z.veh_off.size();
+    z.v_off.need(G * 4ull, st); z.v_len.need(G * 4ull, st);
+    RM_HIP(hipMemcpy(z.v_off.p, z.veh_off.data(), G * 4, hipMemcpyHostToDevice));
+    RM_HIP(hipMemcpy(z.v_len.p, z.veh_len.data(), G * 4, hipMemcpyHostToDevice));
   }
   RM_HIP(hipEventRecord(z.ev[3], st));
   RM_HIP(hipStreamSynchronize(st));
   z.info[4] = z.veh_off.size();
+  z.n_groups = (uint32_t)z.veh_off.size();
   z.parsed = true;
+}
+
+int Matcher::device() const { return eng_->device(); }
+
+bool Matcher::line_time_span(double t[2]) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  if (!ls_->n_points) return false;
+  t[0] = ls_->tmin;
+  t[1] = ls_->tmax;
+  return true;
+}
+
+LineGroups Matcher::line_groups() const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  const LineState& z = *ls_;
+  LineGroups g;
+  g.n_points = z.n_points;
+  g.n_groups = z.n_points ? z.n_groups : 0u;
+  g.text = z.n_points ? z.text.as<uint8_t>() + kLineFront : nullptr;
+  g.v_off = z.v_off.as<uint32_t>(); g.v_len = z.v_len.as<uint32_t>();
+  g.p_uuid = sb_.p_uuid; g.p_time = sb_.p_time; g.p_lon = sb_.p_lon; g.p_lat = sb_.p_lat; g.p_acc = sb_.p_acc;
+  g.hash_mask = hash_mask();
+  return g;
+}
+
+uint64_t Matcher::dropped_messages(std::vector<DroppedMessage>* first) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  if (first) *first = ls_->dropped;
+  return ls_->n_dropped;
 }
 
 void Matcher::run_lines(const LinesDesc& d, const RunParams& rp) {
@@ -613,6 +694,60 @@ void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, doub
       ++info[0];
       info[1] += st == sv::kBlank;
       info[2] += st == sv::kOutside;
+      if (st == sv::kPoint) {
+        const uint8_t* id = b + v.id_off;
+        const auto it = table.emplace(std::string_view((const char*)id, v.id_len), (uint32_t)table.size());
+        if (it.second) {
+          const size_t r = table.size() - 1;
+          if (v_chunk) v_chunk[r] = c;
+          if (v_off) v_off[r] = (uint64_t)(id - b0);
+          if (v_len) v_len[r] = v.id_len;
+        }
+        if (uuid) uuid[P] = it.first->second;
+        if (time) time[P] = v.time;
+        if (lon) lon[P] = v.lon;
+        if (lat) lat[P] = v.lat;
+        if (acc) acc[P] = v.acc;
+        ++P;
+      }
+      b = nl ? nl + 1 : e;
+    }
+  }
+  info[3] = P;
+  info[4] = table.size();
+}
+
+// Rule 14's generic rule over the same input, on the host alone (rm_messages_parse_host): as
+// lines_parse_host, with either kind; a tolerant call drops and lists malformed lines
+void messages_parse_host(const MessagesDesc& d, uint64_t info[8], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
+                         uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len, std::vector<DroppedMessage>* dropped) {
+  if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("message chunks are NULL");
+  if (const char* e = msg::format_error(d.fmt); *e) throw std::runtime_error(std::string("message format: ") + e);
+  std::fill(info, info + 8, 0);
+  if (dropped) dropped->clear();
+  std::unordered_map<std::string_view, uint32_t> table;
+  uint64_t P = 0;
+  for (uint32_t c = 0; c < d.n_chunks; ++c) {
+    const uint8_t* b = (const uint8_t*)d.data[c];
+    const uint8_t* const b0 = b;
+    const uint8_t* const e = b + d.len[c];
+    uint64_t line = 0;
+    while (b < e) {
+      const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(e - b));
+      const uint8_t* le = nl ? nl : e;
+      ++line;
+      sv::Line v{};
+      const char* why = nullptr;
+      const uint32_t st = msg::generic_message(b, le, d.fmt, v, &why);
+      if (st == sv::kBad && d.strict)
+        throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + why);
+      ++info[0];
+      info[1] += st == sv::kBlank;
+      info[2] += st == sv::kOutside;
+      if (st == sv::kBad) {
+        ++info[7];
+        if (dropped && dropped->size() < kMaxDropped) dropped->push_back(DroppedMessage{c + 1, line, why});
+      }
       if (st == sv::kPoint) {
         const uint8_t* id = b + v.id_off;
         const auto it = table.emplace(std::string_view((const char*)id, v.id_len), (uint32_t)table.size());

@@ -19,6 +19,9 @@
 //             from pinned memory and stops at zero triggers
 //   output    windows and forwarded reports of a call, radix-sorted by the triggering arrival
 //
+//   entries   push() stages host arrays through pinned memory; push_device() takes arrivals that
+//             already lie in HBM (the line reader's points, rule 14) and joins push() at the append
+//
 // Nothing here loops over points or vehicles on the host.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -302,6 +305,12 @@ __global__ void k_sess_trim(SessArgs a, uint32_t T, int evict, const ReportStats
   }
 }
 
+// the stream time of arrivals that come without one: one for all, or each point's own time
+__global__ void k_sess_stamp(uint64_t n, const double* time, int has_stamp, long long stamp, long long* out) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) out[j] = has_stamp ? stamp : (long long)(time[j] * 1000.0);
+}
+
 __global__ void k_sess_fill(uint32_t n, uint32_t* v, uint32_t x) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k < n) v[k] = x;
@@ -348,6 +357,7 @@ struct Session::Impl {
   // the micro-batch: pinned staging and its device copy (grow-only)
   char* hstage = nullptr; char* dstage = nullptr; uint64_t stage_cap = 0;
   unsigned long long* key0 = nullptr; unsigned long long* key1 = nullptr; uint64_t key_cap = 0;
+  long long* gen_stamp = nullptr; uint64_t gen_cap = 0;   // push_device: stamps made on the device
   // a call's output: as written (unsorted) and sorted by triggering arrival
   SessionWindow* win = nullptr; SessionWindow* win_s = nullptr; unsigned long long* win_key = nullptr;
   uint32_t* win_rank = nullptr; uint32_t win_cap = 0;
@@ -451,6 +461,9 @@ struct Session::Impl {
       dstage = alloc<char>(c * 32);
       stage_cap = c;
     }
+    ensure_keys(n);
+  }
+  void ensure_keys(uint64_t n) {
     if (n > key_cap) {
       drop(key0); drop(key1);
       key_cap = 0;
@@ -746,6 +759,52 @@ void Session::push(const SessionPoints& pts, uint64_t out[8]) {
   for (int q = 0; q < (pts.accuracy ? 4 : 3); ++q)
     RM_HIP(hipMemcpyAsync(d + c * (16 + 4 * q), h + c * (16 + 4 * q), n * 4, hipMemcpyHostToDevice, st));
   s.toc(st);
+  append(n, d_veh, d_time, d_lon, d_lat, d_acc, d_stamp, out);
+}
+
+void Session::check_room(uint64_t n) const {
+  if (p_->extent + n >= 0xffffffffull) throw BatchTooLarge("session store too large (points >= 2^32)");
+}
+
+void Session::push_device(uint64_t n, const uint32_t* d_vehicle, const double* d_time, const float* d_lon, const float* d_lat,
+                          const float* d_acc, const long long* d_stamp, bool has_stamp, int64_t stamp, uint64_t out[8]) {
+  Impl& s = *p_;
+  Matcher& m = *s.m;
+  RM_HIP(hipSetDevice(m.eng_->device()));
+  hipStream_t st = m.stream_;
+  if (n && (!d_vehicle || !d_time || !d_lon || !d_lat)) throw std::runtime_error("session point arrays are NULL");
+  check_room(n);
+  m.sync();
+  s.begin_call(st);
+  if (n == 0) {
+    s.hctr[kSActive] = 0;
+    rounds(false, out);
+    return;
+  }
+  s.ensure_keys(n);
+  s.ensure_win(n);
+  if (!d_stamp) {
+    if (n > s.gen_cap) {
+      s.drop(s.gen_stamp);
+      s.gen_cap = 0;
+      const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
+      s.gen_stamp = s.alloc<long long>(c);
+      s.gen_cap = c;
+    }
+    s.tic(1, st);
+    hipLaunchKernelGGL(k_sess_stamp, dim3(grid(n)), dim3(256), 0, st, n, d_time, has_stamp ? 1 : 0, (long long)stamp, s.gen_stamp);
+    s.toc(st);
+    d_stamp = s.gen_stamp;
+  }
+  append(n, d_vehicle, d_time, d_lon, d_lat, d_acc, d_stamp, out);
+}
+
+// push() behind its staging: the n arrivals lie in HBM.  They are copied into the store before the
+// first match round, which reuses the runner's workspace.
+void Session::append(uint64_t n, const uint32_t* d_veh, const double* d_time, const float* d_lon, const float* d_lat,
+                     const float* d_acc, const long long* d_stamp, uint64_t out[8]) {
+  Impl& s = *p_;
+  hipStream_t st = s.m->stream_;
   s.tic(1, st);
   hipLaunchKernelGGL(k_sess_keys, dim3(grid(n)), dim3(256), 0, st, n, d_veh, d_time, s.nV, s.key0, s.ctr);
   s.sort_keys(s.key0, s.key1, n, st);

@@ -254,6 +254,147 @@ def parse_lines_host(chunks, fmt=None):
                 info=dict(zip(LINES_INFO, (int(x) for x in info))))
 
 
+MESSAGES_INFO = LINES_INFO + ("dropped",)
+MESSAGE_KEYS = ("id", "lat", "lon", "time", "accuracy")
+
+
+class MessageFormat:
+    """Layout of raw stream messages (rm_message_format; DESIGN.md §3 rule 14): kind 0, separated
+    values read by `line` (a LineFormat); kind 1, one JSON object per line whose members `keys`
+    (id, lat, lon, time, accuracy; an empty accuracy key: none) hold the values, with `line`'s
+    time_format, accuracy_cap and bbox."""
+
+    def __init__(self, kind=0, line=None, keys=("id", "latitude", "longitude", "timestamp", "accuracy")):
+        if kind not in (0, 1):
+            raise ValueError("kind is 0 (separated values) or 1 (JSON)")
+        keys = tuple(k.encode() if isinstance(k, str) else bytes(k) for k in keys)
+        if len(keys) != 5:
+            raise ValueError("keys are id, lat, lon, time, accuracy")
+        if kind == 1:
+            if any(len(k) > 31 for k in keys):
+                raise ValueError("a key is longer than 31 bytes")
+            if any(len(k) == 0 for k in keys[:4]):
+                raise ValueError("the id, lat, lon and time keys cannot be empty")
+            if any(c in b'"\\' or c < 0x20 for k in keys for c in k):
+                raise ValueError("a key holds a quote, a backslash or a control byte")
+            used = [k for k in keys if k]
+            if len(set(used)) != len(used):
+                raise ValueError("two keys are equal")
+        self.kind, self.line, self.keys = int(kind), line or LineFormat(), keys
+
+    @classmethod
+    def from_spec(cls, spec, **kw):
+        """Either formatter string of the reference (Formatter.java:36-51): the separated-value form
+        LineFormat.from_spec reads, or ``@json@id@lat@lon@time@accuracy[@yyyy-MM-dd HH:mm:ss]`` (the
+        first character splits the rest into type, the five keys and an optional date pattern)."""
+        if len(spec) < 2:
+            raise ValueError("empty formatter spec")
+        args = spec[1:].split(spec[0])
+        if args[0] == "sv":
+            return cls(0, LineFormat.from_spec(spec, **kw))
+        if args[0] != "json":
+            raise ValueError("unsupported raw format parser: %r" % args[0])
+        if len(args) < 6:
+            raise ValueError("json formatter needs the id, lat, lon, time and accuracy keys")
+        pattern = args[6] if len(args) > 6 else None
+        if pattern not in (None, DATE_PATTERN):
+            raise ValueError("only the date pattern %r is read" % DATE_PATTERN)
+        return cls(1, LineFormat(time_format=1 if pattern else 0, **kw), args[1:6])
+
+    def _c(self):
+        f = _lib.RmMessageFormat()
+        _lib.lib().rm_default_message_format(C.byref(f))
+        f.kind = self.kind
+        f.line = self.line._c()
+        for i, k in enumerate(self.keys):
+            f.key[i].value = k if self.kind == 1 else b""
+        return f
+
+
+def _messages_desc(chunks, fmt, strict, stamp_ms):
+    views = _chunk_views(chunks)
+    n = len(views)
+    data = (C.c_void_p * max(n, 1))(*[v.ctypes.data if len(v) else None for v in views])
+    lens = (C.c_uint64 * max(n, 1))(*[len(v) for v in views])
+    fmt = fmt or MessageFormat()
+    if isinstance(fmt, LineFormat):
+        fmt = MessageFormat(0, fmt)
+    d = _lib.RmMessagesDesc(n, C.cast(data, C.c_void_p), C.cast(lens, C.c_void_p), fmt._c(), 1 if strict else 0,
+                            0 if stamp_ms is None else 1, 0 if stamp_ms is None else int(stamp_ms))
+    return d, (views, data, lens)
+
+
+def _dropped(n, chunk, line, reasons):
+    why = reasons.raw.split(b"\0")
+    return [(int(chunk[k]), int(line[k]), why[k].decode()) for k in range(int(n.value))]
+
+
+def parse_messages_host(chunks, fmt=None, strict=False):
+    """Rule 14's generic rule over `chunks` on the host (no GPU): parse_lines_host's dict with
+    info["dropped"] and `dropped`, the first (at most 64) malformed messages of a tolerant call as
+    (chunk, line, reason), both 1-based.  A strict call raises on the first one instead."""
+    d, keep = _messages_desc(chunks, fmt, strict, None)
+    info = (C.c_uint64 * 8)()
+    err = C.create_string_buffer(512)
+    L = _lib.lib()
+    if L.rm_messages_parse_host(C.byref(d), info, None, None, None, None, None, None, None, None, None, None, None, None, 0,
+                                err, 512) != 0:
+        raise _lib.RmError(err.value.decode("utf-8", "replace"))
+    n, nv = int(info[3]), int(info[4])
+    uuid = np.empty(n, np.uint32)
+    time = np.empty(n, np.float64)
+    lon, lat, acc = (np.empty(n, np.float32) for _ in range(3))
+    chunk = np.empty(nv, np.uint32)
+    off = np.empty(nv, np.uint64)
+    ln = np.empty(nv, np.uint32)
+    nd = C.c_uint32(0)
+    dchunk = (C.c_uint32 * 64)()
+    dline = (C.c_uint64 * 64)()
+    reasons = C.create_string_buffer(64 * 64)
+    if L.rm_messages_parse_host(C.byref(d), info, uuid.ctypes.data, time.ctypes.data, lon.ctypes.data, lat.ctypes.data,
+                                acc.ctypes.data, chunk.ctypes.data, off.ctypes.data, ln.ctypes.data, C.byref(nd),
+                                C.addressof(dchunk), C.addressof(dline), C.addressof(reasons), 64 * 64, err, 512) != 0:
+        raise _lib.RmError(err.value.decode("utf-8", "replace"))
+    return dict(uuid=uuid, time=time, lon=lon, lat=lat, accuracy=acc, names=_names(chunks, chunk, off, ln),
+                info=dict(zip(MESSAGES_INFO, (int(x) for x in info))), dropped=_dropped(nd, dchunk, dline, reasons))
+
+
+class VehicleDirectory:
+    """The map from vehicle id bytes to a dense index that holds for a whole stream, kept on the GPU
+    (rm_directory_*; DESIGN.md §3 rule 14): indices in first-seen order over every call's kept points."""
+
+    def __init__(self, max_vehicles, device=0):
+        self.max_vehicles = int(max_vehicles)
+        self._h = _lib.lib().rm_directory_create(int(device), self.max_vehicles)
+        if not self._h:
+            raise _lib.RmError(_lib.last_error())
+
+    def close(self):
+        if getattr(self, "_h", None):
+            _lib.lib().rm_directory_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def size(self):
+        n = C.c_uint32(0)
+        _lib.check(_lib.lib().rm_directory_size(self._h, C.byref(n)))
+        return int(n.value)
+
+    def names(self, first=0, n=None):
+        """The names of vehicles [first, first + n) (default: all), in index order."""
+        n = self.size - first if n is None else int(n)
+        nb = C.c_uint64(0)
+        off = np.zeros(n + 1, np.uint64)
+        _lib.check(_lib.lib().rm_directory_names(self._h, int(first), n, off.ctypes.data, None, C.byref(nb)))
+        raw = np.zeros(max(int(nb.value), 1), np.uint8)
+        _lib.check(_lib.lib().rm_directory_names(self._h, int(first), n, off.ctypes.data, raw.ctypes.data, C.byref(nb)))
+        b = raw.tobytes()
+        return [b[int(off[k]):int(off[k + 1])].decode("utf-8", "replace") for k in range(n)]
+
+
 class BatchMatcher:
     """One HIP stream + device workspace; runs whole batches of traces."""
 
@@ -658,6 +799,41 @@ class VehicleSessions:
         out = (C.c_uint64 * 8)()
         _lib.check(_lib.lib().rm_session_push(self._h, C.byref(d), out))
         return dict(zip(SESSION_COUNTS, (int(x) for x in out)))
+
+    def push_messages(self, chunks, fmt, directory, stamp_ms=None, strict=False):
+        """Raw messages (one per line, in `chunks`) read, keyed through `directory` and pushed, all
+        on the GPU (DESIGN.md §3 rule 14).  stamp_ms: the stream time of the whole call, or None
+        for each message's own time.  Returns (push counts, line counts): SESSION_COUNTS and
+        MESSAGES_INFO.  A tolerant call drops malformed messages (dropped_messages() lists them)."""
+        d, keep = _messages_desc(chunks, fmt, strict, stamp_ms)
+        out = (C.c_uint64 * 8)()
+        info = (C.c_uint64 * 8)()
+        _lib.check(_lib.lib().rm_session_push_messages(self._h, getattr(directory, "_h", None), C.byref(d), out, info))
+        return dict(zip(SESSION_COUNTS, (int(x) for x in out))), dict(zip(MESSAGES_INFO, (int(x) for x in info)))
+
+    def dropped_messages(self):
+        """The first (at most 64) messages the last push_messages dropped: (chunk, line, reason)."""
+        nd = C.c_uint32(0)
+        dchunk = (C.c_uint32 * 64)()
+        dline = (C.c_uint64 * 64)()
+        reasons = C.create_string_buffer(64 * 64)
+        _lib.check(_lib.lib().rm_session_dropped_messages(self._h, C.byref(nd), C.addressof(dchunk), C.addressof(dline),
+                                                          C.addressof(reasons), 64 * 64))
+        return _dropped(nd, dchunk, dline, reasons)
+
+    def messages_span(self):
+        """(smallest, largest) time among the points the last push_messages kept, or None for none."""
+        t = (C.c_double * 2)()
+        n = C.c_uint64(0)
+        _lib.check(_lib.lib().rm_session_messages_span(self._h, t, C.byref(n)))
+        return (float(t[0]), float(t[1])) if n.value else None
+
+    def messages_ms(self):
+        """Device ms of the last push_messages: upload, parse, ids, directory, then ms()'s five."""
+        t = (C.c_double * 9)()
+        _lib.check(_lib.lib().rm_session_messages_time(self._h, t))
+        return dict(zip(("text_upload", "parse", "ids", "directory", "upload", "append", "trigger", "match", "trim"),
+                        (float(x) for x in t)))
 
     def punctuate(self, timestamp_ms):
         out = (C.c_uint64 * 8)()

@@ -1,0 +1,138 @@
+"""GPU stream reporter: the reference's streaming topology (Reporter.java: formatter -> batcher ->
+anonymiser) over files of raw messages, every processor on the MI355X.
+
+    python -m reporter_amd.stream --formatter '@json@id@lat@lon@time@acc' --match-config conf.json \\
+        --output-location out/ messages.txt [more files or directories ...]
+
+The text goes up in polls of about --poll-bytes; each poll is read, keyed through the vehicle
+directory and pushed into the vehicle sessions on the device (rm_session_push_messages), and the
+forwarded reports join the tile store device to device.  Stream time is the messages' own: whenever
+it has advanced --flush-interval seconds past the last flush the tile store is flushed, and once at
+the end, after a punctuate that evicts every vehicle.  Tiles are written under --output-location as
+reporter_amd.batch writes them; a tile flushed again later gets the suffix ".<flush number>".
+"""
+import argparse
+import json
+import logging
+import os
+import sys
+
+
+def polls(paths, poll_bytes):
+    """The files' bytes in order, cut behind line ends into pieces of about poll_bytes."""
+    for p in paths:
+        with open(p, "rb") as f:
+            data = f.read()
+        at = 0
+        while at < len(data):
+            end = len(data) if len(data) - at <= poll_bytes else data.find(b"\n", at + poll_bytes - 1) + 1
+            end = end if end > 0 else len(data)
+            yield data[at:end]
+            at = end
+
+
+def write_flush(files, dest, k):
+    from .batch import write_tiles
+    out = {}
+    for name, body in files.items():
+        if os.path.exists(os.path.join(dest, name)):
+            name = "%s.%d" % (name, k)
+        out[name] = body.decode()
+    write_tiles(out, dest)
+    return len(out)
+
+
+def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transition_levels=(0, 1), privacy=2,
+        quantisation=3600, flush_interval=300, source="smpl_rprt", max_vehicles=1 << 16, poll_bytes=1 << 20, device=0,
+        report_dist_m=None, report_count=None, report_time_s=None):
+    from . import engine
+    from .batch import options_from_config
+    opts, graph = options_from_config(conf, mode)
+    fmt = engine.MessageFormat.from_spec(formatter)
+    eng = engine.Engine(graph, device)
+    with open(conf) as f:
+        radius = json.load(f).get("reporter_amd", {}).get("ball_radius")
+    if radius is not None:
+        eng.set_ball_radius(float(radius))
+    bm = engine.BatchMatcher(eng)
+    sess = engine.VehicleSessions(bm, max_vehicles, report_dist_m, report_count, report_time_s, opts=opts,
+                                  report_levels=report_levels, transition_levels=transition_levels)
+    vdir = engine.VehicleDirectory(max_vehicles, device)
+    store = engine.TileStore(device, quantisation, privacy, source, mode)
+    stats = dict(polls=0, messages=0, dropped=0, forwarded=0, flushes=0, files=0)
+    last_flush = now = None
+    try:
+        def flush():
+            files, _ = store.flush()
+            stats["files"] += write_flush(files, dest, stats["flushes"])
+            stats["flushes"] += 1
+
+        for text in polls(paths, poll_bytes):
+            out, info = sess.push_messages([text], fmt, vdir)
+            store.add_session(sess)
+            stats["polls"] += 1
+            stats["messages"] += info["points"]
+            stats["dropped"] += info["dropped"]
+            stats["forwarded"] += out["forwarded"]
+            for c, ln, why in sess.dropped_messages():
+                logging.warning("poll %d line %d dropped: %s", stats["polls"], ln, why)
+            span = sess.messages_span()
+            if span is None:
+                continue
+            now = span[1] if now is None else max(now, span[1])
+            last_flush = span[0] if last_flush is None else last_flush
+            if now - last_flush >= flush_interval:
+                flush()
+                last_flush = now
+        if now is not None:
+            out = sess.punctuate(int(now * 1000) + 10 ** 7)   # every vehicle is stale: all report and leave
+            store.add_session(sess)
+            stats["forwarded"] += out["forwarded"]
+        flush()
+        stats["vehicles"] = vdir.size
+        return stats
+    finally:
+        store.close()
+        vdir.close()
+        sess.close()
+        bm.close()
+        eng.close()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("inputs", nargs="+", help="files (or directories of files) of raw messages, one per line")
+    ap.add_argument("--formatter", required=True, help="the reference's formatter string, e.g. ',sv,\\|,1,9,10,0,5' or "
+                    "'@json@id@latitude@longitude@timestamp@accuracy'")
+    ap.add_argument("--match-config", required=True)
+    ap.add_argument("--output-location", required=True, help="a directory for the tile files")
+    ap.add_argument("--mode", default="auto")
+    ap.add_argument("--reports", default="0,1")
+    ap.add_argument("--transitions", default="0,1")
+    ap.add_argument("--privacy", type=int, default=2)
+    ap.add_argument("--quantisation", type=int, default=3600)
+    ap.add_argument("--flush-interval", type=int, default=300)
+    ap.add_argument("--source", default="smpl_rprt")
+    ap.add_argument("--max-vehicles", type=int, default=1 << 16)
+    ap.add_argument("--poll-bytes", type=int, default=1 << 20, help="about how much text goes into one push")
+    ap.add_argument("--report-dist", type=float, help="session trigger distance in metres (default 500)")
+    ap.add_argument("--report-count", type=int, help="session trigger point count (default 10)")
+    ap.add_argument("--report-time", type=float, help="session trigger time in seconds (default 60)")
+    a = ap.parse_args(argv)
+    paths = []
+    for p in a.inputs:
+        if os.path.isdir(p):
+            for root, _, fs in sorted(os.walk(p)):
+                paths += [os.path.join(root, f) for f in sorted(fs)]
+        else:
+            paths.append(p)
+    levels = lambda s: tuple(int(x) for x in s.split(",") if x != "")
+    stats = run(paths, a.match_config, a.output_location, a.formatter, a.mode, levels(a.reports), levels(a.transitions),
+                a.privacy, a.quantisation, a.flush_interval, a.source, a.max_vehicles, a.poll_bytes,
+                int(os.environ.get("LOCAL_RANK", "0")), a.report_dist, a.report_count, a.report_time)
+    print(json.dumps(stats))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -1,0 +1,143 @@
+"""Stream formatter probe (rule 14): C2's workload as raw messages into vehicle sessions,
+by the device route and by the route the host arrays offered before it.
+
+    python scripts/stream_probe.py [--vehicles 10000] [--points 600] [--per-push 60] [--runs 4]
+                                   [--out profiles/stream/stream_probe.json]
+
+The vehicles' traces are written as text in time order, --per-push messages per vehicle in a push
+(10,000 x 60: 600 k messages), once as separated values and once as JSON.  Route (a) is
+VehicleSessions.push_messages: one upload of the text, everything else on the device; its split is
+rm_session_messages_time's.  Route (b) is what the same bytes took before: BatchMatcher.parse_lines,
+the download of the points and the names, a Python dictionary from name to persistent index, then
+VehicleSessions.push with host arrays.  (b) reads separated values only: there was no such route
+for JSON text, so JSON is timed by (a) alone.  The routes alternate --runs times in one process
+after a warm-up push of each.  Prints one JSON line and writes it to --out."""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from reporter_amd import engine, world   # noqa: E402
+
+PARTS = ("text_upload", "parse", "ids", "directory", "upload", "append", "trigger", "match", "trim")
+
+
+def write_text(arr, a, b, kind):
+    v, t, la, lo, ac = arr["vehicle"][a:b], arr["time"][a:b], arr["lat"][a:b], arr["lon"][a:b], arr["accuracy"][a:b]
+    if kind == 0:
+        rows = ["veh-%07d,%d,%.6f,%.6f,%.1f" % r for r in zip(v.tolist(), t.astype(np.int64).tolist(), la.tolist(), lo.tolist(),
+                                                               ac.tolist())]
+    else:
+        rows = ['{"id":"veh-%07d","timestamp":%d,"latitude":%.6f,"longitude":%.6f,"accuracy":%.1f}' % r
+                for r in zip(v.tolist(), t.astype(np.int64).tolist(), la.tolist(), lo.tolist(), ac.tolist())]
+    return ("\n".join(rows) + "\n").encode()
+
+
+def route_a(bm, texts, fmt, n_vehicles):
+    sess = engine.VehicleSessions(bm, n_vehicles)
+    vdir = engine.VehicleDirectory(n_vehicles)
+    pushes, msgs, host_lines, lines, fwd = [], 0, 0, 0, 0
+    for text in texts:
+        t0 = time.perf_counter()
+        out, info = sess.push_messages([text], fmt, vdir)
+        wall = (time.perf_counter() - t0) * 1e3
+        ms = sess.messages_ms()
+        pushes.append([round(wall, 3)] + [round(ms[p], 3) for p in PARTS])
+        msgs += info["points"]
+        host_lines += info["host_lines"]
+        lines += info["lines"]
+        fwd += out["forwarded"]
+    size = vdir.size
+    vdir.close()
+    sess.close()
+    p = np.array(pushes)
+    wall_s = p[:, 0].sum() * 1e-3
+    return dict(wall_s=wall_s, messages=msgs, messages_per_s=msgs / wall_s, forwarded=fwd, vehicles=size,
+                host_line_share=host_lines / max(lines, 1), sum_ms=dict(zip(("wall",) + PARTS, p.sum(axis=0).round(2).tolist())),
+                push_columns=["wall_ms"] + list(PARTS), pushes=pushes)
+
+
+def route_b(bm, texts, n_vehicles):
+    sess = engine.VehicleSessions(bm, n_vehicles)
+    table = {}
+    pushes, msgs, fwd = [], 0, 0
+    for text in texts:
+        t0 = time.perf_counter()
+        pts = bm.parse_lines([text])
+        t1 = time.perf_counter()
+        names = bm.vehicle_names([text])
+        lut = np.empty(len(names), np.uint32)
+        for k, name in enumerate(names):
+            lut[k] = table.setdefault(name, len(table))
+        idx = lut[pts["uuid"]]
+        t2 = time.perf_counter()
+        out = sess.push(idx, pts["time"], pts["lon"], pts["lat"], pts["accuracy"], (pts["time"] * 1000.0).astype(np.int64))
+        t3 = time.perf_counter()
+        pushes.append([round((t3 - t0) * 1e3, 3), round((t1 - t0) * 1e3, 3), round((t2 - t1) * 1e3, 3), round((t3 - t2) * 1e3, 3)])
+        msgs += len(idx)
+        fwd += out["forwarded"]
+    sess.close()
+    p = np.array(pushes)
+    wall_s = p[:, 0].sum() * 1e-3
+    cols = ("wall", "parse_and_download", "names_and_dictionary", "push")
+    return dict(wall_s=wall_s, messages=msgs, messages_per_s=msgs / wall_s, forwarded=fwd, vehicles=len(table),
+                sum_ms=dict(zip(cols, p.sum(axis=0).round(2).tolist())), push_columns=[c + "_ms" for c in cols], pushes=pushes)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--vehicles", type=int, default=10000)
+    ap.add_argument("--points", type=int, default=600)
+    ap.add_argument("--per-push", type=int, default=60)
+    ap.add_argument("--runs", type=int, default=4)
+    ap.add_argument("--out", default=os.path.join("profiles", "stream", "stream_probe.json"))
+    a = ap.parse_args()
+    cfg = world.CONFIGS["C2"]
+    tmp = tempfile.mkdtemp(prefix="stream_probe")
+    graph = os.path.join(tmp, "c2.rmg")
+    world.build_world(graph, cfg["rows"], cfg["cols"], cfg["block_m"], seed=1, cell_m=cfg["cell_m"])
+    tr = world.generate_traces(graph, n_traces=a.vehicles, n_points=a.points, rate_s=cfg["rate_s"], noise_m=cfg["noise_m"],
+                               seed=1000)
+    T, n = a.vehicles, a.points
+    order = np.arange(T * n).reshape(T, n).T.ravel()          # time-major: every vehicle's k-th point, then the next
+    arr = {"vehicle": (order // n).astype(np.uint32)}
+    for f in ("time", "lon", "lat", "accuracy"):
+        arr[f] = np.ascontiguousarray(tr[f][order])
+    per = a.per_push * T
+    cuts = [(s, min(s + per, T * n)) for s in range(0, T * n, per)]
+    texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in (0, 1)}
+    fmt = {0: engine.MessageFormat(0), 1: engine.MessageFormat(1)}
+    eng = engine.Engine(graph, 0)
+    bm = engine.BatchMatcher(eng)
+    # warm every route (route tables, workspaces, the readers' buffers)
+    route_a(bm, texts[0][:2], fmt[0], T)
+    route_a(bm, texts[1][:2], fmt[1], T)
+    route_b(bm, texts[0][:2], T)
+    runs = []
+    for _ in range(max(a.runs, 1)):
+        runs.append(dict(a_sv=route_a(bm, texts[0], fmt[0], T), b_sv=route_b(bm, texts[0], T),
+                         a_json=route_a(bm, texts[1], fmt[1], T)))
+    out = dict(args=dict(vehicles=a.vehicles, points=a.points, per_push=a.per_push, runs=a.runs),   # the invocation
+               vehicles=T, points_per_vehicle=n, messages_per_push=per, pushes=len(cuts),
+               text_bytes=dict(sv=sum(len(t) for t in texts[0]), json=sum(len(t) for t in texts[1])), runs=runs,
+               a_sv_messages_per_s=[r["a_sv"]["messages_per_s"] for r in runs],
+               b_sv_messages_per_s=[r["b_sv"]["messages_per_s"] for r in runs],
+               a_json_messages_per_s=[r["a_json"]["messages_per_s"] for r in runs],
+               note="(b) has no JSON route: a_json stands beside b_sv only as the same messages in another spelling")
+    line = json.dumps(out)
+    print(line)
+    os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+    with open(a.out, "w") as f:
+        f.write(line + "\n")
+    bm.close()
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()

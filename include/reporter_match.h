@@ -613,6 +613,40 @@ int rm_tilestore_flush(rm_tilestore* t, char** blob, size_t* len, uint64_t out[5
 /* device time (ms, HIP events) of the last call: upload, expand, sort, cull, text, download */
 int rm_tilestore_time(rm_tilestore* t, double ms[6]);
 
+/* ---------------- stream snapshot (DESIGN.md §3 rule 15) ----------------
+ * The state of a stream -- every vehicle's open point list (rm_session), every id-to-index
+ * assignment (rm_directory), every tile row still waiting for its privacy count (rm_tilestore) --
+ * saved into one versioned, checksummed blob and restored from it: the reference's changelog-backed
+ * state stores (BatchingProcessor.GetStore, AnonymisingProcessor.GetTileStore / GetMapStore).  A
+ * stream stopped anywhere, saved, torn down, rebuilt from the blob and continued gives the output of
+ * the stream that never stopped, bit for bit.
+ *
+ * Any of the three objects may be NULL: a save leaves that section out, a load skips it.  A load
+ * into an object whose section is absent fails, as do objects on different devices.  The targets of
+ * a load must be empty, as created; the blob's sessions fit any n_vehicles above the largest saved
+ * index and its names any max_vehicles and any RM_LINES_HASH_BITS (the table is rebuilt).  A load
+ * that fails -- a damaged or forged blob (each clause of the rule has its own message), a target too
+ * small, a quantisation other than the tile store's, HBM running out -- leaves its targets empty and
+ * usable.  A save changes nothing the stream will output.
+ *
+ * What is not state: the session's thresholds, options and run parameters, the tile store's source,
+ * mode and privacy (they are the loading objects'); the last call's windows and reports (after a load
+ * rm_session_get_reports gives 0 and rm_tilestore_add_session adds nothing); and the run parameters'
+ * hist_dev / dur_dev, which belong to the caller and are not part of a snapshot.
+ *
+ * save: *blob is library-allocated (free with rm_free); `user` bytes travel opaque.
+ *   out: [0] blob bytes [1] names [2] vehicles holding points [3] points [4] tile rows [5] user bytes
+ *   ms (HIP events): [0] pack [1] gather [2] checksum [3] download
+ * load: out as for save; ms: [0] upload [1] check [2] unpack */
+int rm_snapshot_save(rm_session* s, rm_directory* d, rm_tilestore* t, const char* user, size_t user_len, char** blob,
+                     size_t* len, uint64_t out[6], double ms[6]);
+int rm_snapshot_load(rm_session* s, rm_directory* d, rm_tilestore* t, const char* blob, size_t len, uint64_t out[6],
+                     double ms[6]);
+/* Host only, no GPU: header, table, checksums and the whole structural rule that does not need the
+ * loading objects.  info: [0] version [1] bytes [2] names [3] vehicles [4] points [5] rows
+ * [6] quantisation [7] user offset [8] user bytes.  On failure the reason is in err (and rm_last_error). */
+int rm_snapshot_check_host(const char* blob, size_t len, uint64_t info[9], char* err, size_t errlen);
+
 /* ---------------- RCCL over xGMI (multi-GPU histogram exchange) ----------------
  * One process per GPU.  Replaces the reference's keyed Kafka repartition of
  * "id next_id" reports (BatchingProcessor.java:126) with one all-reduce of the

@@ -239,6 +239,10 @@ PROTOTYPES = [
     ("rm_tilestore_add_session", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
     ("rm_tilestore_flush", C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64)]),
     ("rm_tilestore_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_snapshot_save", C.c_int, [P, P, P, C.c_char_p, C.c_size_t, C.POINTER(P), C.POINTER(C.c_size_t), C.POINTER(C.c_uint64),
+                                   C.POINTER(C.c_double)]),
+    ("rm_snapshot_load", C.c_int, [P, P, P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rm_snapshot_check_host", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("rm_comm_unique_id", C.c_int, [P]),
     ("rm_comm_init", P, [C.c_int, C.c_int, P, C.c_int]),
     ("rm_comm_destroy", None, [P]),

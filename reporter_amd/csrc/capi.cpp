@@ -32,6 +32,7 @@
 #include "json.hpp"
 #include "osm_model.hpp"
 #include "serve_policy.hpp"
+#include "snapshot.hpp"
 #include "trace_json.hpp"
 
 using namespace rm;
@@ -2108,6 +2109,33 @@ int rm_tilestore_time(rm_tilestore* t, double ms[6]) {
     if (!t || !ms) throw std::runtime_error("tile store or ms is NULL");
     t->t->times(ms);
   });
+}
+
+// ---------------- stream snapshot (snapshot.hpp, snapshot.hip) ----------------
+int rm_snapshot_save(rm_session* s, rm_directory* d, rm_tilestore* t, const char* user, size_t user_len, char** blob,
+                     size_t* len, uint64_t out[6], double ms[6]) {
+  if (!blob || !len) return fail("blob/len is NULL");
+  *blob = nullptr;
+  *len = 0;
+  return guarded([&] { snapshot_save(s ? s->s.get() : nullptr, d ? d->d.get() : nullptr, t ? t->t.get() : nullptr, user, user_len, blob, len, out, ms); });
+}
+int rm_snapshot_load(rm_session* s, rm_directory* d, rm_tilestore* t, const char* blob, size_t len, uint64_t out[6],
+                     double ms[6]) {
+  return guarded([&] {
+    if (!blob) throw std::runtime_error("blob is NULL");
+    snapshot_load(s ? s->s.get() : nullptr, d ? d->d.get() : nullptr, t ? t->t.get() : nullptr, blob, len, out, ms);
+  });
+}
+int rm_snapshot_check_host(const char* blob, size_t len, uint64_t info[9], char* err, size_t errlen) {
+  const int rc = guarded([&] {
+    const std::string why = snap::check_host(blob, len, info);
+    if (!why.empty()) throw std::runtime_error(why);
+  });
+  if (rc && err && errlen) {
+    std::strncpy(err, g_err.c_str(), errlen - 1);
+    err[errlen - 1] = 0;
+  }
+  return rc;
 }
 
 }  // extern "C"

@@ -114,6 +114,56 @@ __global__ void k_dir_scatter(uint64_t P, uint32_t G, const uint32_t* map, uint3
   p_uuid[k] = u < G ? map[u] : kDirEmpty;
 }
 
+// ---- the stream snapshot (DESIGN.md §3 rule 15) ----
+// the arena holds the names in index order, so a name's arena offset is its snapshot offset
+__global__ void k_dir_snap_off(uint32_t cap, DirTable t, uint32_t n_known, unsigned long long arena_used, unsigned long long* off) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k == 0u) off[n_known] = arena_used;
+  if (k >= cap) return;
+  const uint32_t v = t.veh[k];
+  if (v != kDirEmpty && v < n_known) off[v] = t.noff[k];
+}
+
+// name k of a snapshot takes index k: its bytes lie in the arena at off[k] already
+__global__ void k_dir_snap_insert(uint32_t n, const unsigned long long* off, unsigned long long hmask, DirTable t, uint32_t* err) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t a = (uint32_t)off[k], len = (uint32_t)(off[k + 1] - off[k]);
+  const unsigned long long h = sv::id_hash(t.arena + a, len) & hmask;
+  uint32_t slot = dir_slot(h, t.mask);
+  for (uint32_t probe = 0; probe <= t.mask; ++probe) {
+    if (atomicCAS(t.veh + slot, kDirEmpty, k) == kDirEmpty) {
+      t.hash[slot] = h; t.noff[slot] = a; t.nlen[slot] = len;
+      return;
+    }
+    slot = (slot + 1u) & t.mask;
+  }
+  err[0] = 1u;
+}
+
+// ... and must be the first of its bytes that a lookup finds: of two equal names one is not
+__global__ void k_dir_snap_verify(uint32_t n, const unsigned long long* off, unsigned long long hmask, DirTable t,
+                                  unsigned long long* snap_err, unsigned long long dup) {
+  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint32_t len = (uint32_t)(off[k + 1] - off[k]);
+  const uint8_t* s = t.arena + (uint32_t)off[k];
+  const unsigned long long h = sv::id_hash(s, len) & hmask;
+  uint32_t slot = dir_slot(h, t.mask), res = kDirEmpty;
+  for (uint32_t probe = 0; probe <= t.mask; ++probe) {
+    const uint32_t v = t.veh[slot];
+    if (v == kDirEmpty) break;
+    if (t.hash[slot] == h && t.nlen[slot] == len) {
+      const uint8_t* q = t.arena + t.noff[slot];
+      bool same = true;
+      for (uint32_t i = 0; same && i < len; ++i) same = q[i] == s[i];
+      if (same) { res = v; break; }
+    }
+    slot = (slot + 1u) & t.mask;
+  }
+  if (res != k) atomicOr(snap_err, dup);
+}
+
 }  // namespace
 
 struct Directory::Impl {
@@ -269,6 +319,65 @@ void Directory::assign(Matcher& m) {
   s.arena_used += new_bytes;
   float t = 0.f;
   if (hipEventElapsedTime(&t, s.ev[0], s.ev[1]) == hipSuccess) s.ms = t;
+}
+
+uint64_t Directory::name_bytes() const { return p_->arena_used; }
+
+void Directory::snapshot_gather(unsigned long long* d_off, uint8_t* d_bytes, hipStream_t st) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  hipLaunchKernelGGL(k_dir_snap_off, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.t, s.n_known, (unsigned long long)s.arena_used, d_off);
+  RM_HIP(hipGetLastError());
+  if (s.arena_used) RM_HIP(hipMemcpyAsync(d_bytes, s.t.arena, s.arena_used, hipMemcpyDeviceToDevice, st));
+}
+
+void Directory::snapshot_insert(uint32_t n, const unsigned long long* d_off, const uint8_t* d_bytes, uint64_t n_bytes,
+                                unsigned long long* d_err, uint32_t dup_bit, hipStream_t st) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  if (s.n_known) throw std::runtime_error("snapshot: the directory is not empty");
+  if (n > s.max_vehicles) throw std::runtime_error("snapshot: more names than the directory's max_vehicles");
+  if (n_bytes >= (1ull << 32)) throw std::runtime_error("directory names pass 2^32 bytes");
+  if (!n) return;
+  if (n_bytes > s.arena_cap) {   // (ensure_arena, with a full HBM reported as the workspaces report it)
+    const uint64_t c = std::max<uint64_t>(n_bytes + n_bytes / 2, 1u << 16);
+    uint8_t* a2 = nullptr;
+    const hipError_t e = hipMalloc((void**)&a2, c);
+    if (e == hipErrorOutOfMemory) {
+      (void)hipGetLastError();
+      throw BatchTooLarge("directory names do not fit in HBM");
+    }
+    RM_HIP(e);
+    RM_HIP(hipStreamSynchronize(st));
+    if (s.t.arena) (void)hipFree(s.t.arena);
+    s.t.arena = a2;
+    s.arena_cap = c;
+  }
+  if (n_bytes) RM_HIP(hipMemcpyAsync(s.t.arena, d_bytes, n_bytes, hipMemcpyDeviceToDevice, st));
+  const unsigned long long hmask = lines_hash_mask();
+  RM_HIP(hipMemsetAsync(s.derr, 0, 4, st));
+  hipLaunchKernelGGL(k_dir_snap_insert, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.t, s.derr);
+  hipLaunchKernelGGL(k_dir_snap_verify, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.t, d_err, 1ull << dup_bit);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipMemcpyAsync(s.hctl + 2, s.derr, 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipStreamSynchronize(st));
+  if (s.hctl[2]) {
+    snapshot_clear(st);
+    throw std::runtime_error("directory: an insert found no room (the table and the host disagree)");
+  }
+  s.n_known = n;
+  s.arena_used = n_bytes;
+}
+
+void Directory::snapshot_clear(hipStream_t st) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  hipLaunchKernelGGL(k_dir_fill, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.t.veh, kDirEmpty);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipMemsetAsync(s.derr, 0, 8, st));
+  RM_HIP(hipStreamSynchronize(st));
+  s.n_known = 0;
+  s.arena_used = 0;
 }
 
 uint64_t Directory::names(uint32_t first, uint32_t n, uint64_t* off, char* bytes) {

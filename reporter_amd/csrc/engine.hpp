@@ -370,6 +370,19 @@ struct SessionWindow {
 };
 static_assert(sizeof(SessionWindow) == 24, "SessionWindow is rm_session_window");
 
+// what snapshot.hip sees of a session (DESIGN.md §3 rule 15): the per-vehicle state and the current
+// point buffer, on `stream`
+struct SessionSnap {
+  uint32_t n_vehicles = 0, n_live = 0;   // n_live: vehicles holding points (after snapshot_pack)
+  uint64_t n_points = 0;
+  uint32_t* off = nullptr; uint32_t* cnt = nullptr; uint32_t* scan_from = nullptr; uint32_t* try_from = nullptr;
+  float* max_sep = nullptr; long long* last_update = nullptr;
+  uint32_t* rank = nullptr;   // n_vehicles + 1 words: after snapshot_pack each vehicle's rank among the non-empty ones
+  float* lon = nullptr; float* lat = nullptr; float* acc = nullptr; double* time = nullptr;
+  uint32_t* arr = nullptr; uint32_t* veh = nullptr;
+  hipStream_t stream = nullptr;
+};
+
 class Session {
  public:
   Session(Matcher* m, uint32_t n_vehicles, const SessionParams& sp);
@@ -401,10 +414,20 @@ class Session {
   // reports in HBM (n_reports() of them, complete when the call has returned)
   int device() const;
   const SessionReport* reports_device() const;
+  // the stream snapshot (rule 15).  snapshot_pack: the store packed as get_store packs it (no
+  // output of the stream changes), the non-empty vehicles ranked.  snapshot_room: the current
+  // buffer with room for n points, for a session that holds none.  snapshot_loaded: n points and
+  // their vehicles' state are in place; the last call's windows and reports are empty.
+  hipStream_t stream() const;   // the runner's
+  SessionSnap snapshot_pack();
+  SessionSnap snapshot_room(uint64_t n_points);
+  void snapshot_loaded(uint64_t n_points);
+  void snapshot_clear();   // every vehicle empty, as created (a load that failed half way)
 
  private:
   struct Impl;
   Impl* p_;
+  SessionSnap snap_view(uint64_t n_points, uint32_t n_live);
   void match_round(uint32_t T, uint64_t P, bool evict);
   void rounds(bool evict, uint64_t out[8]);
   void finish_call(uint64_t out[8]);
@@ -431,6 +454,15 @@ class Directory {
   // written; returns the bytes of the range
   uint64_t names(uint32_t first, uint32_t n, uint64_t* off, char* bytes);
   double last_ms() const;   // device time of the last assign
+  // the stream snapshot (rule 15).  snapshot_gather: the names' offsets (size() + 1) and bytes
+  // (name_bytes()) in index order into device memory.  snapshot_insert, into an empty directory:
+  // name k of the n at d_off / d_bytes gets index k under this process's hash mask; two equal
+  // names set bit dup_bit of *d_err.  snapshot_clear: empty again, as created.
+  uint64_t name_bytes() const;
+  void snapshot_gather(unsigned long long* d_off, uint8_t* d_bytes, hipStream_t st);
+  void snapshot_insert(uint32_t n, const unsigned long long* d_off, const uint8_t* d_bytes, uint64_t n_bytes,
+                       unsigned long long* d_err, uint32_t dup_bit, hipStream_t st);
+  void snapshot_clear(hipStream_t st);
 
  private:
   struct Impl;
@@ -464,11 +496,28 @@ class TileStore {
   int device() const;
   uint64_t rows_held() const;
   uint64_t capacity() const;
+  // the stream snapshot (rule 15): the rows held in store order, the running arrival number, and
+  // a load's two steps: room for n rows in an empty store (grown as add grows it), then n rows in place
+  const void* rows_device() const;
+  uint64_t arrivals() const;
+  uint32_t quantisation() const;
+  hipStream_t stream() const;
+  void* snapshot_room(uint64_t n_rows);
+  void snapshot_loaded(uint64_t n_rows, uint64_t arrivals);
 
  private:
   struct Impl;
   Impl* p_;
 };
+
+// The stream snapshot (DESIGN.md §3 rule 15; snapshot.hpp, snapshot.hip).  Any object may be null.
+// save: *blob is malloc'd; out: bytes, names, vehicles, points, rows, user bytes; ms: pack, gather,
+// checksum, download.  load, into empty objects: out: bytes, names, vehicles, points, rows, user
+// bytes; ms: upload, check, unpack.  A load that throws leaves its targets empty and usable.
+void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, size_t user_len, char** blob, size_t* len,
+                   uint64_t out[6], double ms[6]);
+void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, size_t len, uint64_t out[6], double ms[6]);
+unsigned long long lines_hash_mask();   // RM_LINES_HASH_BITS as the line reader reads it (lines.hip)
 
 // report() (reference py/reporter_service.py:79-179) on the device over host-supplied segment
 // lists: trace k's segments are segs[seg_off[k] .. seg_off[k+1]); reports come back compacted

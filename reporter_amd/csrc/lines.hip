@@ -304,6 +304,8 @@ struct HostLine {
 
 }  // namespace
 
+unsigned long long lines_hash_mask() { return hash_mask(); }
+
 struct LineState {
   DevBuf text, wcnt, wfirst, scan_tmp, status, lat, lon, acc, time, id_off, id_len, hash, flag, pos;
   DevBuf p_off, p_len, v_off, v_len, patch, part, stats, derr;

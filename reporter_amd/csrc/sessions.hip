@@ -581,6 +581,9 @@ Session::Session(Matcher* m, uint32_t n_vehicles, const SessionParams& sp) : p_(
     RM_HIP(hipMemsetAsync(s.cnt, 0, V * 4, st));
     RM_HIP(hipMemsetAsync(s.max_sep, 0, V * 4, st));
     RM_HIP(hipMemsetAsync(s.last_update, 0, V * 8, st));
+    // the counters: a read-out before the first call (get_store, the snapshot's pack) reads them
+    RM_HIP(hipMemsetAsync(s.ctr, 0, kSNumCtr * sizeof(uint32_t), st));
+    std::memset(s.hctr, 0, kSNumCtr * sizeof(uint32_t));
     // an empty vehicle: scan_from = try_from = 1 (its first point never triggers)
     hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.scan_from, 1u);
     hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.try_from, 1u);
@@ -874,6 +877,80 @@ uint64_t Session::get_store(uint32_t* cnt, float* max_sep, int64_t* last_update,
   if (n && time) RM_HIP(hipMemcpy(time, b.time, n * 8, hipMemcpyDeviceToHost));
   if (n && acc) RM_HIP(hipMemcpy(acc, b.acc, n * 4, hipMemcpyDeviceToHost));
   return n;
+}
+
+// ---- the stream snapshot's access (DESIGN.md §3 rule 15; snapshot.hip holds the kernels) ----
+namespace {
+__global__ void k_sess_live(uint32_t nV, const uint32_t* cnt, uint32_t* flag) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v <= nV) flag[v] = v < nV && cnt[v] > 0u ? 1u : 0u;   // (flag[nV] = 0: the scan's last entry is the total)
+}
+}  // namespace
+
+hipStream_t Session::stream() const { return p_->m->stream_; }
+
+SessionSnap Session::snapshot_pack() {
+  Impl& s = *p_;
+  Matcher& m = *s.m;
+  RM_HIP(hipSetDevice(m.eng_->device()));
+  hipStream_t st = m.stream_;
+  m.sync();
+  // get_store's pack, then the rank of every non-empty vehicle among them.  The error word is
+  // the last call's (an overflow there has been thrown already): the pack sets no bit of it
+  RM_HIP(hipMemsetAsync(s.ctr + kSErr, 0, sizeof(uint32_t), st));
+  s.layout_and_copy(0, nullptr, nullptr, nullptr, nullptr, st);
+  RM_HIP(hipMemsetAsync(s.ctr + kSActive, 0, sizeof(uint32_t), st));
+  s.commit(nullptr, st);
+  hipLaunchKernelGGL(k_sess_live, dim3(grid(s.nV + 1ull)), dim3(256), 0, st, s.nV, (const uint32_t*)s.cnt, s.tot);
+  s.scan(s.tot, s.noff, s.nV + 1u, st);
+  RM_HIP(hipMemcpyAsync(s.ctr + kSActive, s.noff + s.nV, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+  RM_HIP(hipGetLastError());
+  s.read_ctr(st);
+  s.extent = s.hctr[kSTotal];
+  return snap_view(s.extent, s.hctr[kSActive]);
+}
+
+SessionSnap Session::snapshot_room(uint64_t n_points) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.m->eng_->device()));
+  if (n_points >= 0xffffffffull) throw BatchTooLarge("session store too large (points >= 2^32)");
+  s.ensure_buf(s.buf[s.cur], n_points);   // (the session holds no points: nothing to keep)
+  return snap_view(n_points, 0u);
+}
+
+void Session::snapshot_loaded(uint64_t n_points) {
+  Impl& s = *p_;
+  s.extent = n_points;
+  s.n_win = s.n_rep = 0;   // the last call's outputs are not part of a snapshot
+}
+
+void Session::snapshot_clear() {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.m->eng_->device()));
+  hipStream_t st = s.m->stream_;
+  const uint64_t V = s.nV;
+  RM_HIP(hipMemsetAsync(s.off, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.cnt, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.max_sep, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.last_update, 0, V * 8, st));
+  hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, s.nV, s.scan_from, 1u);
+  hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, s.nV, s.try_from, 1u);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipStreamSynchronize(st));
+  s.extent = 0;
+  s.n_win = s.n_rep = 0;
+}
+
+SessionSnap Session::snap_view(uint64_t n_points, uint32_t n_live) {
+  Impl& s = *p_;
+  SessionSnap v;
+  v.n_vehicles = s.nV; v.n_live = n_live; v.n_points = n_points;
+  v.off = s.off; v.cnt = s.cnt; v.scan_from = s.scan_from; v.try_from = s.try_from; v.max_sep = s.max_sep;
+  v.last_update = s.last_update; v.rank = s.noff;
+  const PtBuf& b = s.buf[s.cur];
+  v.lon = b.lon; v.lat = b.lat; v.acc = b.acc; v.time = b.time; v.arr = b.arr; v.veh = b.veh;
+  v.stream = s.m->stream_;
+  return v;
 }
 
 }  // namespace rm

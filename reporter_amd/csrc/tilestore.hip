@@ -478,6 +478,24 @@ uint64_t TileStore::rows_held() const { return p_->n_rows; }
 uint64_t TileStore::capacity() const { return p_->cap; }
 void TileStore::times(double ms[6]) const { for (int i = 0; i < 6; ++i) ms[i] = p_->ms[i]; }
 
+// the stream snapshot's access (DESIGN.md §3 rule 15)
+const void* TileStore::rows_device() const { return p_->rows; }
+uint64_t TileStore::arrivals() const { return p_->arrivals; }
+uint32_t TileStore::quantisation() const { return p_->tp.quantisation; }
+hipStream_t TileStore::stream() const { return p_->st; }
+void* TileStore::snapshot_room(uint64_t n_rows) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  if (s.n_rows) throw std::runtime_error("snapshot: the tile store is not empty");
+  if (n_rows >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
+  s.ensure_rows(n_rows);
+  return s.rows;
+}
+void TileStore::snapshot_loaded(uint64_t n_rows, uint64_t arrivals) {
+  p_->n_rows = n_rows;
+  p_->arrivals = arrivals;
+}
+
 void TileStore::add(const TileSegment* segs, uint64_t n, uint64_t out[4]) {
   Impl& s = *p_;
   if (n && !segs) throw std::runtime_error("tile segments are NULL");

@@ -950,6 +950,65 @@ class TileStore:
         return dict(zip(("upload", "expand", "sort", "cull", "text", "download"), (float(x) for x in t)))
 
 
+SNAPSHOT_COUNTS = ("bytes", "names", "vehicles", "points", "rows", "user_bytes")
+SNAPSHOT_INFO = ("version", "bytes", "names", "vehicles", "points", "rows", "quantisation", "user_offset", "user_bytes")
+
+
+def _snapshot_handle(obj, what):
+    """None stays None (the section is left out or skipped); a closed object raises."""
+    if obj is None:
+        return None
+    if not getattr(obj, "_h", None):
+        raise _lib.RmError("%s is closed" % what)
+    return obj._h
+
+
+def save_stream(sessions=None, directory=None, store=None, user=b""):
+    """The state of a stream as one blob (rm_snapshot_save; DESIGN.md §3 rule 15): the sessions' open
+    point lists, the directory's names and the tile store's rows, any of them left out when None,
+    with `user` bytes carried opaque.  Changes nothing the stream will output."""
+    blob = C.c_void_p()
+    n = C.c_size_t()
+    out = (C.c_uint64 * 6)()
+    ms = (C.c_double * 6)()
+    user = bytes(user)
+    handles = (_snapshot_handle(sessions, "sessions"), _snapshot_handle(directory, "directory"), _snapshot_handle(store, "store"))
+    _lib.check(_lib.lib().rm_snapshot_save(*handles, user, len(user), C.byref(blob), C.byref(n), out, ms))
+    try:
+        raw = C.string_at(blob.value, n.value)
+    finally:
+        _lib.lib().rm_free(blob)
+    save_stream.last = dict(zip(SNAPSHOT_COUNTS, (int(x) for x in out)),
+                            ms=dict(zip(("pack", "gather", "checksum", "download"), (float(x) for x in ms))))
+    return raw
+
+
+def load_stream(blob, sessions=None, directory=None, store=None):
+    """Restore save_stream's blob into empty objects (rm_snapshot_load); a None object's section is
+    skipped.  Returns the counts (SNAPSHOT_COUNTS) and the device ms of upload, check and unpack.  A
+    load that raises leaves the objects empty and usable."""
+    blob = bytes(blob)
+    out = (C.c_uint64 * 6)()
+    ms = (C.c_double * 6)()
+    handles = (_snapshot_handle(sessions, "sessions"), _snapshot_handle(directory, "directory"), _snapshot_handle(store, "store"))
+    _lib.check(_lib.lib().rm_snapshot_load(*handles, blob, len(blob), out, ms))
+    return dict(zip(SNAPSHOT_COUNTS, (int(x) for x in out)),
+                ms=dict(zip(("upload", "check", "unpack"), (float(x) for x in ms))))
+
+
+def snapshot_info(blob):
+    """Check a snapshot on the host alone (rm_snapshot_check_host: header, table, checksums and the
+    structural rule) and return its numbers (SNAPSHOT_INFO) and its user bytes; raises with the reason."""
+    blob = bytes(blob)
+    info = (C.c_uint64 * 9)()
+    err = C.create_string_buffer(512)
+    if _lib.lib().rm_snapshot_check_host(blob, len(blob), info, err, 512) != 0:
+        raise _lib.RmError(err.value.decode("utf-8", "replace"))
+    d = dict(zip(SNAPSHOT_INFO, (int(x) for x in info)))
+    d["user"] = blob[d["user_offset"]:d["user_offset"] + d["user_bytes"]]
+    return d
+
+
 def split_by_points(trace_off, parts):
     """Trace index cuts [0, ..., T] of `parts` contiguous ranges with about equal point counts
     (a cut where the running point count crosses k * P / parts); empty ranges are dropped."""

@@ -10,6 +10,12 @@ forwarded reports join the tile store device to device.  Stream time is the mess
 it has advanced --flush-interval seconds past the last flush the tile store is flushed, and once at
 the end, after a punctuate that evicts every vehicle.  Tiles are written under --output-location as
 reporter_amd.batch writes them; a tile flushed again later gets the suffix ".<flush number>".
+
+With --checkpoint FILE the stream's state (sessions, directory, tile store: DESIGN.md §3 rule 15) and
+its position in the input are written to FILE after every tile flush and at a stop;
+--stop-after-polls N stops after N polls without the final punctuate and flush (the file-fed
+counterpart of Reporter.java --duration), and --resume continues from FILE, writing what the
+stream that never stopped would have written.
 """
 import argparse
 import json
@@ -18,17 +24,34 @@ import os
 import sys
 
 
-def polls(paths, poll_bytes):
-    """The files' bytes in order, cut behind line ends into pieces of about poll_bytes."""
-    for p in paths:
-        with open(p, "rb") as f:
+def polls_from(paths, poll_bytes, first=0, offset=0):
+    """polls() from byte `offset` of file `first` on, each piece with the position behind it:
+    (text, file index, byte offset) of the next poll."""
+    for k in range(first, len(paths)):
+        with open(paths[k], "rb") as f:
             data = f.read()
-        at = 0
+        at = offset if k == first else 0
         while at < len(data):
             end = len(data) if len(data) - at <= poll_bytes else data.find(b"\n", at + poll_bytes - 1) + 1
             end = end if end > 0 else len(data)
-            yield data[at:end]
+            yield (data[at:end],) + ((k, end) if end < len(data) else (k + 1, 0))
             at = end
+
+
+def polls(paths, poll_bytes):
+    """The files' bytes in order, cut behind line ends into pieces of about poll_bytes."""
+    for text, _, _ in polls_from(paths, poll_bytes):
+        yield text
+
+
+def write_checkpoint(path, blob):
+    """Replace `path` by `blob` so that a reader sees the old file or the new one, never a part."""
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    with open(tmp, "wb") as f:
+        f.write(blob)
+        f.flush()
+        os.fsync(f.fileno())
+    os.replace(tmp, path)
 
 
 def write_flush(files, dest, k):
@@ -44,7 +67,7 @@ def write_flush(files, dest, k):
 
 def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transition_levels=(0, 1), privacy=2,
         quantisation=3600, flush_interval=300, source="smpl_rprt", max_vehicles=1 << 16, poll_bytes=1 << 20, device=0,
-        report_dist_m=None, report_count=None, report_time_s=None):
+        report_dist_m=None, report_count=None, report_time_s=None, checkpoint=None, stop_after_polls=None, resume=False):
     from . import engine
     from .batch import options_from_config
     opts, graph = options_from_config(conf, mode)
@@ -61,13 +84,31 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
     store = engine.TileStore(device, quantisation, privacy, source, mode)
     stats = dict(polls=0, messages=0, dropped=0, forwarded=0, flushes=0, files=0)
     last_flush = now = None
+    inputs = [[os.path.abspath(p), os.path.getsize(p)] for p in paths]
+    pos = [0, 0]   # file index and byte offset of the next poll
     try:
+        if resume:
+            with open(checkpoint, "rb") as f:
+                blob = f.read()
+            user = json.loads(engine.snapshot_info(blob)["user"].decode())
+            if user["inputs"] != inputs:
+                raise ValueError("the checkpoint was written for other inputs (their list or sizes differ)")
+            if user.get("done"):   # written behind the final flush: nothing is left to do
+                return user["stats"]
+            engine.load_stream(blob, sess, vdir, store)
+            pos, now, last_flush, stats = [user["file"], user["offset"]], user["now"], user["last_flush"], user["stats"]
+
+        def save(done=False):
+            user = dict(inputs=inputs, file=pos[0], offset=pos[1], now=now, last_flush=last_flush, stats=stats, done=done)
+            write_checkpoint(checkpoint, engine.save_stream(sess, vdir, store, json.dumps(user).encode()))
+
         def flush():
             files, _ = store.flush()
             stats["files"] += write_flush(files, dest, stats["flushes"])
             stats["flushes"] += 1
 
-        for text in polls(paths, poll_bytes):
+        polled = 0
+        for text, pos[0], pos[1] in polls_from(paths, poll_bytes, pos[0], pos[1]):
             out, info = sess.push_messages([text], fmt, vdir)
             store.add_session(sess)
             stats["polls"] += 1
@@ -77,19 +118,31 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
             for c, ln, why in sess.dropped_messages():
                 logging.warning("poll %d line %d dropped: %s", stats["polls"], ln, why)
             span = sess.messages_span()
-            if span is None:
-                continue
-            now = span[1] if now is None else max(now, span[1])
-            last_flush = span[0] if last_flush is None else last_flush
-            if now - last_flush >= flush_interval:
-                flush()
-                last_flush = now
+            if span is not None:
+                now = span[1] if now is None else max(now, span[1])
+                last_flush = span[0] if last_flush is None else last_flush
+                if now - last_flush >= flush_interval:
+                    flush()
+                    last_flush = now
+                    if checkpoint:
+                        save()
+            polled += 1
+            if stop_after_polls is not None and polled >= stop_after_polls:
+                break
+        else:
+            stop_after_polls = None   # the input ended first: finish as ever
+        if stop_after_polls is not None:
+            save()
+            stats["stopped"] = True
+            return stats
         if now is not None:
             out = sess.punctuate(int(now * 1000) + 10 ** 7)   # every vehicle is stale: all report and leave
             store.add_session(sess)
             stats["forwarded"] += out["forwarded"]
         flush()
         stats["vehicles"] = vdir.size
+        if checkpoint:
+            save(done=True)
         return stats
     finally:
         store.close()
@@ -118,7 +171,13 @@ def main(argv=None):
     ap.add_argument("--report-dist", type=float, help="session trigger distance in metres (default 500)")
     ap.add_argument("--report-count", type=int, help="session trigger point count (default 10)")
     ap.add_argument("--report-time", type=float, help="session trigger time in seconds (default 60)")
+    ap.add_argument("--checkpoint", help="a file for the stream's state, written after every tile flush and at a stop")
+    ap.add_argument("--stop-after-polls", type=int, help="stop after this many polls, without the final punctuate and "
+                    "flush, leaving the checkpoint to --resume from")
+    ap.add_argument("--resume", action="store_true", help="continue from --checkpoint")
     a = ap.parse_args(argv)
+    if (a.resume or a.stop_after_polls is not None) and not a.checkpoint:
+        ap.error("--resume and --stop-after-polls need --checkpoint")
     paths = []
     for p in a.inputs:
         if os.path.isdir(p):
@@ -129,7 +188,8 @@ def main(argv=None):
     levels = lambda s: tuple(int(x) for x in s.split(",") if x != "")
     stats = run(paths, a.match_config, a.output_location, a.formatter, a.mode, levels(a.reports), levels(a.transitions),
                 a.privacy, a.quantisation, a.flush_interval, a.source, a.max_vehicles, a.poll_bytes,
-                int(os.environ.get("LOCAL_RANK", "0")), a.report_dist, a.report_count, a.report_time)
+                int(os.environ.get("LOCAL_RANK", "0")), a.report_dist, a.report_count, a.report_time, a.checkpoint,
+                a.stop_after_polls, a.resume)
     print(json.dumps(stats))
     return 0
 

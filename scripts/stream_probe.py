@@ -11,7 +11,16 @@ rm_session_messages_time's.  Route (b) is what the same bytes took before: Batch
 the download of the points and the names, a Python dictionary from name to persistent index, then
 VehicleSessions.push with host arrays.  (b) reads separated values only: there was no such route
 for JSON text, so JSON is timed by (a) alone.  The routes alternate --runs times in one process
-after a warm-up push of each.  Prints one JSON line and writes it to --out."""
+after a warm-up push of each.  Prints one JSON line and writes it to --out.
+
+    python scripts/stream_probe.py --snapshot-at 5 [--out profiles/snapshot/snapshot_probe.json]
+
+instead measures the stream snapshot (rule 15) on the separated-value messages: the whole topology
+(directory, sessions, tile store) runs unbroken, then again with a save after push K, new objects, a
+load, and the remaining pushes; the outputs of the pushes behind K and the hash of the flushed files
+must equal the unbroken run's.  Reported: the blob's bytes per section, the save and load parts (HIP
+events, after one warm-up save and load), the checksum kernel's bytes/s, and beside them the only
+read-out there was before, VehicleSessions.store() plus VehicleDirectory.names() on the same state."""
 import argparse
 import json
 import os
@@ -90,14 +99,93 @@ def route_b(bm, texts, n_vehicles):
                 sum_ms=dict(zip(cols, p.sum(axis=0).round(2).tolist())), push_columns=[c + "_ms" for c in cols], pushes=pushes)
 
 
+SECTION_NAMES = {1: "user", 2: "name_offsets", 3: "name_bytes", 4: "session_records", 5: "lon", 6: "lat", 7: "accuracy",
+                 8: "time", 9: "tile_rows", 10: "tile_numbers"}
+
+
+def snapshot_probe(bm, texts, fmt, n_vehicles, at):
+    import hashlib
+    import struct
+    digest = lambda *xs: hashlib.sha256(b"".join(xs)).hexdigest()
+    make = lambda: (engine.VehicleSessions(bm, n_vehicles), engine.VehicleDirectory(n_vehicles), engine.TileStore(0))
+
+    def pushes(objs, first, last):
+        out = []
+        for text in texts[first:last]:
+            objs[0].push_messages([text], fmt, objs[1])
+            objs[2].add_session(objs[0])
+            out.append(digest(objs[0].windows().tobytes(), objs[0].reports().tobytes()))
+        return out
+
+    def finish(objs):
+        files, counts = objs[2].flush()
+        names = digest(*(n.encode() for n in objs[1].names()))
+        for o in reversed(objs):
+            o.close()
+        return digest(*(k.encode() + b"\0" + v for k, v in files.items())), counts, names
+
+    objs = make()
+    want = pushes(objs, 0, len(texts))
+    want_end = finish(objs)
+    print("unbroken run done", file=sys.stderr, flush=True)
+    objs = make()
+    head = pushes(objs, 0, at)
+    scratch = make()                      # one warm-up save and load
+    engine.load_stream(engine.save_stream(*objs), *scratch)
+    for o in reversed(scratch):
+        o.close()
+    save_runs, load_runs = [], []
+    for _ in range(5):                    # a save changes nothing: the same state, five times
+        t0 = time.perf_counter()
+        blob = engine.save_stream(*objs, user=b"stream_probe")
+        save_runs.append(dict(engine.save_stream.last["ms"], wall=(time.perf_counter() - t0) * 1e3))
+    saved = dict(engine.save_stream.last)
+    for _ in range(4):                    # ... and four loads into objects made for it, before the one that goes on
+        scratch = make()
+        t0 = time.perf_counter()
+        got = engine.load_stream(blob, *scratch)
+        load_runs.append(dict(got["ms"], wall=(time.perf_counter() - t0) * 1e3))
+        for o in reversed(scratch):
+            o.close()
+    t0 = time.perf_counter()              # what there was before: two read-outs, no restore, no tile rows
+    st = objs[0].store()
+    t1 = time.perf_counter()
+    names = objs[1].names()
+    t2 = time.perf_counter()
+    for o in reversed(objs):
+        o.close()
+    objs = make()
+    t3 = time.perf_counter()
+    loaded = engine.load_stream(blob, *objs)
+    load_runs.append(dict(loaded["ms"], wall=(time.perf_counter() - t3) * 1e3))
+    tail = pushes(objs, at, len(texts))
+    end = finish(objs)
+    n_sec = struct.unpack_from("<I", blob, 12)[0]
+    sections = {}
+    for k in range(n_sec):
+        kind, _, _, nbytes, _, _ = struct.unpack_from("<IIQQQQ", blob, 32 + 40 * k)
+        sections[SECTION_NAMES.get(kind, str(kind))] = nbytes
+    summed = sum(sections.values())
+    return dict(snapshot_at=at, pushes=len(texts), outputs_equal=head + tail == want, flush_equal=end == want_end,
+                flush_sha256=end[0], flush_counts=end[1], blob_bytes=len(blob), section_bytes=sections,
+                counts={k: v for k, v in saved.items() if k != "ms"}, save_ms_runs=save_runs, load_ms_runs=load_runs,
+                checksum_bytes_per_s=[summed / (r["checksum"] * 1e-3) if r["checksum"] > 0 else None for r in save_runs],
+                peak_bytes_per_s=8e12,
+                before=dict(store_wall_ms=(t1 - t0) * 1e3, names_wall_ms=(t2 - t1) * 1e3, points=len(st["lon"]), names=len(names),
+                            note="VehicleSessions.store() + VehicleDirectory.names(): read-outs only, no tile rows, nothing loads them"))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, default=10000)
     ap.add_argument("--points", type=int, default=600)
     ap.add_argument("--per-push", type=int, default=60)
     ap.add_argument("--runs", type=int, default=4)
-    ap.add_argument("--out", default=os.path.join("profiles", "stream", "stream_probe.json"))
+    ap.add_argument("--snapshot-at", type=int, help="measure the stream snapshot: save after this push, load, finish")
+    ap.add_argument("--out")
     a = ap.parse_args()
+    a.out = a.out or (os.path.join("profiles", "snapshot", "snapshot_probe.json") if a.snapshot_at is not None
+                      else os.path.join("profiles", "stream", "stream_probe.json"))
     cfg = world.CONFIGS["C2"]
     tmp = tempfile.mkdtemp(prefix="stream_probe")
     graph = os.path.join(tmp, "c2.rmg")
@@ -111,10 +199,23 @@ def main():
         arr[f] = np.ascontiguousarray(tr[f][order])
     per = a.per_push * T
     cuts = [(s, min(s + per, T * n)) for s in range(0, T * n, per)]
-    texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in (0, 1)}
+    texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in ((0,) if a.snapshot_at is not None else (0, 1))}
     fmt = {0: engine.MessageFormat(0), 1: engine.MessageFormat(1)}
     eng = engine.Engine(graph, 0)
     bm = engine.BatchMatcher(eng)
+    if a.snapshot_at is not None:
+        print("text written", file=sys.stderr, flush=True)
+        route_a(bm, texts[0][:2], fmt[0], T)   # warm the route
+        out = dict(args=dict(vehicles=a.vehicles, points=a.points, per_push=a.per_push, snapshot_at=a.snapshot_at),
+                   messages_per_push=per, **snapshot_probe(bm, texts[0], fmt[0], T, a.snapshot_at))
+        line = json.dumps(out)
+        print(line)
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+        bm.close()
+        eng.close()
+        return
     # warm every route (route tables, workspaces, the readers' buffers)
     route_a(bm, texts[0][:2], fmt[0], T)
     route_a(bm, texts[1][:2], fmt[1], T)

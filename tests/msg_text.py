@@ -35,6 +35,12 @@ def _civil(t):
     return "%04d-%02d-%02d %02d:%02d:%02d" % _time.gmtime(int(t))[:6]
 
 
+def _with_exponent(s):
+    """A spelling with an exponent: its own if it has one (near 0 degrees the shortest spelling of
+    a float32 is already 4.2e-05), else "e0" appended."""
+    return s if "e" in s else s + "e0"
+
+
 def message(arr, j, kind, odd):
     v, t = int(arr["vehicle"][j]), arr["time"][j]
     assert t == int(t)
@@ -42,11 +48,11 @@ def message(arr, j, kind, odd):
     acc = str(np.float32(arr["accuracy"][j]))   # (read back as its ceiling: expected())
     if kind == 0:
         if odd:
-            return " %s , %d,%se0,\t%s,%s \r" % (name(v), int(t), lat, lon, acc)
+            return " %s , %d,%s,\t%s,%s \r" % (name(v), int(t), _with_exponent(lat), lon, acc)
         return "%s,%d,%s,%s,%s" % (name(v), int(t), lat, lon, acc)
     if odd:
-        return ' {"nest":{"uuid":["x",{"la":"}"}]}, "lo" : %se0 , "acc":"%s","when":"%s", "uuid":"%s","la":%s}\t' % (
-            lon, acc, _civil(t), name(v), lat)
+        return ' {"nest":{"uuid":["x",{"la":"}"}]}, "lo" : %s , "acc":"%s","when":"%s", "uuid":"%s","la":%s}\t' % (
+            _with_exponent(lon), acc, _civil(t), name(v), lat)
     return '{"uuid":"%s","when":"%s","la":%s,"lo":%s,"acc":%s,"speed":12.5}' % (name(v), _civil(t), lat, lon, acc)
 
 

@@ -29,11 +29,15 @@ def _outputs(bm):
 
 @pytest.fixture(scope="module")
 def stream_case(small_world, tmp_path_factory):
-    """_stream's 40 vehicles as text in three chunks, and what today's path makes of that text."""
-    lines = _text_lines(_stream(small_world))
+    return make_stream_case(small_world, tmp_path_factory.mktemp("lines"))
+
+
+def make_stream_case(path, d):
+    """_stream's 40 vehicles on the graph at `path` as text in three chunks (files in directory d), and
+    what today's path makes of that text."""
+    lines = _text_lines(_stream(path))
     a, b = len(lines) // 3, 2 * len(lines) // 3
     chunks = ["".join(lines[:a]).encode(), "".join(lines[a:b]).encode(), "".join(lines[b:]).encode().rstrip(b"\n")]
-    d = tmp_path_factory.mktemp("lines")
     paths = []
     for k, c in enumerate(chunks):
         p = d / ("%03d" % k)
@@ -41,7 +45,7 @@ def stream_case(small_world, tmp_path_factory):
         paths.append(str(p))
     uuids, pts = batch.read_trace_files(paths)
     idx, names = batch.dense_ids(uuids)
-    eng = engine.Engine(small_world, 0)
+    eng = engine.Engine(path, 0)
     bm = engine.BatchMatcher(eng)
     bm.run_points(idx, pts["time"], pts["lon"], pts["lat"], pts["accuracy"], inactivity=120, n_uuids=len(names))
     want = _outputs(bm)
@@ -57,8 +61,11 @@ def _same_points(got, ref):
 
 
 def test_run_lines_equals_run_points(small_world, stream_case):
-    c = stream_case
-    eng = engine.Engine(small_world, 0)
+    run_lines_equals_run_points(small_world, stream_case)
+
+
+def run_lines_equals_run_points(path, c):
+    eng = engine.Engine(path, 0)
     bm = engine.BatchMatcher(eng)
     bm.run_lines(c["chunks"], inactivity=120)
     info = bm.lines_info()

@@ -228,6 +228,30 @@ def test_turn_costs(built_lib, small_world):
     run_and_compare(small_world, tr, engine.default_options(1, turn_penalty_factor=200.0), what="turn costs")
 
 
+def check_reply(text, plain, rec, lon, lat, elen):
+    """One MatchPoints reply against Match's reply for the request and the trace's records (its
+    input lon / lat, the graph's edge lengths); returns the reply's matched_points."""
+    names = {mp.UNMATCHED: "unmatched", mp.MATCHED: "matched", mp.INTERPOLATED: "interpolated"}
+    assert text.startswith(plain[:-1] + ',"matched_points":[')    # the segments, string for string
+    rep = json.loads(text)
+    assert set(rep) == {"segments", "matched_points"} and rep["segments"] == json.loads(plain)["segments"]
+    pts = rep["matched_points"]
+    assert len(pts) == len(rec)
+    for q, p in enumerate(pts):
+        r = rec[q]
+        assert p["type"] == names[int(r["type"])], q
+        if r["type"] == mp.UNMATCHED:
+            assert set(p) == {"lat", "lon", "type"}
+            assert np.float32(p["lat"]) == np.float32(lat[q]) and np.float32(p["lon"]) == np.float32(lon[q])
+            continue
+        assert set(p) == {"lat", "lon", "type", "edge_id", "way_id", "distance_along_edge", "distance_from_trace_point"}
+        assert p["edge_id"] == int(r["edge"]) and p["way_id"] == int(r["way"])
+        assert np.float32(p["lat"]) == r["lat"] and np.float32(p["lon"]) == r["lon"]
+        assert p["distance_along_edge"] == pytest.approx(int(r["off_cm"]) / int(elen[r["edge"]]), rel=1e-6)
+        assert p["distance_from_trace_point"] == pytest.approx(math.sqrt(float(r["sq"])), rel=1e-6)
+    return pts
+
+
 def test_json_replies(built_lib, small_world, tmp_path):
     """7. MatchPoints: one entry per input point, types and edges of the array API, the two
     distances as the records give them, and Match's segments string for string."""
@@ -247,27 +271,9 @@ def test_json_replies(built_lib, small_world, tmp_path):
     sm = valhalla.SegmentMatcher()
     reqs = [json.dumps(world.trace_to_request(tr, k), separators=(",", ":")) for k in range(3)]
     outs = [sm.MatchPoints(reqs[0])] + sm.MatchPointsMany(reqs[1:])
-    names = {mp.UNMATCHED: "unmatched", mp.MATCHED: "matched", mp.INTERPOLATED: "interpolated"}
     for k in range(3):
-        plain = sm.Match(reqs[k])
-        assert outs[k].startswith(plain[:-1] + ',"matched_points":['), k    # the segments, string for string
-        rep = json.loads(outs[k])
-        assert set(rep) == {"segments", "matched_points"} and rep["segments"] == json.loads(plain)["segments"]
-        pts = rep["matched_points"]
         o = int(tr["trace_off"][k])
-        assert len(pts) == 60
-        for q, p in enumerate(pts):
-            r = rec[o + q]
-            assert p["type"] == names[int(r["type"])], (k, q)
-            if r["type"] == mp.UNMATCHED:
-                assert set(p) == {"lat", "lon", "type"}
-                assert np.float32(p["lat"]) == np.float32(tr["lat"][o + q]) and np.float32(p["lon"]) == np.float32(tr["lon"][o + q])
-                continue
-            assert set(p) == {"lat", "lon", "type", "edge_id", "way_id", "distance_along_edge", "distance_from_trace_point"}
-            assert p["edge_id"] == int(r["edge"]) and p["way_id"] == int(r["way"])
-            assert np.float32(p["lat"]) == r["lat"] and np.float32(p["lon"]) == r["lon"]
-            assert p["distance_along_edge"] == pytest.approx(int(r["off_cm"]) / int(elen[r["edge"]]), rel=1e-6)
-            assert p["distance_from_trace_point"] == pytest.approx(math.sqrt(float(r["sq"])), rel=1e-6)
+        pts = check_reply(outs[k], sm.Match(reqs[k]), rec[o:o + 60], tr["lon"][o:o + 60], tr["lat"][o:o + 60], elen)
         assert sum(p["type"] == "interpolated" for p in pts) > 10
     sm.close()
 

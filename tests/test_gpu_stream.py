@@ -31,10 +31,11 @@ Q = 60
 SPEC = {0: "@sv@,@0@2@3@1@4", 1: "@json@uuid@la@lo@when@acc@yyyy-MM-dd HH:mm:ss"}
 
 
-@pytest.fixture(scope="module")
-def ctx(built_lib, small_world):
-    g = graphfile.load(small_world)
-    tr = world.generate_traces(small_world, n_traces=32, n_points=400, rate_s=1.0, noise_m=5.0, seed=11)
+def make_ctx(path, tr, n_vehicles):
+    """The inputs of the end-to-end run on the graph at `path`: the traces' arrivals, what their text
+    reads back to per kind (host reader, directory model), the session and anonymiser models' reports,
+    and an engine with a runner (close_ctx closes them)."""
+    g = graphfile.load(path)
     arr = sr.interleave(tr)
     fmt = msg_text.formats(engine)
     # what the messages read back to, by the host reader and the directory model, per kind
@@ -43,27 +44,38 @@ def ctx(built_lib, small_world):
         text = msg_text.text(arr, kind)
         host = engine.parse_messages_host([text], fmt[kind], strict=True)
         ref = messages_ref.parse([text], fmt[kind])
-        host["vehicle"] = messages_ref.Directory(32).assign(ref["point_names"])
+        host["vehicle"] = messages_ref.Directory(n_vehicles).assign(ref["point_names"])
         host["stamp_ms"] = (host["time"] * 1000.0).astype(np.int64)
         pts[kind] = host
     ts = int(arr["time"].max() * 1000) + 10 ** 7
     p = pts[0]
-    model = sr.Sessions(32, sr.oracle_matcher(g, engine.default_options(1)), **B_PARAMS)
+    model = sr.Sessions(n_vehicles, sr.oracle_matcher(g, engine.default_options(1)), **B_PARAMS)
     model.push(p["vehicle"], p["time"], p["lon"], p["lat"], p["accuracy"], p["stamp_ms"])
     n_push, n_win_push = len(model.reports), len(model.windows)
     model.punctuate(ts)
     segs = [(int(r["id"]), int(r["next_id"]), float(r["t0"]), float(r["t1"]), int(r["length"]), int(r["queue_length"]))
             for r, _, _ in model.reports]
-    eng = engine.Engine(small_world, 0)
+    eng = engine.Engine(path, 0)
     bm = engine.BatchMatcher(eng)
-    yield {"arr": arr, "fmt": fmt, "pts": pts, "ts": ts, "model": model, "n_push": n_push, "n_win_push": n_win_push,
-           "segs": segs, "eng": eng, "bm": bm, "path": small_world}
-    bm.close()
-    eng.close()
+    return {"arr": arr, "fmt": fmt, "pts": pts, "ts": ts, "model": model, "n_push": n_push, "n_win_push": n_win_push,
+            "segs": segs, "eng": eng, "bm": bm, "path": path, "n": n_vehicles}
+
+
+def close_ctx(ctx):
+    ctx["bm"].close()
+    ctx["eng"].close()
+
+
+@pytest.fixture(scope="module")
+def ctx(built_lib, small_world):
+    tr = world.generate_traces(small_world, n_traces=32, n_points=400, rate_s=1.0, noise_m=5.0, seed=11)
+    c = make_ctx(small_world, tr, 32)
+    yield c
+    close_ctx(c)
 
 
 def _session(ctx):
-    return engine.VehicleSessions(ctx["bm"], 32, report_dist_m=B_PARAMS["dist"], report_count=B_PARAMS["count"],
+    return engine.VehicleSessions(ctx["bm"], ctx["n"], report_dist_m=B_PARAMS["dist"], report_count=B_PARAMS["count"],
                                   report_time_s=B_PARAMS["time_s"])
 
 
@@ -82,6 +94,13 @@ def test_inputs_are_not_vacuous(ctx):
 @pytest.mark.parametrize("gran", ["20s", "one_push"])
 @pytest.mark.parametrize("kind", [0, 1])
 def test_messages_to_tiles(ctx, kind, gran, privacy):
+    assert messages_to_tiles(ctx, kind, gran, privacy) == (80, 8)
+
+
+def messages_to_tiles(ctx, kind, gran, privacy):
+    """Messages -> directory -> sessions -> tile store -> CSV on the GPU against push() fed the host
+    reader's arrays, the session model and the anonymiser model; returns the reports forwarded by the
+    pushes and by the final punctuate."""
     arr, pts, fmt = ctx["arr"], ctx["pts"][kind], ctx["fmt"][kind]
     cuts = sr.slices(arr, {"20s": 20.0, "one_push": None}[gran])
     # the yardstick: push() fed the host reader's arrays and the model's indices
@@ -96,7 +115,7 @@ def test_messages_to_tiles(ctx, kind, gran, privacy):
     plain.close()
     # the new route
     sess = _session(ctx)
-    vdir = engine.VehicleDirectory(32)
+    vdir = engine.VehicleDirectory(ctx["n"])
     store = engine.TileStore(0, Q, privacy, initial_rows=32)
     got = []
     for a, b in cuts:
@@ -124,7 +143,8 @@ def test_messages_to_tiles(ctx, kind, gran, privacy):
         reps.append(gr)
     assert np.concatenate(wins).tobytes() == model.window_array().tobytes()
     assert np.concatenate(reps).tobytes() == model.report_array().tobytes()
-    assert sum(len(r) for _, r in got[:-1]) == 80 and len(got[-1][1]) == 8
+    pushed, punctuated = sum(len(r) for _, r in got[:-1]), len(got[-1][1])
+    assert pushed == ctx["n_push"] and pushed + punctuated == len(ctx["segs"])
     # the flushed files are the anonymiser model's
     anon = ar.Anonymiser(Q, privacy)
     anon.add(ctx["segs"])
@@ -135,6 +155,7 @@ def test_messages_to_tiles(ctx, kind, gran, privacy):
     store.close()
     vdir.close()
     sess.close()
+    return pushed, punctuated
 
 
 @pytest.mark.parametrize("kind", [0, 1])

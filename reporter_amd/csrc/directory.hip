@@ -41,15 +41,8 @@ struct DirTable {
   uint8_t* arena;
 };
 
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)std::max<uint64_t>((n + b - 1) / b, 1); }
-
 __device__ __forceinline__ uint32_t dir_slot(unsigned long long h, uint32_t mask) {
   return (uint32_t)(((h ^ (h >> 29)) * 0x9e3779b97f4a7c15ull) >> 32) & mask;
-}
-
-__global__ void k_dir_fill(uint32_t n, uint32_t* v, uint32_t x) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) v[k] = x;
 }
 
 // per group: the masked hash, the vehicle found (kDirEmpty: new), and the scans' inputs (entry G
@@ -169,107 +162,64 @@ __global__ void k_dir_snap_verify(uint32_t n, const unsigned long long* off, uns
 struct Directory::Impl {
   int device = 0;
   uint32_t max_vehicles = 0, cap = 0, n_known = 0;
-  DirTable t{};
+  // the table and the arena of names
+  DevBuf<unsigned long long> hash;
+  DevBuf<uint32_t> veh, noff, nlen;
+  DevBuf<uint8_t> arena;
   uint64_t arena_cap = 0, arena_used = 0;
   // per call (grow-only): ghash, found, isnew, nbytes, rank, aoff, map
-  unsigned long long* ghash = nullptr;
-  uint32_t* w[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  DevBuf<unsigned long long> ghash;
+  DevBuf<uint32_t> w[6];
   uint32_t call_cap = 0;
-  void* tmp = nullptr;
-  size_t tmp_bytes = 0;
-  uint32_t* derr = nullptr;
-  uint32_t* hctl = nullptr;   // pinned read-back words
-  hipEvent_t ev[2] = {nullptr, nullptr};
+  ScanScratch scr;
+  DevBuf<uint32_t> derr;
+  PinBuf<uint32_t> hctl;   // pinned read-back words
+  PartTimer timer;
   double ms = 0.0;
 
-  void free_call() {
-    if (ghash) (void)hipFree(ghash);
-    for (uint32_t*& p : w) { if (p) (void)hipFree(p); p = nullptr; }
-    ghash = nullptr;
-    call_cap = 0;
-  }
+  DirTable table() const { return DirTable{hash, veh, noff, nlen, cap - 1u, arena}; }
   void ensure_call(uint32_t G) {
     if (G + 1u <= call_cap) return;
-    free_call();
+    call_cap = 0;
     const uint32_t c = G + G / 2u + 256u;
-    RM_HIP(hipMalloc((void**)&ghash, c * 8ull));
-    for (uint32_t*& p : w) RM_HIP(hipMalloc((void**)&p, c * 4ull));
+    ghash.reserve(c);
+    for (DevBuf<uint32_t>& p : w) p.reserve(c);
     call_cap = c;
   }
-  void ensure_arena(uint64_t n, hipStream_t st) {
+  // room for n name bytes, the names held moving by a device copy; a full HBM is reported as
+  // too_large where the caller names one (as the workspaces report it)
+  void ensure_arena(uint64_t n, hipStream_t st, const char* too_large = nullptr) {
     if (n <= arena_cap) return;
     const uint64_t c = std::max<uint64_t>(n + n / 2, 1u << 16);
-    uint8_t* a2 = nullptr;
-    RM_HIP(hipMalloc((void**)&a2, c));
-    if (arena_used) RM_HIP(hipMemcpyAsync(a2, t.arena, arena_used, hipMemcpyDeviceToDevice, st));
-    RM_HIP(hipStreamSynchronize(st));
-    if (t.arena) (void)hipFree(t.arena);
-    t.arena = a2;
+    arena.reserve(c, too_large, arena_used, st);
     arena_cap = c;
-  }
-  void scan(const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t st) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, st));
-    if (b > tmp_bytes || !tmp) {
-      if (tmp) { RM_HIP(hipStreamSynchronize(st)); (void)hipFree(tmp); tmp = nullptr; }
-      tmp_bytes = b + b / 2 + 256;
-      RM_HIP(hipMalloc(&tmp, tmp_bytes));
-    }
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, in, out, (int)n, st));
-  }
-  void release() {
-    free_call();
-    if (t.hash) (void)hipFree(t.hash);
-    if (t.veh) (void)hipFree(t.veh);
-    if (t.noff) (void)hipFree(t.noff);
-    if (t.nlen) (void)hipFree(t.nlen);
-    if (t.arena) (void)hipFree(t.arena);
-    if (tmp) (void)hipFree(tmp);
-    if (derr) (void)hipFree(derr);
-    if (hctl) (void)hipHostFree(hctl);
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
   }
 };
 
 Directory::Directory(int device, uint32_t max_vehicles) : p_(new Impl) {
   Impl& s = *p_;
-  try {
-    if (max_vehicles == 0 || max_vehicles >= 0x40000000u) throw std::runtime_error("directory needs 1 .. 2^30 - 1 vehicles");
-    s.device = device;
-    s.max_vehicles = max_vehicles;
-    RM_HIP(hipSetDevice(device));
-    uint32_t cap = 64;
-    while (cap < 2ull * max_vehicles) cap <<= 1;
-    s.cap = cap;
-    s.t.mask = cap - 1u;
-    RM_HIP(hipMalloc((void**)&s.t.hash, cap * 8ull));
-    RM_HIP(hipMalloc((void**)&s.t.veh, cap * 4ull));
-    RM_HIP(hipMalloc((void**)&s.t.noff, cap * 4ull));
-    RM_HIP(hipMalloc((void**)&s.t.nlen, cap * 4ull));
-    RM_HIP(hipMalloc((void**)&s.derr, 8));
-    RM_HIP(hipHostMalloc((void**)&s.hctl, 4 * sizeof(uint32_t), hipHostMallocDefault));
-    for (hipEvent_t& e : s.ev) RM_HIP(hipEventCreate(&e));
-    RM_HIP(hipMemset(s.t.hash, 0, cap * 8ull));
-    RM_HIP(hipMemset(s.t.noff, 0, cap * 4ull));
-    RM_HIP(hipMemset(s.t.nlen, 0, cap * 4ull));
-    RM_HIP(hipMemset(s.derr, 0, 8));
-    hipLaunchKernelGGL(k_dir_fill, dim3(grid(cap)), dim3(256), 0, nullptr, cap, s.t.veh, kDirEmpty);
-    RM_HIP(hipGetLastError());
-    RM_HIP(hipDeviceSynchronize());
-  } catch (...) {
-    s.release();
-    delete p_;
-    throw;
-  }
+  if (max_vehicles == 0 || max_vehicles >= 0x40000000u) throw std::runtime_error("directory needs 1 .. 2^30 - 1 vehicles");
+  s.device = device;
+  s.max_vehicles = max_vehicles;
+  RM_HIP(hipSetDevice(device));
+  uint32_t cap = 64;
+  while (cap < 2ull * max_vehicles) cap <<= 1;
+  s.cap = cap;
+  s.hash.reserve(cap); s.veh.reserve(cap); s.noff.reserve(cap); s.nlen.reserve(cap);
+  s.derr.reserve(2);
+  s.hctl.reserve(4);
+  RM_HIP(hipMemset(s.hash, 0, cap * 8ull));
+  RM_HIP(hipMemset(s.noff, 0, cap * 4ull));
+  RM_HIP(hipMemset(s.nlen, 0, cap * 4ull));
+  RM_HIP(hipMemset(s.derr, 0, 8));
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(cap)), dim3(256), 0, nullptr, cap, s.veh, kDirEmpty);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipDeviceSynchronize());
 }
 
 Directory::~Directory() {
   (void)hipSetDevice(p_->device);
   (void)hipDeviceSynchronize();
-  p_->release();
-  delete p_;
 }
 
 uint32_t Directory::size() const { return p_->n_known; }
@@ -283,20 +233,21 @@ void Directory::assign(Matcher& m) {
   RM_HIP(hipSetDevice(s.device));
   const LineGroups g = m.line_groups();
   s.ms = 0.0;
+  s.timer.harvest(nullptr);   // (a pair a call that threw left behind)
   const uint32_t G = g.n_groups;
   if (!g.n_points || !G) return;
   hipStream_t st = m.stream();
   s.ensure_call(G);
   uint32_t* found = s.w[0]; uint32_t* isnew = s.w[1]; uint32_t* nbytes = s.w[2];
   uint32_t* rank = s.w[3]; uint32_t* aoff = s.w[4]; uint32_t* map = s.w[5];
-  RM_HIP(hipEventRecord(s.ev[0], st));
+  s.timer.tic(0, st);
   RM_HIP(hipMemsetAsync(isnew + G, 0, 4, st));
   RM_HIP(hipMemsetAsync(nbytes + G, 0, 4, st));
-  hipLaunchKernelGGL(k_dir_lookup, dim3(grid(G)), dim3(256), 0, st, G, g.text, g.v_off, g.v_len, g.hash_mask, s.t, s.ghash, found,
+  hipLaunchKernelGGL(k_dir_lookup, dim3(grid(G)), dim3(256), 0, st, G, g.text, g.v_off, g.v_len, g.hash_mask, s.table(), s.ghash, found,
                      isnew, nbytes);
   RM_HIP(hipGetLastError());
-  s.scan(isnew, rank, G + 1u, st);
-  s.scan(nbytes, aoff, G + 1u, st);
+  s.scr.scan(isnew, rank, G + 1u, st);
+  s.scr.scan(nbytes, aoff, G + 1u, st);
   RM_HIP(hipMemcpyAsync(s.hctl + 0, rank + G, 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipMemcpyAsync(s.hctl + 1, aoff + G, 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
@@ -308,17 +259,16 @@ void Directory::assign(Matcher& m) {
   if (n_new) s.ensure_arena(s.arena_used + new_bytes, st);
   hipLaunchKernelGGL(k_dir_insert, dim3(grid(G)), dim3(256), 0, st, G, g.text, g.v_off, g.v_len, (const unsigned long long*)s.ghash,
                      (const uint32_t*)found, (const uint32_t*)rank, (const uint32_t*)aoff, s.n_known, s.max_vehicles,
-                     (uint32_t)s.arena_used, s.arena_cap, s.t, map, s.derr);
+                     (uint32_t)s.arena_used, s.arena_cap, s.table(), map, s.derr);
   hipLaunchKernelGGL(k_dir_scatter, dim3(grid(g.n_points)), dim3(256), 0, st, g.n_points, G, (const uint32_t*)map, g.p_uuid);
   RM_HIP(hipGetLastError());
   RM_HIP(hipMemcpyAsync(s.hctl + 2, s.derr, 4, hipMemcpyDeviceToHost, st));
-  RM_HIP(hipEventRecord(s.ev[1], st));
+  s.timer.toc(st);
   RM_HIP(hipStreamSynchronize(st));
   if (s.hctl[2]) throw std::runtime_error("directory: an insert found no room (the table and the host disagree)");
   s.n_known += n_new;
   s.arena_used += new_bytes;
-  float t = 0.f;
-  if (hipEventElapsedTime(&t, s.ev[0], s.ev[1]) == hipSuccess) s.ms = t;
+  s.timer.harvest(&s.ms);
 }
 
 uint64_t Directory::name_bytes() const { return p_->arena_used; }
@@ -326,9 +276,9 @@ uint64_t Directory::name_bytes() const { return p_->arena_used; }
 void Directory::snapshot_gather(unsigned long long* d_off, uint8_t* d_bytes, hipStream_t st) {
   Impl& s = *p_;
   RM_HIP(hipSetDevice(s.device));
-  hipLaunchKernelGGL(k_dir_snap_off, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.t, s.n_known, (unsigned long long)s.arena_used, d_off);
+  hipLaunchKernelGGL(k_dir_snap_off, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.table(), s.n_known, (unsigned long long)s.arena_used, d_off);
   RM_HIP(hipGetLastError());
-  if (s.arena_used) RM_HIP(hipMemcpyAsync(d_bytes, s.t.arena, s.arena_used, hipMemcpyDeviceToDevice, st));
+  if (s.arena_used) RM_HIP(hipMemcpyAsync(d_bytes, s.arena, s.arena_used, hipMemcpyDeviceToDevice, st));
 }
 
 void Directory::snapshot_insert(uint32_t n, const unsigned long long* d_off, const uint8_t* d_bytes, uint64_t n_bytes,
@@ -339,25 +289,12 @@ void Directory::snapshot_insert(uint32_t n, const unsigned long long* d_off, con
   if (n > s.max_vehicles) throw std::runtime_error("snapshot: more names than the directory's max_vehicles");
   if (n_bytes >= (1ull << 32)) throw std::runtime_error("directory names pass 2^32 bytes");
   if (!n) return;
-  if (n_bytes > s.arena_cap) {   // (ensure_arena, with a full HBM reported as the workspaces report it)
-    const uint64_t c = std::max<uint64_t>(n_bytes + n_bytes / 2, 1u << 16);
-    uint8_t* a2 = nullptr;
-    const hipError_t e = hipMalloc((void**)&a2, c);
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      throw BatchTooLarge("directory names do not fit in HBM");
-    }
-    RM_HIP(e);
-    RM_HIP(hipStreamSynchronize(st));
-    if (s.t.arena) (void)hipFree(s.t.arena);
-    s.t.arena = a2;
-    s.arena_cap = c;
-  }
-  if (n_bytes) RM_HIP(hipMemcpyAsync(s.t.arena, d_bytes, n_bytes, hipMemcpyDeviceToDevice, st));
+  s.ensure_arena(n_bytes, st, "directory names do not fit in HBM");   // (the directory is empty: nothing moves)
+  if (n_bytes) RM_HIP(hipMemcpyAsync(s.arena, d_bytes, n_bytes, hipMemcpyDeviceToDevice, st));
   const unsigned long long hmask = lines_hash_mask();
   RM_HIP(hipMemsetAsync(s.derr, 0, 4, st));
-  hipLaunchKernelGGL(k_dir_snap_insert, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.t, s.derr);
-  hipLaunchKernelGGL(k_dir_snap_verify, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.t, d_err, 1ull << dup_bit);
+  hipLaunchKernelGGL(k_dir_snap_insert, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.table(), s.derr);
+  hipLaunchKernelGGL(k_dir_snap_verify, dim3(grid(n)), dim3(256), 0, st, n, d_off, hmask, s.table(), d_err, 1ull << dup_bit);
   RM_HIP(hipGetLastError());
   RM_HIP(hipMemcpyAsync(s.hctl + 2, s.derr, 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
@@ -372,7 +309,7 @@ void Directory::snapshot_insert(uint32_t n, const unsigned long long* d_off, con
 void Directory::snapshot_clear(hipStream_t st) {
   Impl& s = *p_;
   RM_HIP(hipSetDevice(s.device));
-  hipLaunchKernelGGL(k_dir_fill, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.t.veh, kDirEmpty);
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(s.cap)), dim3(256), 0, st, s.cap, s.veh, kDirEmpty);
   RM_HIP(hipGetLastError());
   RM_HIP(hipMemsetAsync(s.derr, 0, 8, st));
   RM_HIP(hipStreamSynchronize(st));
@@ -386,9 +323,9 @@ uint64_t Directory::names(uint32_t first, uint32_t n, uint64_t* off, char* bytes
   RM_HIP(hipSetDevice(s.device));
   // the slots in vehicle order (a diagnostic path: the table comes to the host whole)
   std::vector<uint32_t> veh(s.cap), noff(s.cap), nlen(s.cap);
-  RM_HIP(hipMemcpy(veh.data(), s.t.veh, s.cap * 4ull, hipMemcpyDeviceToHost));
-  RM_HIP(hipMemcpy(noff.data(), s.t.noff, s.cap * 4ull, hipMemcpyDeviceToHost));
-  RM_HIP(hipMemcpy(nlen.data(), s.t.nlen, s.cap * 4ull, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(veh.data(), s.veh, s.cap * 4ull, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(noff.data(), s.noff, s.cap * 4ull, hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(nlen.data(), s.nlen, s.cap * 4ull, hipMemcpyDeviceToHost));
   std::vector<uint32_t> o(n, 0), l(n, 0);
   for (uint32_t k = 0; k < s.cap; ++k) {
     if (veh[k] == kDirEmpty || veh[k] < first || veh[k] >= first + n) continue;
@@ -404,7 +341,7 @@ uint64_t Directory::names(uint32_t first, uint32_t n, uint64_t* off, char* bytes
     total += l[v];
   }
   if (off) off[n] = total;
-  if (bytes && total) RM_HIP(hipMemcpy(bytes, s.t.arena + o[0], total, hipMemcpyDeviceToHost));
+  if (bytes && total) RM_HIP(hipMemcpy(bytes, s.arena + o[0], total, hipMemcpyDeviceToHost));
   return total;
 }
 

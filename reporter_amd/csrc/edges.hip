@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 
 #include "engine.hpp"
+#include "wave_util.hpp"
 
 namespace rm {
 
@@ -49,39 +50,6 @@ struct EdgeArgs {
   unsigned long long* tot;         // visits, shape vertices
   uint4* edges; float2* shape;     // the compacted records and the shapes
 };
-
-__device__ __forceinline__ int hi_le(unsigned long long m, int i) {   // highest set bit <= i, or -1
-  if (i < 0) return -1;
-  const unsigned long long mm = m & ((2ull << i) - 1ull);
-  return mm ? 63 - __builtin_clzll(mm) : -1;
-}
-__device__ __forceinline__ int lo_gt(unsigned long long m, int i) {   // lowest set bit > i, or 64
-  const unsigned long long mm = m & ~((2ull << i) - 1ull);
-  return mm ? __builtin_ctzll(mm) : 64;
-}
-__device__ __forceinline__ unsigned long long wave_incl_sum(unsigned long long v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-// value of v in lane src (clamped to 0).  Called with every lane active: a bpermute under a
-// divergent condition reads nothing from the lanes the condition switched off.
-template <class T>
-__device__ __forceinline__ T at_lane(T v, int src) { return __shfl(v, src < 0 ? 0 : src, 64); }
-
-// rule 6's time of route distance x of D between the two state times (the oracle's operation order)
-__device__ __forceinline__ double interp_time(double ta, double tb, uint64_t x, uint64_t D) {
-  if (D == 0) return ta;
-  return ta + (tb - ta) * ((double)x / (double)D);
-}
-
-__device__ __forceinline__ bool same_chain(uint32_t slot_prev, uint32_t slot_next) {
-  // records of a chain come from consecutive transition slots; traces are at least two slots apart
-  return slot_next == slot_prev || slot_next == slot_prev + 1;
-}
 
 // the road's stored vertices strictly inside (lo, hi): the first one and how many
 __device__ __forceinline__ uint32_t interior(const DevGraph& g, uint32_t va, uint32_t vb, uint32_t lo, uint32_t hi,
@@ -324,30 +292,13 @@ __global__ void __launch_bounds__(kFillThreads) k_edge_fill(DevGraph g, EdgeArgs
 }
 
 // grow-only device buffer of n bytes (by half again)
-void grow(void*& p, uint64_t& cap, uint64_t need, const char* what) {
-  if (need <= cap) return;
-  if (p) RM_HIP(hipFree(p));
-  p = nullptr;
-  cap = 0;
+void grow(DevBuf<char>& p, uint64_t need, const char* what) {
+  if (need <= p.cap()) return;
   const uint64_t c = std::max<uint64_t>(need + need / 2, 4096);
-  const hipError_t e = hipMalloc(&p, c);
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();
-    p = nullptr;
-    throw BatchTooLarge(std::string("matched-edge ") + what + " buffer of " + std::to_string(c) + " bytes does not fit in HBM");
-  }
-  RM_HIP(e);
-  cap = c;
+  p.reserve(c, (std::string("matched-edge ") + what + " buffer of " + std::to_string(c) + " bytes does not fit in HBM").c_str());
 }
 
 }  // namespace
-
-void Matcher::free_matched_edges() {
-  for (void* q : {me_stage_, me_small_, me_edges_, me_shape_})
-    if (q) (void)hipFree(q);
-  for (hipEvent_t ev : me_ev_)
-    if (ev) (void)hipEventDestroy(ev);
-}
 
 void Matcher::matched_edges(uint64_t out[2]) {
   RM_HIP(hipSetDevice(eng_->device()));
@@ -355,16 +306,15 @@ void Matcher::matched_edges(uint64_t out[2]) {
   const uint32_t T = n_traces_;
   const uint64_t R = n_path_;   // one traversal record per chosen path edge
   me_traces_ = T; me_n_ = 0; me_v_ = 0; me_ms_ = 0.0; me_ran_ = true;
+  me_timer_.harvest(nullptr);   // (a pair a call that threw left behind)
   out[0] = out[1] = 0;
   if (!T) return;
   if (R >= 0xffffffffull) throw BatchTooLarge("batch too large (traversal records >= 2^32)");
   const uint32_t* rvo = eng_->road_vert_off_dev();
   // per trace 2 counts, 2 (T + 1) offsets, then the two totals (8-byte aligned)
   const uint64_t words = 4ull * T + 2;
-  grow(me_small_, me_small_cap_, (words + (words & 1)) * 4 + 16, "offset");
-  grow(me_stage_, me_stage_cap_, std::max<uint64_t>(R, 1) * sizeof(MatchedEdge), "staging");
-  for (hipEvent_t& ev : me_ev_)
-    if (!ev) RM_HIP(hipEventCreate(&ev));
+  grow(me_small_, (words + (words & 1)) * 4 + 16, "offset");
+  grow(me_stage_, std::max<uint64_t>(R, 1) * sizeof(MatchedEdge), "staging");
   const Workspace& w = ws_;
   EdgeArgs a;
   a.T = T; a.total = (uint32_t)R; a.P = n_points_; a.visits = 0;
@@ -373,40 +323,38 @@ void Matcher::matched_edges(uint64_t out[2]) {
   a.path_sab = w.path_sab; a.route_dist = w.route_dist; a.trav_off = w.trav_off; a.rec_slot = w.rec_slot;
   a.trace_err = w.trace_err;
   a.road_vert_off = rvo;
-  a.stage = (uint4*)me_stage_;
-  a.cnt = (uint32_t*)me_small_;
+  a.stage = (uint4*)me_stage_.get();
+  a.cnt = (uint32_t*)me_small_.get();
   a.off = a.cnt + 2ull * T;
-  a.tot = (unsigned long long*)((char*)me_small_ + (words + (words & 1)) * 4);
+  a.tot = (unsigned long long*)(me_small_ + (words + (words & 1)) * 4);
   a.edges = nullptr; a.shape = nullptr;
   const DevGraph g = eng_->dev_snapshot();
   // every run path leaves rec_slot filled (k_rec_slot, or the path scan's fused apply pass)
-  RM_HIP(hipEventRecord(me_ev_[0], stream_));
+  me_timer_.tic(0, stream_);
   hipLaunchKernelGGL(k_edge_visits, dim3(T), dim3(64), 0, stream_, g, a);
   hipLaunchKernelGGL(k_edge_scan, dim3(1), dim3(kScanThreads), 0, stream_, a);
-  RM_HIP(hipEventRecord(me_ev_[1], stream_));
+  me_timer_.toc(stream_);
   RM_HIP(hipGetLastError());
   unsigned long long tot[2] = {0, 0};
   RM_HIP(hipMemcpyAsync(tot, a.tot, sizeof tot, hipMemcpyDeviceToHost, stream_));
   sync();
   if (tot[0] > R || tot[1] >= 0xffffffffull) throw BatchTooLarge("batch too large (shape vertices >= 2^32)");
-  float ms0 = 0.f, ms1 = 0.f;
-  RM_HIP(hipEventElapsedTime(&ms0, me_ev_[0], me_ev_[1]));
+  me_timer_.harvest(&me_ms_);
   if (tot[0]) {
-    grow(me_edges_, me_edges_cap_, tot[0] * sizeof(MatchedEdge), "record");
-    grow(me_shape_, me_shape_cap_, tot[1] * sizeof(float2), "shape");
-    a.edges = (uint4*)me_edges_;
-    a.shape = (float2*)me_shape_;
+    grow(me_edges_, tot[0] * sizeof(MatchedEdge), "record");
+    grow(me_shape_, tot[1] * sizeof(float2), "shape");
+    a.edges = (uint4*)me_edges_.get();
+    a.shape = (float2*)me_shape_.get();
     a.visits = tot[0];
     const uint32_t grid = (uint32_t)((tot[0] + kFillThreads - 1) / kFillThreads);
-    RM_HIP(hipEventRecord(me_ev_[2], stream_));
+    me_timer_.tic(0, stream_);
     hipLaunchKernelGGL(k_edge_fill, dim3(grid), dim3(kFillThreads), 0, stream_, g, a);
-    RM_HIP(hipEventRecord(me_ev_[3], stream_));
+    me_timer_.toc(stream_);
     RM_HIP(hipGetLastError());
     sync();
-    RM_HIP(hipEventElapsedTime(&ms1, me_ev_[2], me_ev_[3]));
+    me_timer_.harvest(&me_ms_);
   }
   me_n_ = tot[0]; me_v_ = tot[1];
-  me_ms_ = (double)ms0 + (double)ms1;
   out[0] = me_n_; out[1] = me_v_;
 }
 
@@ -416,7 +364,7 @@ void Matcher::get_matched_edges(uint32_t* edge_off, MatchedEdge* edges, uint32_t
   if (!me_ran_) throw std::runtime_error("matched_edges has not run");
   const uint32_t T = me_traces_;
   if (!T) { edge_off[0] = 0; shape_off[0] = 0; return; }
-  const uint32_t* off = (const uint32_t*)me_small_ + 2ull * T;
+  const uint32_t* off = (const uint32_t*)me_small_.get() + 2ull * T;
   RM_HIP(hipMemcpyAsync(edge_off, off, (T + 1ull) * 4, hipMemcpyDeviceToHost, stream_));
   RM_HIP(hipMemcpyAsync(shape_off, off + T + 1, (T + 1ull) * 4, hipMemcpyDeviceToHost, stream_));
   if (me_n_) {

@@ -35,6 +35,7 @@
 
 #include "engine.hpp"
 #include "json_points.hpp"
+#include "wave_util.hpp"
 
 namespace rm {
 
@@ -4261,18 +4262,7 @@ __device__ __forceinline__ void run_close(const DevGraph& g, RunState& R, Segmen
   R.open = false;
 }
 
-__device__ __forceinline__ double interp_time(double ta, double tb, uint64_t x, uint64_t D) {
-  if (D == 0) return ta;
-  return ta + (tb - ta) * ((double)x / (double)D);
-}
-
 enum : uint8_t { kRecSkip = 0, kRecNew = 1, kRecMerged = 2 };
-
-__device__ __forceinline__ bool same_chain(uint32_t slot_prev, uint32_t slot_next) {
-  // traversal records of a chain come from consecutive transition slots; traces are
-  // at least two slots apart, so this also separates traces
-  return slot_next == slot_prev || slot_next == slot_prev + 1;
-}
 
 // kind / head flag of t given the previous kept record u of its chain (has_u)
 __device__ __forceinline__ void flag_vs(const TravRec& t, bool has_u, const TravRec& u, uint8_t& kind, uint32_t& head) {
@@ -4298,28 +4288,8 @@ __device__ __forceinline__ void flag_vs(const TravRec& t, bool has_u, const Trav
 // the trailing slow pieces, last differing way).  The run or piece still open at a window's
 // end is carried in wave-uniform registers.  Segments of trace k land at seg_base[k] = its
 // first record (a trace has no more runs than records).  No LDS, no block barrier: the
-// per-trace work is independent, so the launch is as wide as the trace count.
-__device__ __forceinline__ int hi_le(unsigned long long m, int i) {   // highest set bit <= i, or -1
-  if (i < 0) return -1;
-  const unsigned long long mm = m & ((2ull << i) - 1ull);
-  return mm ? 63 - __builtin_clzll(mm) : -1;
-}
-__device__ __forceinline__ int lo_gt(unsigned long long m, int i) {   // lowest set bit > i, or 64
-  const unsigned long long mm = m & ~((2ull << i) - 1ull);
-  return mm ? __builtin_ctzll(mm) : 64;
-}
-__device__ __forceinline__ unsigned long long wave_incl_sum(unsigned long long v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const unsigned long long t = __shfl_up(v, d, 64);
-    if (lane >= d) v += t;
-  }
-  return v;
-}
-// value of v in lane src (clamped to 0).  Called with every lane active: a bpermute under a
-// divergent condition reads nothing from the lanes the condition switched off.
-template <class T>
-__device__ __forceinline__ T at_lane(T v, int src) { return __shfl(v, src < 0 ? 0 : src, 64); }
+// per-trace work is independent, so the launch is as wide as the trace count.  The mask
+// searches, the wave scan and the time interpolation are wave_util.hpp's, shared with edges.hip.
 
 __global__ void k_rec_slot(DevBatch b, uint32_t* rec_slot) {
   if (small_abort(b)) return;   // (a steady run gated off: Matcher::run_steady)
@@ -5569,8 +5539,6 @@ Matcher::~Matcher() {
   for (auto& ev : free_ev_) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
   ws_.release();
   if (dl_dev_) (void)hipFree(dl_dev_);
-  if (mp_dev_) (void)hipFree(mp_dev_);
-  free_matched_edges();
   if (dl_host_) (void)hipHostFree(dl_host_);
   for (void* q : {(void*)jdev_, jspan_, (void*)jflag_, jtsp_})
     if (q) (void)hipFree(q);

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "balls.hpp"
+#include "dev_util.hpp"
 #include "graph.hpp"
 #include "rm_common.hpp"
 #include "msg_lines.hpp"
@@ -23,19 +24,6 @@
 #include "sv_lines.hpp"
 
 namespace rm {
-
-#define RM_HIP(x)                                                                                \
-  do {                                                                                           \
-    hipError_t _e = (x);                                                                         \
-    if (_e != hipSuccess)                                                                        \
-      throw std::runtime_error(std::string("HIP error ") + hipGetErrorString(_e) + " at " #x);   \
-  } while (0)
-
-// hipMalloc found too little free HBM (the engine's allocator; callers decide whether a smaller
-// request can succeed: workspaces turn it into BatchTooLarge, the route-ball build steps down)
-struct OutOfDeviceMemory : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
 
 struct DevGraph {  // POD view of the graph in HBM, passed by value to kernels
   const uint32_t* node_off;
@@ -308,24 +296,19 @@ struct TileRow {
 static_assert(sizeof(TileRow) == 64, "TileRow is four dwordx4");
 
 struct StageBufs {  // grow-only device buffers of the windowing and tile stages
-  std::vector<void*> allocs;
   uint64_t cap_pts = 0, cap_rows = 0;
-  uint32_t cap_tr = 0;
-  uint32_t* derr = nullptr;
-  uint32_t* p_uuid = nullptr; double* p_time = nullptr; float* p_lon = nullptr; float* p_lat = nullptr;
-  float* p_acc = nullptr; uint32_t* p_uopt = nullptr; MatchOptions* p_opts = nullptr;
-  unsigned long long* k0 = nullptr; unsigned long long* k1 = nullptr; uint32_t* v0 = nullptr; uint32_t* v1 = nullptr;
-  uint32_t* flag = nullptr; uint32_t* idx = nullptr; uint32_t* wstart = nullptr; uint32_t* wcnt = nullptr;
-  uint32_t* wofs = nullptr; uint32_t* wflag = nullptr; uint32_t* widx = nullptr;
-  uint32_t* trace_uuid = nullptr;
-  TileRow* rows = nullptr; TileRow* rows2 = nullptr;
-  unsigned long long* rk = nullptr; unsigned long long* rk2 = nullptr;
-  uint32_t* rperm = nullptr; uint32_t* rperm2 = nullptr; uint32_t* rflag = nullptr; uint32_t* ridx = nullptr;
-  uint32_t* gpos = nullptr; uint8_t* gkeep = nullptr; uint32_t* tcnt = nullptr; uint32_t* tofs = nullptr;
-  void* tmp = nullptr; size_t tmp_bytes = 0;
-  uint32_t* hctl = nullptr;            // pinned read-back words
-  uint32_t cap_uuids = 0;
-  ~StageBufs();
+  uint32_t cap_tr = 0, cap_uuids = 0;
+  DevBuf<uint32_t> derr, p_uuid, p_uopt;
+  DevBuf<double> p_time;
+  DevBuf<float> p_lon, p_lat, p_acc;
+  DevBuf<MatchOptions> p_opts;
+  DevBuf<unsigned long long> k0, k1, rk, rk2;
+  DevBuf<uint32_t> v0, v1, flag, idx, wstart, wcnt, wofs, wflag, widx, trace_uuid;
+  DevBuf<TileRow> rows, rows2;
+  DevBuf<uint32_t> rperm, rperm2, rflag, ridx, gpos, tcnt, tofs;
+  DevBuf<uint8_t> gkeep;
+  ScanScratch scr;                     // sized with the buffers (ensure_points, ensure_rows)
+  PinBuf<uint32_t> hctl;               // pinned read-back words
 };
 
 // error bits in ctl[kCtlErr] (and, except the path pool, per trace in Workspace::trace_err)
@@ -426,7 +409,7 @@ class Session {
 
  private:
   struct Impl;
-  Impl* p_;
+  std::unique_ptr<Impl> p_;
   SessionSnap snap_view(uint64_t n_points, uint32_t n_live);
   void match_round(uint32_t T, uint64_t P, bool evict);
   void rounds(bool evict, uint64_t out[8]);
@@ -466,7 +449,7 @@ class Directory {
 
  private:
   struct Impl;
-  Impl* p_;
+  std::unique_ptr<Impl> p_;
 };
 
 // The tile store (DESIGN.md §3 rule 13; tilestore.hip): the reference's streaming anonymiser
@@ -507,7 +490,7 @@ class TileStore {
 
  private:
   struct Impl;
-  Impl* p_;
+  std::unique_ptr<Impl> p_;
 };
 
 // The stream snapshot (DESIGN.md §3 rule 15; snapshot.hpp, snapshot.hip).  Any object may be null.
@@ -630,9 +613,9 @@ class Matcher {
   void run_points(const PointsDesc& pd, const RunParams& rp);
   // The same from the points already in StageBufs (p_uuid, p_time, p_lon, p_lat, p_acc): everything
   // from k_pt_keys on.  n_uopt: vehicles with an option index in p_uopt (0: all take opts[0]);
-  // windows_done: recorded once the windows are built, before the matcher runs
+  // windows_done: its open part is closed once the windows are built, before the matcher runs
   void run_points_device(uint64_t n, double tbase, double inactivity, const MatchOptions* opts, uint32_t n_opts,
-                         uint32_t n_uopt, const RunParams& rp, hipEvent_t windows_done = nullptr);
+                         uint32_t n_uopt, const RunParams& rp, PartTimer* windows_done = nullptr);
   // Trace-file text -> points on the device (lines.hip; DESIGN.md §3 rule 11): lines parsed by
   // k_line_parse (the generic host reader for lines outside the compact layout), the kept points
   // packed in input order into StageBufs, vehicle ids numbered in first-seen order.  run_lines
@@ -727,18 +710,15 @@ class Matcher {
   void* dl_dev_ = nullptr;     // grow-only device / pinned host buffers of download_compacted
   void* dl_host_ = nullptr;
   size_t dl_dev_bytes_ = 0, dl_host_bytes_ = 0;
-  void* mp_dev_ = nullptr;     // grow-only device buffer of matched_points (mp_cap_ records)
-  uint64_t mp_cap_ = 0;
+  DevBuf<MatchedPoint> mp_dev_;   // grow-only device buffer of matched_points
   // matched_edges: grow-only device buffers (the visits staged per trace, the per-trace counts /
   // offsets / totals, the compacted visits, the shapes), its events and the last call's sizes
-  void* me_stage_ = nullptr; void* me_small_ = nullptr; void* me_edges_ = nullptr; void* me_shape_ = nullptr;
-  uint64_t me_stage_cap_ = 0, me_small_cap_ = 0, me_edges_cap_ = 0, me_shape_cap_ = 0;
-  hipEvent_t me_ev_[4] = {nullptr, nullptr, nullptr, nullptr};
+  DevBuf<char> me_stage_, me_small_, me_edges_, me_shape_;
+  PartTimer me_timer_;
   uint32_t me_traces_ = 0;
   uint64_t me_n_ = 0, me_v_ = 0;
   double me_ms_ = 0.0;
   bool me_ran_ = false;
-  void free_matched_edges();
   hipStream_t stream_ = nullptr;
   Workspace ws_;
   uint32_t n_traces_ = 0;
@@ -845,7 +825,7 @@ class Engine {
   double turn_ms_[5] = {};
   bool build_balls_gpu(int mode, uint32_t radius_cm, uint32_t max_keys, uint64_t avail_bytes);
   double ball_info_[5][4] = {};
-  uint32_t* road_vert_off_ = nullptr;
+  DevBuf<uint32_t> road_vert_off_;
 };
 
 }  // namespace rm

@@ -49,8 +49,6 @@ constexpr uint32_t kLineRing = 128;                               // line starts
 constexpr size_t kMaxDropped = 64;                                // dropped messages a tolerant call lists
 static_assert(kLineLds % 16 == 0, "windows are staged with 16-byte loads");
 
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
-
 // bytes of w equal to '\n'
 __device__ __forceinline__ uint32_t newlines(uint32_t w) {
   const uint32_t x = w ^ 0x0a0a0a0au;
@@ -273,19 +271,15 @@ __global__ void __launch_bounds__(256) k_time_span(uint64_t P, const double* tim
   }
 }
 
-struct DevBuf {   // a grow-only device allocation
-  void* p = nullptr;
-  uint64_t bytes = 0;
-  void need(uint64_t n, hipStream_t st) {
-    if (n <= bytes && p) return;
-    if (p) { RM_HIP(hipStreamSynchronize(st)); (void)hipFree(p); p = nullptr; bytes = 0; }
-    const uint64_t c = n + n / 4 + 256;
-    RM_HIP(hipMalloc(&p, c));
-    bytes = c;
-  }
-  template <class T> T* as() const { return (T*)p; }
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
+// room for n elements, grow-only, by a quarter and 256 bytes; the old block may still be in
+// flight on the stream
+template <class T>
+void need(DevBuf<T>& b, uint64_t n, hipStream_t st) {
+  if (n <= b.cap() && b) return;
+  if (b) RM_HIP(hipStreamSynchronize(st));
+  const uint64_t bytes = n * sizeof(T);
+  b.reserve((bytes + bytes / 4 + 256 + sizeof(T) - 1) / sizeof(T));
+}
 
 unsigned long long hash_mask() {   // RM_LINES_HASH_BITS (1-64, default 64), read at every call
   long bits = 64;
@@ -307,10 +301,14 @@ struct HostLine {
 unsigned long long lines_hash_mask() { return hash_mask(); }
 
 struct LineState {
-  DevBuf text, wcnt, wfirst, scan_tmp, status, lat, lon, acc, time, id_off, id_len, hash, flag, pos;
-  DevBuf p_off, p_len, v_off, v_len, patch, part, stats, derr;
-  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  uint32_t* hctl = nullptr;   // pinned read-back words
+  DevBuf<uint8_t> text, status, patch;
+  DevBuf<uint32_t> wcnt, wfirst, id_off, id_len, flag, pos, p_off, p_len, v_off, v_len, stats, derr;
+  DevBuf<float> lat, lon, acc;
+  DevBuf<double> time, part;
+  DevBuf<unsigned long long> hash;
+  ScanScratch scr;
+  PartTimer timer;            // parts: ms[0 .. 3]
+  PinBuf<uint32_t> hctl;      // pinned read-back words
   // the last call
   std::vector<uint64_t> chunk_base;   // n_chunks + 1: where each chunk starts in the text
   std::vector<uint32_t> veh_off, veh_len;
@@ -322,11 +320,6 @@ struct LineState {
   double tmin = 0.0, tmax = 0.0;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};
   bool parsed = false;
-  ~LineState() {
-    for (hipEvent_t e : ev)
-      if (e) (void)hipEventDestroy(e);
-    if (hctl) (void)hipHostFree(hctl);
-  }
   // the chunk holding text position `at`
   uint32_t chunk_of(uint64_t at) const {
     return (uint32_t)(std::upper_bound(chunk_base.begin(), chunk_base.end() - 1, at) - chunk_base.begin()) - 1u;
@@ -362,10 +355,8 @@ void Matcher::parse_text(const MessagesDesc& d) {
   z.dropped.clear();
   z.n_groups = 0;
   hipStream_t st = stream_;
-  if (!z.hctl) {
-    RM_HIP(hipHostMalloc((void**)&z.hctl, 16 * sizeof(uint32_t), hipHostMallocDefault));
-    for (hipEvent_t& e : z.ev) RM_HIP(hipEventCreate(&e));
-  }
+  if (!z.hctl) z.hctl.reserve(16);
+  z.timer.harvest(nullptr);   // (pairs a call that threw left behind)
   // ---- the text: chunks end to end, each ending in '\n'
   z.chunk_base.assign(d.n_chunks + 1ull, 0);
   uint64_t N = 0;
@@ -383,9 +374,9 @@ void Matcher::parse_text(const MessagesDesc& d) {
   z.n_points = 0;
   std::fill(z.ms, z.ms + 4, 0.0);
   if (N == 0) { z.parsed = true; return; }
-  RM_HIP(hipEventRecord(z.ev[0], st));
-  z.text.need(kLineFront + N + kLineTail, st);
-  uint8_t* text = z.text.as<uint8_t>();
+  z.timer.tic(0, st);
+  need(z.text, kLineFront + N + kLineTail, st);
+  uint8_t* text = z.text;
   RM_HIP(hipMemsetAsync(text, '\n', kLineFront, st));
   RM_HIP(hipMemsetAsync(text + kLineFront + N, 0, kLineTail, st));
   for (uint32_t c = 0; c < d.n_chunks; ++c) {
@@ -394,49 +385,42 @@ void Matcher::parse_text(const MessagesDesc& d) {
     RM_HIP(hipMemcpyAsync(at, d.data[c], d.len[c], hipMemcpyHostToDevice, st));
     if (d.data[c][d.len[c] - 1] != '\n') RM_HIP(hipMemsetAsync(at + d.len[c], '\n', 1, st));
   }
-  RM_HIP(hipEventRecord(z.ev[1], st));
+  z.timer.toc(st);
+  z.timer.tic(1, st);
   // ---- lines per window, each window's first line
   const uint32_t nwin = (uint32_t)((N + kLineWin - 1) / kLineWin);
-  z.wcnt.need(nwin * 4ull, st);
-  z.wfirst.need(nwin * 4ull, st);
-  z.derr.need(8, st);
-  RM_HIP(hipMemsetAsync(z.derr.p, 0, 8, st));
-  hipLaunchKernelGGL(k_line_count, dim3(nwin), dim3(64), 0, st, text, N, z.wcnt.as<uint32_t>());
-  auto scan = [&](const uint32_t* in, uint32_t* out, uint64_t n) {
-    size_t need = 0;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, in, out, (int)n, st));
-    z.scan_tmp.need(need, st);
-    need = z.scan_tmp.bytes;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(z.scan_tmp.p, need, in, out, (int)n, st));
-  };
-  scan(z.wcnt.as<uint32_t>(), z.wfirst.as<uint32_t>(), nwin);
-  RM_HIP(hipMemcpyAsync(z.hctl + 0, z.wfirst.as<uint32_t>() + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
-  RM_HIP(hipMemcpyAsync(z.hctl + 1, z.wcnt.as<uint32_t>() + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
+  need(z.wcnt, nwin, st);
+  need(z.wfirst, nwin, st);
+  need(z.derr, 2, st);
+  RM_HIP(hipMemsetAsync(z.derr, 0, 8, st));
+  hipLaunchKernelGGL(k_line_count, dim3(nwin), dim3(64), 0, st, text, N, z.wcnt);
+  z.scr.scan<uint32_t>(z.wcnt, z.wfirst, nwin, st);
+  RM_HIP(hipMemcpyAsync(z.hctl + 0, z.wfirst + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipMemcpyAsync(z.hctl + 1, z.wcnt + (nwin - 1), 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
   const uint64_t L = (uint64_t)z.hctl[0] + z.hctl[1];
   if (L == 0 || L >= 0x7fffffffull) throw std::runtime_error("line input: line count out of range");
   // ---- every line read
-  z.status.need(L, st); z.lat.need(L * 4, st); z.lon.need(L * 4, st); z.acc.need(L * 4, st); z.time.need(L * 8, st);
-  z.id_off.need(L * 4, st); z.id_len.need(L * 4, st); z.hash.need(L * 8, st); z.flag.need(L * 4, st); z.pos.need(L * 4, st);
-  LineArrays la{z.status.as<uint8_t>(), z.lat.as<float>(), z.lon.as<float>(), z.acc.as<float>(), z.time.as<double>(),
-                z.id_off.as<uint32_t>(), z.id_len.as<uint32_t>(), z.hash.as<unsigned long long>()};
+  need(z.status, L, st); need(z.lat, L, st); need(z.lon, L, st); need(z.acc, L, st); need(z.time, L, st);
+  need(z.id_off, L, st); need(z.id_len, L, st); need(z.hash, L, st); need(z.flag, L, st); need(z.pos, L, st);
+  LineArrays la{z.status, z.lat, z.lon, z.acc, z.time, z.id_off, z.id_len, z.hash};
   const msg::Keys keys = msg::make_keys(d.fmt);
   if (d.fmt.kind == 1)
-    hipLaunchKernelGGL(k_line_parse<1>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
-                       (uint32_t)L, d.fmt.line, keys, la, z.derr.as<uint32_t>());
+    hipLaunchKernelGGL(k_line_parse<1>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, keys, la, z.derr);
   else
-    hipLaunchKernelGGL(k_line_parse<0>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst.as<uint32_t>(), z.wcnt.as<uint32_t>(),
-                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr.as<uint32_t>());
+    hipLaunchKernelGGL(k_line_parse<0>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr);
   RM_HIP(hipGetLastError());
   // ---- "is a point" flags and the counts of the rest
   const uint32_t sb = std::min<uint32_t>(1024u, grid(L));
-  z.stats.need(sb * 12ull, st);
+  need(z.stats, sb * 3ull, st);
   std::vector<uint32_t> spart(3ull * sb);
   uint64_t count[3] = {0, 0, 0};   // blank, outside, host
   auto stats = [&] {
-    hipLaunchKernelGGL(k_line_stats, dim3(sb), dim3(256), 0, st, L, la.status, z.flag.as<uint32_t>(), z.stats.as<uint32_t>());
-    RM_HIP(hipMemcpyAsync(spart.data(), z.stats.p, sb * 12ull, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipMemcpyAsync(z.hctl + 2, z.derr.p, 4, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_line_stats, dim3(sb), dim3(256), 0, st, L, la.status, z.flag, z.stats);
+    RM_HIP(hipMemcpyAsync(spart.data(), z.stats, sb * 12ull, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipMemcpyAsync(z.hctl + 2, z.derr, 4, hipMemcpyDeviceToHost, st));
     RM_HIP(hipStreamSynchronize(st));
     count[0] = count[1] = count[2] = 0;
     for (uint32_t b = 0; b < sb; ++b)
@@ -497,9 +481,9 @@ void Matcher::parse_text(const MessagesDesc& d) {
       std::memcpy(&w[3 * Hp + i], &h.v.lat, 4); std::memcpy(&w[4 * Hp + i], &h.v.lon, 4); std::memcpy(&w[5 * Hp + i], &h.v.acc, 4);
       tm[i] = h.v.time; hs[i] = h.v.hash; sp[i] = (uint8_t)h.status;
     }
-    z.patch.need(blk.size(), st);
-    RM_HIP(hipMemcpy(z.patch.p, blk.data(), blk.size(), hipMemcpyHostToDevice));
-    const uint8_t* pb = z.patch.as<uint8_t>();
+    need(z.patch, blk.size(), st);
+    RM_HIP(hipMemcpy(z.patch, blk.data(), blk.size(), hipMemcpyHostToDevice));
+    const uint8_t* pb = z.patch;
     const uint32_t* pw = (const uint32_t*)pb;
     LinePatch lp{pw, pb + Hp * 40, (const float*)(pw + 3 * Hp), (const float*)(pw + 4 * Hp), (const float*)(pw + 5 * Hp),
                  (const double*)(pb + Hp * 24), pw + Hp, pw + 2 * Hp, (const unsigned long long*)(pb + Hp * 32)};
@@ -512,57 +496,55 @@ void Matcher::parse_text(const MessagesDesc& d) {
   z.info[2] = count[1];
   z.info[5] = H;
   // ---- the kept points, in input order
-  scan(z.flag.as<uint32_t>(), z.pos.as<uint32_t>(), L);
-  RM_HIP(hipEventRecord(z.ev[2], st));
+  z.scr.scan<uint32_t>(z.flag, z.pos, L, st);
+  z.timer.toc(st);
+  z.timer.tic(2, st);
   const uint64_t P = L - z.info[1] - z.info[2] - z.n_dropped;
   z.info[3] = P;
   z.n_points = P;
-  if (P == 0) { RM_HIP(hipStreamSynchronize(st)); z.parsed = true; return; }
+  if (P == 0) { RM_HIP(hipStreamSynchronize(st)); z.timer.harvest(nullptr); z.parsed = true; return; }
   ensure_points(P, 0, 1);
   StageBufs& s = sb_;
-  z.p_off.need(P * 4, st); z.p_len.need(P * 4, st);
+  need(z.p_off, P, st); need(z.p_len, P, st);
   const unsigned long long mask = hash_mask();
-  hipLaunchKernelGGL(k_line_compact, dim3(grid(L)), dim3(256), 0, st, L, la, z.flag.as<uint32_t>(), z.pos.as<uint32_t>(), mask,
-                     s.p_time, s.p_lon, s.p_lat, s.p_acc, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(), s.k0, s.v0);
+  hipLaunchKernelGGL(k_line_compact, dim3(grid(L)), dim3(256), 0, st, L, la, z.flag, z.pos, mask,
+                     s.p_time, s.p_lon, s.p_lat, s.p_acc, z.p_off, z.p_len, s.k0, s.v0);
   // ---- the time span (the window sort's key base)
   const uint32_t nb = std::min<uint32_t>(1024u, grid(P));
-  z.part.need(nb * 16ull, st);
-  hipLaunchKernelGGL(k_time_span, dim3(nb), dim3(256), 0, st, P, s.p_time, z.part.as<double>());
+  need(z.part, nb * 2ull, st);
+  hipLaunchKernelGGL(k_time_span, dim3(nb), dim3(256), 0, st, P, s.p_time, z.part);
   std::vector<double> part(2ull * nb);
-  RM_HIP(hipMemcpyAsync(part.data(), z.part.p, nb * 16ull, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipMemcpyAsync(part.data(), z.part, nb * 16ull, hipMemcpyDeviceToHost, st));
   // ---- vehicle ids in first-seen order
-  size_t tmp = s.tmp_bytes;
   int bits = 0;
   while (bits < 64 && (mask >> bits)) ++bits;
-  RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)P, 0, bits, st));
-  hipLaunchKernelGGL(k_id_flags, dim3(grid(P)), dim3(256), 0, st, P, s.k1, s.v1, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(),
-                     text + kLineFront, s.flag, z.derr.as<uint32_t>() + 1);
-  tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.flag, s.idx, (int)P, st));
+  s.scr.sort_pairs(s.k0.get(), s.k1.get(), s.v0, s.v1, P, bits, st);
+  hipLaunchKernelGGL(k_id_flags, dim3(grid(P)), dim3(256), 0, st, P, s.k1, s.v1, z.p_off, z.p_len,
+                     text + kLineFront, s.flag, z.derr + 1);
+  s.scr.scan<uint32_t>(s.flag, s.idx, P, st);
   // k0 / v0 are free again: the groups' (first point, group) pairs; wstart: each point's group
   hipLaunchKernelGGL(k_id_groups, dim3(grid(P)), dim3(256), 0, st, P, s.flag, s.idx, s.v1, s.k0, s.v0, s.wstart, z.hctl + 4);
-  RM_HIP(hipMemcpyAsync(z.hctl + 3, z.derr.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, st));
+  RM_HIP(hipMemcpyAsync(z.hctl + 3, z.derr + 1, 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
   z.tmin = part[0];
   z.tmax = part[1];
   for (uint32_t b = 1; b < nb; ++b) { z.tmin = std::min(z.tmin, part[2 * b]); z.tmax = std::max(z.tmax, part[2 * b + 1]); }
   if (!z.hctl[3]) {
     const uint32_t G = z.hctl[4];
-    z.v_off.need(G * 4ull, st); z.v_len.need(G * 4ull, st);
-    tmp = s.tmp_bytes;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)G, 0, 32, st));
-    hipLaunchKernelGGL(k_id_rank, dim3(grid(G)), dim3(256), 0, st, G, s.k1, s.v1, z.p_off.as<uint32_t>(), z.p_len.as<uint32_t>(),
-                       s.wcnt, z.v_off.as<uint32_t>(), z.v_len.as<uint32_t>());
+    need(z.v_off, G, st); need(z.v_len, G, st);
+    s.scr.sort_pairs(s.k0.get(), s.k1.get(), s.v0, s.v1, G, 32, st);
+    hipLaunchKernelGGL(k_id_rank, dim3(grid(G)), dim3(256), 0, st, G, s.k1, s.v1, z.p_off, z.p_len,
+                       s.wcnt, z.v_off, z.v_len);
     hipLaunchKernelGGL(k_id_scatter, dim3(grid(P)), dim3(256), 0, st, P, s.wstart, s.wcnt, s.p_uuid);
     z.veh_off.resize(G);
     z.veh_len.resize(G);
-    RM_HIP(hipMemcpyAsync(z.veh_off.data(), z.v_off.p, G * 4ull, hipMemcpyDeviceToHost, st));
-    RM_HIP(hipMemcpyAsync(z.veh_len.data(), z.v_len.p, G * 4ull, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipMemcpyAsync(z.veh_off.data(), z.v_off, G * 4ull, hipMemcpyDeviceToHost, st));
+    RM_HIP(hipMemcpyAsync(z.veh_len.data(), z.v_len, G * 4ull, hipMemcpyDeviceToHost, st));
   } else {
     // two ids share a hash: number them on the host from their bytes (the same numbering)
     std::vector<uint32_t> off(P), len(P), id(P);
-    RM_HIP(hipMemcpy(off.data(), z.p_off.p, P * 4, hipMemcpyDeviceToHost));
-    RM_HIP(hipMemcpy(len.data(), z.p_len.p, P * 4, hipMemcpyDeviceToHost));
+    RM_HIP(hipMemcpy(off.data(), z.p_off, P * 4, hipMemcpyDeviceToHost));
+    RM_HIP(hipMemcpy(len.data(), z.p_len, P * 4, hipMemcpyDeviceToHost));
     std::unordered_map<std::string_view, uint32_t> table;
     uint32_t c = 0;
     for (uint64_t k = 0; k < P; ++k) {
@@ -576,12 +558,13 @@ void Matcher::parse_text(const MessagesDesc& d) {
     z.info[6] = 1;
     // (the name spans on the device too, as the other branch leaves them: the directory reads them)
     const uint64_t G = z.veh_off.size();
-    z.v_off.need(G * 4ull, st); z.v_len.need(G * 4ull, st);
-    RM_HIP(hipMemcpy(z.v_off.p, z.veh_off.data(), G * 4, hipMemcpyHostToDevice));
-    RM_HIP(hipMemcpy(z.v_len.p, z.veh_len.data(), G * 4, hipMemcpyHostToDevice));
+    need(z.v_off, G, st); need(z.v_len, G, st);
+    RM_HIP(hipMemcpy(z.v_off, z.veh_off.data(), G * 4, hipMemcpyHostToDevice));
+    RM_HIP(hipMemcpy(z.v_len, z.veh_len.data(), G * 4, hipMemcpyHostToDevice));
   }
-  RM_HIP(hipEventRecord(z.ev[3], st));
+  z.timer.toc(st);
   RM_HIP(hipStreamSynchronize(st));
+  z.timer.harvest(z.ms);
   z.info[4] = z.veh_off.size();
   z.n_groups = (uint32_t)z.veh_off.size();
   z.parsed = true;
@@ -603,8 +586,8 @@ LineGroups Matcher::line_groups() const {
   LineGroups g;
   g.n_points = z.n_points;
   g.n_groups = z.n_points ? z.n_groups : 0u;
-  g.text = z.n_points ? z.text.as<uint8_t>() + kLineFront : nullptr;
-  g.v_off = z.v_off.as<uint32_t>(); g.v_len = z.v_len.as<uint32_t>();
+  g.text = z.n_points ? z.text + kLineFront : nullptr;
+  g.v_off = z.v_off; g.v_len = z.v_len;
   g.p_uuid = sb_.p_uuid; g.p_time = sb_.p_time; g.p_lon = sb_.p_lon; g.p_lat = sb_.p_lat; g.p_acc = sb_.p_acc;
   g.hash_mask = hash_mask();
   return g;
@@ -626,9 +609,9 @@ void Matcher::run_lines(const LinesDesc& d, const RunParams& rp) {
   if (n == 0) { n_traces_ = 0; n_points_ = 0; n_trans_ = 0; n_path_ = 0; seg_used_ = 0; return; }
   const double tbase = std::floor(z.tmin);
   if (std::floor(z.tmax) - tbase >= 4294967295.0) throw std::runtime_error("point times span more than 2^32 s");
-  run_points_device(n, tbase, d.inactivity, d.opts, 1, 0, rp, z.ev[4]);
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, z.ev[3], z.ev[4]) == hipSuccess) z.ms[3] = ms;
+  z.timer.tic(3, stream_);   // the windows: closed inside run_points_device
+  run_points_device(n, tbase, d.inactivity, d.opts, 1, 0, rp, &z.timer);
+  z.timer.harvest(z.ms);
 }
 
 void Matcher::lines_info(uint64_t out[7]) const {
@@ -638,12 +621,7 @@ void Matcher::lines_info(uint64_t out[7]) const {
 
 void Matcher::lines_time(double ms[4]) const {
   if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
-  LineState& z = *ls_;
-  for (int k = 0; k < 3; ++k) {
-    float t = 0.f;
-    if (z.n_points && hipEventElapsedTime(&t, z.ev[k], z.ev[k + 1]) == hipSuccess) z.ms[k] = t;
-  }
-  std::copy(z.ms, z.ms + 4, ms);
+  std::copy(ls_->ms, ls_->ms + 4, ms);
 }
 
 void Matcher::get_line_points(uint32_t* uuid, double* time, float* lon, float* lat, float* acc) {

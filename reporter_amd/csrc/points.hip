@@ -288,12 +288,9 @@ const uint32_t* Engine::road_vert_off_dev() {
   std::lock_guard<std::mutex> lk(ball_mu_);
   if (!road_vert_off_) {
     RM_HIP(hipSetDevice(device_));
-    void* q = nullptr;
     const std::vector<uint32_t>& v = host_.road_vert_off;
-    RM_HIP(hipMalloc(&q, std::max<size_t>(v.size(), 1) * sizeof(uint32_t)));
-    allocs_.push_back(q);
-    RM_HIP(hipMemcpy(q, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    road_vert_off_ = (uint32_t*)q;
+    road_vert_off_.reserve(v.size());
+    RM_HIP(hipMemcpy(road_vert_off_, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   }
   return road_vert_off_;
 }
@@ -304,19 +301,9 @@ void Matcher::matched_points(MatchedPoint* out) {
   const uint64_t P = n_points_;
   if (!n_traces_ || !P) return;
   const uint32_t* rvo = eng_->road_vert_off_dev();
-  if (P > mp_cap_) {   // grow-only, by half again (a service's batch sizes creep upwards)
-    if (mp_dev_) RM_HIP(hipFree(mp_dev_));
-    mp_dev_ = nullptr;
-    mp_cap_ = 0;
+  if (P > mp_dev_.cap()) {   // grow-only, by half again (a service's batch sizes creep upwards)
     const uint64_t c = std::max<uint64_t>(P + P / 2, 4096);
-    const hipError_t e = hipMalloc(&mp_dev_, c * sizeof(MatchedPoint));
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      mp_dev_ = nullptr;
-      throw BatchTooLarge("matched-point buffer of " + std::to_string(c * sizeof(MatchedPoint)) + " bytes does not fit in HBM");
-    }
-    RM_HIP(e);
-    mp_cap_ = c;
+    mp_dev_.reserve(c, ("matched-point buffer of " + std::to_string(c * sizeof(MatchedPoint)) + " bytes does not fit in HBM").c_str());
   }
   const Workspace& w = ws_;
   PointsArgs a;
@@ -328,7 +315,7 @@ void Matcher::matched_points(MatchedPoint* out) {
   a.path_sab = w.path_sab;
   a.trace_err = w.trace_err;
   a.road_vert_off = rvo;
-  a.out = (uint4*)mp_dev_;
+  a.out = (uint4*)mp_dev_.get();
   const uint32_t grid = (uint32_t)((P * kPtW + kPtThreads - 1) / kPtThreads);
   tic(kKPoints);
   hipLaunchKernelGGL(k_matched_points, dim3(grid), dim3(kPtThreads), 0, stream_, eng_->dev_snapshot(), a);

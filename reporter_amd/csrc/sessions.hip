@@ -72,8 +72,6 @@ struct SessArgs {   // what the session kernels share, by value
   double dist_m, time_s; uint32_t count, max_pts;
 };
 
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)std::max<uint64_t>((n + b - 1) / b, 1); }
-
 __global__ void k_sess_keys(uint64_t n, const uint32_t* veh, const double* time, uint32_t nV, unsigned long long* key,
                             uint32_t* ctr) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -311,14 +309,6 @@ __global__ void k_sess_stamp(uint64_t n, const double* time, int has_stamp, long
   if (j < n) out[j] = has_stamp ? stamp : (long long)(time[j] * 1000.0);
 }
 
-__global__ void k_sess_fill(uint32_t n, uint32_t* v, uint32_t x) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) v[k] = x;
-}
-__global__ void k_sess_iota(uint32_t n, uint32_t* v) {
-  const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) v[k] = k;
-}
 __global__ void k_sess_sort_windows(uint32_t n, const uint32_t* perm, const SessionWindow* src, SessionWindow* dst, uint32_t* rank) {
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
@@ -337,157 +327,85 @@ __global__ void k_sess_sort_reports(uint32_t n, uint32_t n_win, const uint32_t* 
 
 }  // namespace
 
+struct PtStore {   // a PtBuf's owner
+  DevBuf<float> lon, lat, acc;
+  DevBuf<double> time;
+  DevBuf<uint32_t> arr, veh;
+  uint64_t cap = 0;
+  PtBuf view() const { return PtBuf{lon, lat, acc, time, arr, veh, cap}; }
+};
+
 struct Session::Impl {
+  static constexpr const char* kFull = "session buffers do not fit in HBM";
   Matcher* m = nullptr;
   SessionParams sp;
   uint32_t nV = 0;
-  std::vector<void*> allocs;
   // per vehicle
-  uint32_t* off = nullptr; uint32_t* cnt = nullptr; uint32_t* scan_from = nullptr; uint32_t* try_from = nullptr;
-  float* max_sep = nullptr; long long* last_update = nullptr;
-  uint32_t* nstart = nullptr; uint32_t* nend = nullptr; uint32_t* tot = nullptr; uint32_t* noff = nullptr;
-  uint32_t* list[2] = {nullptr, nullptr}; uint32_t* tidx = nullptr; uint32_t* wcnt = nullptr; uint32_t* wofs = nullptr;
-  uint32_t* wslot = nullptr;
-  uint32_t* ctr = nullptr;
-  uint32_t* hctr = nullptr;   // pinned mirror of ctr
+  DevBuf<uint32_t> off, cnt, scan_from, try_from;
+  DevBuf<float> max_sep;
+  DevBuf<long long> last_update;
+  DevBuf<uint32_t> nstart, nend, tot, noff, list[2], tidx, wcnt, wofs, wslot;
+  DevBuf<uint32_t> ctr;
+  PinBuf<uint32_t> hctr;   // pinned mirror of ctr
   // the store
-  PtBuf buf[2];
+  PtStore buf[2];
   int cur = 0;
   uint64_t extent = 0;        // points of buf[cur] in use (holes of trimmed prefixes included)
   // the micro-batch: pinned staging and its device copy (grow-only)
-  char* hstage = nullptr; char* dstage = nullptr; uint64_t stage_cap = 0;
-  unsigned long long* key0 = nullptr; unsigned long long* key1 = nullptr; uint64_t key_cap = 0;
-  long long* gen_stamp = nullptr; uint64_t gen_cap = 0;   // push_device: stamps made on the device
+  PinBuf<char> hstage; DevBuf<char> dstage; uint64_t stage_cap = 0;
+  DevBuf<unsigned long long> key0, key1; uint64_t key_cap = 0;
+  DevBuf<long long> gen_stamp; uint64_t gen_cap = 0;   // push_device: stamps made on the device
   // a call's output: as written (unsorted) and sorted by triggering arrival
-  SessionWindow* win = nullptr; SessionWindow* win_s = nullptr; unsigned long long* win_key = nullptr;
-  uint32_t* win_rank = nullptr; uint32_t win_cap = 0;
-  SessionReport* rep = nullptr; SessionReport* rep_s = nullptr; unsigned long long* rep_key = nullptr; uint32_t rep_cap = 0;
-  unsigned long long* skey = nullptr; uint32_t* sidx0 = nullptr; uint32_t* sidx1 = nullptr; uint64_t sort_cap = 0;
-  void* tmp = nullptr; size_t tmp_bytes = 0;
+  DevBuf<SessionWindow> win, win_s; DevBuf<unsigned long long> win_key;
+  DevBuf<uint32_t> win_rank; uint32_t win_cap = 0;
+  DevBuf<SessionReport> rep, rep_s; DevBuf<unsigned long long> rep_key; uint32_t rep_cap = 0;
+  DevBuf<unsigned long long> skey; DevBuf<uint32_t> sidx0, sidx1; uint64_t sort_cap = 0;
+  ScanScratch scr{kFull};
   uint64_t rep_bound = 0;     // host bound on the reports written so far in the call
   uint64_t n_win = 0, n_rep = 0, rounds = 0, triggers = 0, arrivals = 0;
   // HIP-event pairs of the call, by part (0 upload, 1 append, 2 trigger, 3 match, 4 trim)
-  struct Ev { hipEvent_t a, b; int part; };
-  std::vector<Ev> pending;
-  std::vector<hipEvent_t> free_ev;
+  PartTimer timer;
   double ms[5] = {0, 0, 0, 0, 0};
 
-  template <class T>
-  T* alloc(uint64_t n) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(T));
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      throw BatchTooLarge("session buffers do not fit in HBM");
-    }
-    RM_HIP(e);
-    allocs.push_back(p);
-    return (T*)p;
-  }
-  template <class T>
-  void drop(T*& p) {
-    if (!p) return;
-    (void)hipFree(p);
-    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)p));
-    p = nullptr;
-  }
-  hipEvent_t event() {
-    hipEvent_t e;
-    if (!free_ev.empty()) { e = free_ev.back(); free_ev.pop_back(); return e; }
-    RM_HIP(hipEventCreate(&e));
-    return e;
-  }
-  void tic(int part, hipStream_t st) {
-    Ev e{event(), event(), part};
-    RM_HIP(hipEventRecord(e.a, st));
-    pending.push_back(e);
-  }
-  void toc(hipStream_t st) { RM_HIP(hipEventRecord(pending.back().b, st)); }
-  void harvest() {   // after a stream synchronise
-    for (Ev& e : pending) {
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, e.a, e.b) == hipSuccess) ms[e.part] += t;
-      else (void)hipGetLastError();   // (a part an exception cut short)
-      free_ev.push_back(e.a); free_ev.push_back(e.b);
-    }
-    pending.clear();
-  }
-  void need_tmp(size_t bytes) {
-    if (bytes <= tmp_bytes && tmp) return;
-    char* t = (char*)tmp;
-    drop(t);
-    tmp_bytes = bytes + bytes / 2 + 256;
-    tmp = alloc<char>(tmp_bytes);
-  }
-  void scan(const uint32_t* in, uint32_t* out, uint32_t n, hipStream_t st) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, st));
-    need_tmp(b);
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, in, out, (int)n, st));
-  }
-  void sort_keys(const unsigned long long* in, unsigned long long* out, uint64_t n, hipStream_t st) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, b, in, out, (int)n, 0, 64, st));
-    need_tmp(b);
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceRadixSort::SortKeys(tmp, b, in, out, (int)n, 0, 64, st));
-  }
-  void sort_pairs(const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout, uint64_t n,
-                  hipStream_t st) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, (int)n, 0, 64, st));
-    need_tmp(b);
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, b, kin, kout, vin, vout, (int)n, 0, 64, st));
-  }
-  void ensure_buf(PtBuf& b, uint64_t n) {   // (no contents to keep: the copy's destination)
+  void ensure_buf(PtStore& b, uint64_t n) {   // (no contents to keep: the copy's destination)
     if (n <= b.cap) return;
-    drop(b.lon); drop(b.lat); drop(b.acc); drop(b.time); drop(b.arr); drop(b.veh);
     b.cap = 0;
     const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
-    b.lon = alloc<float>(c); b.lat = alloc<float>(c); b.acc = alloc<float>(c); b.time = alloc<double>(c);
-    b.arr = alloc<uint32_t>(c); b.veh = alloc<uint32_t>(c);
+    b.lon.reserve(c, kFull); b.lat.reserve(c, kFull); b.acc.reserve(c, kFull); b.time.reserve(c, kFull);
+    b.arr.reserve(c, kFull); b.veh.reserve(c, kFull);
     b.cap = c;
   }
   void ensure_stage(uint64_t n) {
     if (n > stage_cap) {
-      if (hstage) (void)hipHostFree(hstage);
-      hstage = nullptr;
-      drop(dstage);
       stage_cap = 0;
       const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
-      RM_HIP(hipHostMalloc((void**)&hstage, c * 32, hipHostMallocDefault));
-      dstage = alloc<char>(c * 32);
+      hstage.reserve(c * 32);
+      dstage.reserve(c * 32, kFull);
       stage_cap = c;
     }
     ensure_keys(n);
   }
   void ensure_keys(uint64_t n) {
     if (n > key_cap) {
-      drop(key0); drop(key1);
       key_cap = 0;
       const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
-      key0 = alloc<unsigned long long>(c); key1 = alloc<unsigned long long>(c);
+      key0.reserve(c, kFull); key1.reserve(c, kFull);
       key_cap = c;
     }
   }
   void ensure_win(uint64_t n) {
     if (n <= win_cap) return;
     if (n >= 0xffffffffull) throw BatchTooLarge("session call too large");
-    drop(win); drop(win_s); drop(win_key); drop(win_rank);
     win_cap = 0;
     const uint32_t c = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n + n / 2, 1024), 0xfffffffeull);
-    win = alloc<SessionWindow>(c); win_s = alloc<SessionWindow>(c); win_key = alloc<unsigned long long>(c);
-    win_rank = alloc<uint32_t>(c);
+    win.reserve(c, kFull); win_s.reserve(c, kFull); win_key.reserve(c, kFull); win_rank.reserve(c, kFull);
     win_cap = c;
     ensure_sort(c);
   }
   void ensure_sort(uint64_t n) {
     if (n <= sort_cap) return;
-    drop(skey); drop(sidx0); drop(sidx1);
     sort_cap = 0;
-    skey = alloc<unsigned long long>(n); sidx0 = alloc<uint32_t>(n); sidx1 = alloc<uint32_t>(n);
+    skey.reserve(n, kFull); sidx0.reserve(n, kFull); sidx1.reserve(n, kFull);
     sort_cap = n;
   }
   // room for `more` reports behind the `keep` already written (their contents move)
@@ -496,16 +414,16 @@ struct Session::Impl {
     if (n <= rep_cap) return;
     if (n >= 0xffffffffull) throw BatchTooLarge("session call too large");
     const uint32_t c = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n + n / 2, 4096), 0xfffffffeull);
-    SessionReport* r2 = alloc<SessionReport>(c);
-    unsigned long long* k2 = alloc<unsigned long long>(c);
+    DevBuf<SessionReport> r2, s2;   // all three first: a full HBM leaves the session as it was
+    DevBuf<unsigned long long> k2;
+    r2.reserve(c, kFull); k2.reserve(c, kFull); s2.reserve(c, kFull);
     const uint64_t have = std::min<uint64_t>(keep, rep_cap);
     if (have) {
       RM_HIP(hipMemcpyAsync(r2, rep, have * sizeof(SessionReport), hipMemcpyDeviceToDevice, st));
       RM_HIP(hipMemcpyAsync(k2, rep_key, have * 8, hipMemcpyDeviceToDevice, st));
       RM_HIP(hipStreamSynchronize(st));
     }
-    drop(rep); drop(rep_key); drop(rep_s);
-    rep = r2; rep_key = k2; rep_s = alloc<SessionReport>(c);
+    rep = std::move(r2); rep_key = std::move(k2); rep_s = std::move(s2);   // (the old blocks go with r2, k2, s2)
     rep_cap = c;
     ensure_sort(c);
   }
@@ -521,6 +439,7 @@ struct Session::Impl {
     return a;
   }
   void begin_call(hipStream_t st) {
+    timer.harvest(nullptr);   // (pairs a call that threw left behind)
     for (double& x : ms) x = 0.0;
     n_win = n_rep = rounds = triggers = arrivals = 0;
     rep_bound = 0;
@@ -529,7 +448,7 @@ struct Session::Impl {
   void read_ctr(hipStream_t st) {
     RM_HIP(hipMemcpyAsync(hctr, ctr, kSNumCtr * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     RM_HIP(hipStreamSynchronize(st));
-    harvest();
+    timer.harvest(ms);
     if (hctr[kSErr] & 4u) throw std::runtime_error("session output buffers overflowed");
   }
   // lay the store out anew in the other buffer with the n sorted new points (key1) behind each
@@ -540,12 +459,12 @@ struct Session::Impl {
     RM_HIP(hipMemsetAsync(nend, 0, nV * sizeof(uint32_t), st));
     if (n) hipLaunchKernelGGL(k_sess_runs, dim3(grid(n)), dim3(256), 0, st, n, key1, nV, nstart, nend);
     hipLaunchKernelGGL(k_sess_tot, dim3(grid(nV + 1ull)), dim3(256), 0, st, nV, cnt, nstart, nend, tot);
-    scan(tot, noff, nV + 1u, st);
+    scr.scan<uint32_t>(tot, noff, nV + 1u, st);
     RM_HIP(hipMemcpyAsync(ctr + kSTotal, noff + nV, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     ensure_buf(buf[1 - cur], extent + n);
     if (extent + n)
-      hipLaunchKernelGGL(k_sess_copy, dim3(grid(extent + n)), dim3(256), 0, st, extent, n, nV, buf[cur], buf[1 - cur], off, cnt,
-                         noff, nstart, key1, b_lon, b_lat, b_time, b_acc);
+      hipLaunchKernelGGL(k_sess_copy, dim3(grid(extent + n)), dim3(256), 0, st, extent, n, nV, buf[cur].view(),
+                         buf[1 - cur].view(), off, cnt, noff, nstart, key1, b_lon, b_lat, b_time, b_acc);
   }
   void commit(const long long* stamp, hipStream_t st) {
     hipLaunchKernelGGL(k_sess_commit, dim3(grid(nV)), dim3(256), 0, st, nV, off, cnt, last_update, noff, nstart, nend, key1,
@@ -556,57 +475,41 @@ struct Session::Impl {
 
 Session::Session(Matcher* m, uint32_t n_vehicles, const SessionParams& sp) : p_(new Impl) {
   Impl& s = *p_;
-  try {
-    if (!m) throw std::runtime_error("runner is NULL");
-    if (n_vehicles == 0 || n_vehicles >= 0x7fffffffu) throw std::runtime_error("session needs 1 .. 2^31 - 2 vehicles");
-    if (!(sp.report_dist_m >= 0.0) || !(sp.report_time_s == sp.report_time_s))
-      throw std::runtime_error("session thresholds must be numbers, the distance non-negative");
-    s.m = m; s.sp = sp; s.nV = n_vehicles;
-    s.sp.run.do_report = 1;
-    s.sp.run.zero_hist = 0;
-    s.sp.run.prefetch_segments = 0;
-    RM_HIP(hipSetDevice(m->eng_->device()));
-    m->scan_options(&s.sp.opt, 1);   // the checks of a batch's option sets
-    const uint64_t V = n_vehicles;
-    s.off = s.alloc<uint32_t>(V); s.cnt = s.alloc<uint32_t>(V); s.scan_from = s.alloc<uint32_t>(V);
-    s.try_from = s.alloc<uint32_t>(V); s.max_sep = s.alloc<float>(V); s.last_update = s.alloc<long long>(V);
-    s.nstart = s.alloc<uint32_t>(V); s.nend = s.alloc<uint32_t>(V); s.tot = s.alloc<uint32_t>(V + 1);
-    s.noff = s.alloc<uint32_t>(V + 1);
-    s.list[0] = s.alloc<uint32_t>(V + 1); s.list[1] = s.alloc<uint32_t>(V + 1); s.tidx = s.alloc<uint32_t>(V + 1);
-    s.wcnt = s.alloc<uint32_t>(V + 1); s.wofs = s.alloc<uint32_t>(V + 1); s.wslot = s.alloc<uint32_t>(V + 1);
-    s.ctr = s.alloc<uint32_t>(kSNumCtr);
-    RM_HIP(hipHostMalloc((void**)&s.hctr, kSNumCtr * sizeof(uint32_t), hipHostMallocDefault));
-    hipStream_t st = m->stream_;
-    RM_HIP(hipMemsetAsync(s.off, 0, V * 4, st));
-    RM_HIP(hipMemsetAsync(s.cnt, 0, V * 4, st));
-    RM_HIP(hipMemsetAsync(s.max_sep, 0, V * 4, st));
-    RM_HIP(hipMemsetAsync(s.last_update, 0, V * 8, st));
-    // the counters: a read-out before the first call (get_store, the snapshot's pack) reads them
-    RM_HIP(hipMemsetAsync(s.ctr, 0, kSNumCtr * sizeof(uint32_t), st));
-    std::memset(s.hctr, 0, kSNumCtr * sizeof(uint32_t));
-    // an empty vehicle: scan_from = try_from = 1 (its first point never triggers)
-    hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.scan_from, 1u);
-    hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.try_from, 1u);
-    RM_HIP(hipGetLastError());
-    RM_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    for (void* q : s.allocs) (void)hipFree(q);
-    if (s.hctr) (void)hipHostFree(s.hctr);
-    delete p_;
-    throw;
-  }
+  if (!m) throw std::runtime_error("runner is NULL");
+  if (n_vehicles == 0 || n_vehicles >= 0x7fffffffu) throw std::runtime_error("session needs 1 .. 2^31 - 2 vehicles");
+  if (!(sp.report_dist_m >= 0.0) || !(sp.report_time_s == sp.report_time_s))
+    throw std::runtime_error("session thresholds must be numbers, the distance non-negative");
+  s.m = m; s.sp = sp; s.nV = n_vehicles;
+  s.sp.run.do_report = 1;
+  s.sp.run.zero_hist = 0;
+  s.sp.run.prefetch_segments = 0;
+  RM_HIP(hipSetDevice(m->eng_->device()));
+  m->scan_options(&s.sp.opt, 1);   // the checks of a batch's option sets
+  const uint64_t V = n_vehicles;
+  for (DevBuf<uint32_t>* b : {&s.off, &s.cnt, &s.scan_from, &s.try_from, &s.nstart, &s.nend}) b->reserve(V, Impl::kFull);
+  s.max_sep.reserve(V, Impl::kFull); s.last_update.reserve(V, Impl::kFull);
+  for (DevBuf<uint32_t>* b : {&s.tot, &s.noff, &s.list[0], &s.list[1], &s.tidx, &s.wcnt, &s.wofs, &s.wslot})
+    b->reserve(V + 1, Impl::kFull);
+  s.ctr.reserve(kSNumCtr, Impl::kFull);
+  s.hctr.reserve(kSNumCtr);
+  hipStream_t st = m->stream_;
+  RM_HIP(hipMemsetAsync(s.off, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.cnt, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.max_sep, 0, V * 4, st));
+  RM_HIP(hipMemsetAsync(s.last_update, 0, V * 8, st));
+  // the counters: a read-out before the first call (get_store, the snapshot's pack) reads them
+  RM_HIP(hipMemsetAsync(s.ctr, 0, kSNumCtr * sizeof(uint32_t), st));
+  std::memset(s.hctr, 0, kSNumCtr * sizeof(uint32_t));
+  // an empty vehicle: scan_from = try_from = 1 (its first point never triggers)
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.scan_from, 1u);
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(V)), dim3(256), 0, st, n_vehicles, s.try_from, 1u);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipStreamSynchronize(st));
 }
 
 Session::~Session() {
-  Impl& s = *p_;
-  (void)hipSetDevice(s.m->eng_->device());
-  (void)hipStreamSynchronize(s.m->stream_);
-  for (Impl::Ev& e : s.pending) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
-  for (hipEvent_t e : s.free_ev) (void)hipEventDestroy(e);
-  for (void* q : s.allocs) (void)hipFree(q);
-  if (s.hctr) (void)hipHostFree(s.hctr);
-  if (s.hstage) (void)hipHostFree(s.hstage);
-  delete p_;
+  (void)hipSetDevice(p_->m->eng_->device());
+  (void)hipStreamSynchronize(p_->m->stream_);
 }
 
 uint32_t Session::n_vehicles() const { return p_->nV; }
@@ -623,9 +526,9 @@ void Session::match_round(uint32_t T, uint64_t P, bool evict) {
   Matcher& m = *s.m;
   hipStream_t st = m.stream_;
   if (P >= 0xffffffffull) throw BatchTooLarge("session round too large (points >= 2^32)");
-  s.tic(3, st);
+  s.timer.tic(3, st);
   RM_HIP(hipMemsetAsync(s.wcnt + T, 0, sizeof(uint32_t), st));
-  s.scan(s.wcnt, s.wofs, T + 1u, st);
+  s.scr.scan<uint32_t>(s.wcnt, s.wofs, T + 1u, st);
   m.scan_options(&s.sp.opt, 1);
   m.ensure(P, T, 1);
   m.use_ws_inputs();
@@ -648,15 +551,15 @@ void Session::match_round(uint32_t T, uint64_t P, bool evict) {
     throw;
   }
   m.isolate_ = iso;
-  s.toc(st);
+  s.timer.toc(st);
   // every report comes from one segment, every segment from at least one traversal record
   s.ensure_rep(s.rep_bound, m.seg_used_, st);
   s.rep_bound += m.seg_used_;
-  s.tic(4, st);
+  s.timer.tic(4, st);
   hipLaunchKernelGGL(k_sess_trim, dim3(grid(T)), dim3(256), 0, st, a, T, evict ? 1 : 0, (const ReportStats*)w.stats,
                      (const uint32_t*)w.trace_err, (const uint32_t*)w.rep_cnt, (const uint32_t*)w.seg_base,
                      (const ReportRec*)w.reps, s.rep, s.rep_key, s.rep_cap);
-  s.toc(st);
+  s.timer.toc(st);
   RM_HIP(hipGetLastError());
 }
 
@@ -670,11 +573,11 @@ void Session::rounds(bool evict, uint64_t out[8]) {
     a.tveh = s.list[1];
     if (!evict) {
       if (!n_act) break;
-      s.tic(2, st);
+      s.timer.tic(2, st);
       RM_HIP(hipMemsetAsync(s.ctr + kSTrig, 0, 2 * sizeof(uint32_t), st));
       hipLaunchKernelGGL(k_sess_trigger, dim3(grid((uint64_t)n_act * kSeW, kSeThreads)), dim3(kSeThreads), 0, st, a, n_act,
                          (const uint32_t*)s.list[0]);
-      s.toc(st);
+      s.timer.toc(st);
       RM_HIP(hipGetLastError());
     }
     s.read_ctr(st);   // the round's triggered count (and the call's counters so far)
@@ -698,23 +601,23 @@ void Session::finish_call(uint64_t out[8]) {
   s.read_ctr(st);
   const uint32_t nw = s.hctr[kSWin], nr = s.hctr[kSRep];
   if (nw > s.win_cap || nr > s.rep_cap) throw std::runtime_error("session output buffers overflowed");
-  s.tic(4, st);
+  s.timer.tic(4, st);
   if (nw) {
-    hipLaunchKernelGGL(k_sess_iota, dim3(grid(nw)), dim3(256), 0, st, nw, s.sidx0);
-    s.sort_pairs(s.win_key, s.skey, s.sidx0, s.sidx1, nw, st);
+    hipLaunchKernelGGL(k_iota<uint32_t>, dim3(grid(nw)), dim3(256), 0, st, nw, s.sidx0);
+    s.scr.sort_pairs(s.win_key.get(), s.skey.get(), s.sidx0, s.sidx1, nw, 64, st);
     hipLaunchKernelGGL(k_sess_sort_windows, dim3(grid(nw)), dim3(256), 0, st, nw, (const uint32_t*)s.sidx1,
                        (const SessionWindow*)s.win, s.win_s, s.win_rank);
   }
   if (nr) {
-    hipLaunchKernelGGL(k_sess_iota, dim3(grid(nr)), dim3(256), 0, st, nr, s.sidx0);
-    s.sort_pairs(s.rep_key, s.skey, s.sidx0, s.sidx1, nr, st);
+    hipLaunchKernelGGL(k_iota<uint32_t>, dim3(grid(nr)), dim3(256), 0, st, nr, s.sidx0);
+    s.scr.sort_pairs(s.rep_key.get(), s.skey.get(), s.sidx0, s.sidx1, nr, 64, st);
     hipLaunchKernelGGL(k_sess_sort_reports, dim3(grid(nr)), dim3(256), 0, st, nr, nw, (const uint32_t*)s.sidx1,
                        (const SessionReport*)s.rep, (const uint32_t*)s.win_rank, s.rep_s);
   }
-  s.toc(st);
+  s.timer.toc(st);
   RM_HIP(hipGetLastError());
   RM_HIP(hipStreamSynchronize(st));
-  s.harvest();
+  s.timer.harvest(s.ms);
   s.n_win = nw; s.n_rep = nr;
   if (out) {
     out[0] = s.arrivals - std::min<uint64_t>(s.arrivals, s.hctr[kSSkip]);
@@ -756,12 +659,12 @@ void Session::push(const SessionPoints& pts, uint64_t out[8]) {
   const float* d_lon = (const float*)(d + c * 20);
   const float* d_lat = (const float*)(d + c * 24);
   const float* d_acc = pts.accuracy ? (const float*)(d + c * 28) : nullptr;
-  s.tic(0, st);
+  s.timer.tic(0, st);
   RM_HIP(hipMemcpyAsync(d, h, n * 8, hipMemcpyHostToDevice, st));
   RM_HIP(hipMemcpyAsync(d + c * 8, h + c * 8, n * 8, hipMemcpyHostToDevice, st));
   for (int q = 0; q < (pts.accuracy ? 4 : 3); ++q)
     RM_HIP(hipMemcpyAsync(d + c * (16 + 4 * q), h + c * (16 + 4 * q), n * 4, hipMemcpyHostToDevice, st));
-  s.toc(st);
+  s.timer.toc(st);
   append(n, d_veh, d_time, d_lon, d_lat, d_acc, d_stamp, out);
 }
 
@@ -788,15 +691,14 @@ void Session::push_device(uint64_t n, const uint32_t* d_vehicle, const double* d
   s.ensure_win(n);
   if (!d_stamp) {
     if (n > s.gen_cap) {
-      s.drop(s.gen_stamp);
       s.gen_cap = 0;
       const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
-      s.gen_stamp = s.alloc<long long>(c);
+      s.gen_stamp.reserve(c, Impl::kFull);
       s.gen_cap = c;
     }
-    s.tic(1, st);
+    s.timer.tic(1, st);
     hipLaunchKernelGGL(k_sess_stamp, dim3(grid(n)), dim3(256), 0, st, n, d_time, has_stamp ? 1 : 0, (long long)stamp, s.gen_stamp);
-    s.toc(st);
+    s.timer.toc(st);
     d_stamp = s.gen_stamp;
   }
   append(n, d_vehicle, d_time, d_lon, d_lat, d_acc, d_stamp, out);
@@ -808,18 +710,18 @@ void Session::append(uint64_t n, const uint32_t* d_veh, const double* d_time, co
                      const float* d_acc, const long long* d_stamp, uint64_t out[8]) {
   Impl& s = *p_;
   hipStream_t st = s.m->stream_;
-  s.tic(1, st);
+  s.timer.tic(1, st);
   hipLaunchKernelGGL(k_sess_keys, dim3(grid(n)), dim3(256), 0, st, n, d_veh, d_time, s.nV, s.key0, s.ctr);
-  s.sort_keys(s.key0, s.key1, n, st);
+  s.scr.sort_keys(s.key0.get(), s.key1.get(), n, st);
   s.layout_and_copy(n, d_lon, d_lat, d_time, d_acc, st);
-  s.toc(st);
+  s.timer.toc(st);
   RM_HIP(hipGetLastError());
   s.read_ctr(st);   // nothing of the session has changed yet: a bad input leaves it as it was
   if (s.hctr[kSErr] & 1u) throw std::runtime_error("session vehicle index out of range");
   if (s.hctr[kSErr] & 2u) throw std::runtime_error("session point time is NaN");
-  s.tic(1, st);
+  s.timer.tic(1, st);
   s.commit(d_stamp, st);
-  s.toc(st);
+  s.timer.toc(st);
   s.extent = s.hctr[kSTotal];
   s.arrivals = n;
   s.read_ctr(st);   // round 0's work list
@@ -836,9 +738,9 @@ void Session::punctuate(int64_t timestamp_ms, uint64_t out[8]) {
   s.ensure_win(s.nV);
   SessArgs a = s.args();
   a.tveh = s.list[1];
-  s.tic(2, st);
+  s.timer.tic(2, st);
   hipLaunchKernelGGL(k_sess_stale, dim3(grid(s.nV)), dim3(256), 0, st, a, (long long)timestamp_ms, (long long)s.sp.session_gap_ms);
-  s.toc(st);
+  s.timer.toc(st);
   RM_HIP(hipGetLastError());
   rounds(true, out);
 }
@@ -871,7 +773,7 @@ uint64_t Session::get_store(uint32_t* cnt, float* max_sep, int64_t* last_update,
   if (cnt) RM_HIP(hipMemcpy(cnt, s.cnt, V * 4, hipMemcpyDeviceToHost));
   if (max_sep) RM_HIP(hipMemcpy(max_sep, s.max_sep, V * 4, hipMemcpyDeviceToHost));
   if (last_update) RM_HIP(hipMemcpy(last_update, s.last_update, V * 8, hipMemcpyDeviceToHost));
-  const PtBuf& b = s.buf[s.cur];
+  const PtStore& b = s.buf[s.cur];
   if (n && lon) RM_HIP(hipMemcpy(lon, b.lon, n * 4, hipMemcpyDeviceToHost));
   if (n && lat) RM_HIP(hipMemcpy(lat, b.lat, n * 4, hipMemcpyDeviceToHost));
   if (n && time) RM_HIP(hipMemcpy(time, b.time, n * 8, hipMemcpyDeviceToHost));
@@ -902,7 +804,7 @@ SessionSnap Session::snapshot_pack() {
   RM_HIP(hipMemsetAsync(s.ctr + kSActive, 0, sizeof(uint32_t), st));
   s.commit(nullptr, st);
   hipLaunchKernelGGL(k_sess_live, dim3(grid(s.nV + 1ull)), dim3(256), 0, st, s.nV, (const uint32_t*)s.cnt, s.tot);
-  s.scan(s.tot, s.noff, s.nV + 1u, st);
+  s.scr.scan<uint32_t>(s.tot, s.noff, s.nV + 1u, st);
   RM_HIP(hipMemcpyAsync(s.ctr + kSActive, s.noff + s.nV, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
   RM_HIP(hipGetLastError());
   s.read_ctr(st);
@@ -933,8 +835,8 @@ void Session::snapshot_clear() {
   RM_HIP(hipMemsetAsync(s.cnt, 0, V * 4, st));
   RM_HIP(hipMemsetAsync(s.max_sep, 0, V * 4, st));
   RM_HIP(hipMemsetAsync(s.last_update, 0, V * 8, st));
-  hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, s.nV, s.scan_from, 1u);
-  hipLaunchKernelGGL(k_sess_fill, dim3(grid(V)), dim3(256), 0, st, s.nV, s.try_from, 1u);
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(V)), dim3(256), 0, st, s.nV, s.scan_from, 1u);
+  hipLaunchKernelGGL(k_fill<uint32_t>, dim3(grid(V)), dim3(256), 0, st, s.nV, s.try_from, 1u);
   RM_HIP(hipGetLastError());
   RM_HIP(hipStreamSynchronize(st));
   s.extent = 0;
@@ -947,7 +849,7 @@ SessionSnap Session::snap_view(uint64_t n_points, uint32_t n_live) {
   v.n_vehicles = s.nV; v.n_live = n_live; v.n_points = n_points;
   v.off = s.off; v.cnt = s.cnt; v.scan_from = s.scan_from; v.try_from = s.try_from; v.max_sep = s.max_sep;
   v.last_update = s.last_update; v.rank = s.noff;
-  const PtBuf& b = s.buf[s.cur];
+  const PtStore& b = s.buf[s.cur];
   v.lon = b.lon; v.lat = b.lat; v.acc = b.acc; v.time = b.time; v.arr = b.arr; v.veh = b.veh;
   v.stream = s.m->stream_;
   return v;

@@ -47,8 +47,6 @@ struct SumSecs {   // the sections of one k_snap_sum launch, by value
   unsigned long long off[kMaxSecs], bytes[kMaxSecs], dst[kMaxSecs];   // dst: byte offset of the u64 that takes the sum
 };
 
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)std::max<uint64_t>((n + b - 1) / b, 1); }
-
 // the block's values summed into *dst by one atomic: shuffles inside each wave, LDS across the waves
 __device__ __forceinline__ void block_add(unsigned long long* dst, unsigned long long v) {
   __shared__ unsigned long long part[kSumThreads / 64];
@@ -149,43 +147,13 @@ __global__ void k_snap_point_veh(uint64_t n, SessionSnap v) {
   v.arr[q] = kNone;
 }
 
-struct DevMem {   // a call's device buffer
-  void* p = nullptr;
-  void need(uint64_t bytes, const char* what) {
-    const hipError_t e = hipMalloc(&p, std::max<uint64_t>(bytes, 16));
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      p = nullptr;
-      throw BatchTooLarge(what);
-    }
-    RM_HIP(e);
-  }
-  ~DevMem() { if (p) (void)hipFree(p); }
-};
+constexpr const char* kSnapFull = "the snapshot does not fit in HBM";
 
-struct Parts {   // HIP-event pairs of a call's parts
-  static constexpr int kN = 4;
-  hipEvent_t ev[kN][2] = {};
-  bool used[kN] = {};
-  hipStream_t st = nullptr;
-  explicit Parts(hipStream_t s) : st(s) {
-    for (auto& e : ev) { RM_HIP(hipEventCreate(&e[0])); RM_HIP(hipEventCreate(&e[1])); }
-  }
-  ~Parts() {
-    for (auto& e : ev) { if (e[0]) (void)hipEventDestroy(e[0]); if (e[1]) (void)hipEventDestroy(e[1]); }
-  }
-  void tic(int k) { RM_HIP(hipEventRecord(ev[k][0], st)); }
-  void toc(int k) { RM_HIP(hipEventRecord(ev[k][1], st)); used[k] = true; }
-  void read(double ms[6]) {   // after a stream synchronise
-    if (!ms) return;
-    for (int k = 0; k < 6; ++k) ms[k] = 0.0;
-    for (int k = 0; k < kN; ++k) {
-      float t = 0.f;
-      if (used[k] && hipEventElapsedTime(&t, ev[k][0], ev[k][1]) == hipSuccess) ms[k] = t;
-      else if (used[k]) (void)hipGetLastError();
-    }
-  }
-};
+// a call's part times into its ms[6] (null: dropped), after a stream synchronise
+void read_parts(PartTimer& ev, double ms[6]) {
+  if (ms) for (int k = 0; k < 6; ++k) ms[k] = 0.0;
+  ev.harvest(ms);
+}
 
 void launch_sum(const uint8_t* blob, const std::vector<snap::Entry>& ent, const std::vector<uint64_t>& dst, uint8_t* dst_base,
                 hipStream_t st) {
@@ -225,10 +193,10 @@ void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, siz
   if (t) RM_HIP(hipStreamSynchronize(t->stream()));
   SessionSnap v;
   hipStream_t st = s ? s->stream() : (t ? t->stream() : nullptr);
-  Parts ev(st);
-  ev.tic(0);   // pack: the store as get_store packs it, the non-empty vehicles ranked
+  PartTimer ev;
+  ev.tic(0, st);   // pack: the store as get_store packs it, the non-empty vehicles ranked
   if (s) v = s->snapshot_pack();
-  ev.toc(0);   // (the pack synchronises and reads its counts back: the pair spans that read, and no more)
+  ev.toc(st);   // (the pack synchronises and reads its counts back: the pair spans that read, and no more)
   const uint32_t n_names = d ? d->size() : 0u;
   const uint64_t name_bytes = d ? d->name_bytes() : 0, n_rows = t ? t->rows_held() : 0;
   if (v.n_points >= 0xffffffffull) throw BatchTooLarge("session store too large (points >= 2^32)");
@@ -242,14 +210,14 @@ void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, siz
   }
   if (t) { w.add(snap::kTileRows, nullptr, n_rows); w.add(snap::kTileMeta, nullptr, 1); }
   const uint64_t len = w.layout();
-  DevMem buf;
-  buf.need(len, "the snapshot does not fit in HBM");
-  uint8_t* b = (uint8_t*)buf.p;
+  DevBuf<uint8_t> buf;
+  buf.reserve(std::max<uint64_t>(len, 16), kSnapFull);
+  uint8_t* b = buf;
   char* host = (char*)std::malloc(len);
   if (!host) throw std::bad_alloc();
   try {
     snap::TileMeta meta{};
-    ev.tic(1);   // gather: records by rank, points, names and rows into the blob's layout
+    ev.tic(1, st);   // gather: records by rank, points, names and rows into the blob's layout
     RM_HIP(hipMemsetAsync(b, 0, len, st));
     std::vector<uint64_t> dst(w.ent.size());
     for (size_t k = 0; k < w.ent.size(); ++k) {
@@ -278,13 +246,13 @@ void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, siz
       if (src && e.bytes) RM_HIP(hipMemcpyAsync(at, src, e.bytes, hipMemcpyDeviceToDevice, st));
     }
     RM_HIP(hipGetLastError());
-    ev.toc(1);
-    ev.tic(2);   // checksum: every section's sum into its table entry in the buffer
+    ev.toc(st);
+    ev.tic(2, st);   // checksum: every section's sum into its table entry in the buffer
     launch_sum(b, w.ent, dst, b, st);
-    ev.toc(2);
-    ev.tic(3);   // the one download
+    ev.toc(st);
+    ev.tic(3, st);   // the one download
     RM_HIP(hipMemcpyAsync(host, b, len, hipMemcpyDeviceToHost, st));
-    ev.toc(3);
+    ev.toc(st);
     RM_HIP(hipStreamSynchronize(st));
     for (size_t k = 0; k < w.ent.size(); ++k) std::memcpy(&w.ent[k].sum, host + dst[k], 8);
     w.seal(host, len);
@@ -292,7 +260,7 @@ void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, siz
     std::free(host);
     throw;
   }
-  ev.read(ms);
+  read_parts(ev, ms);
   *blob_out = host;
   *len_out = len;
   if (out) { out[0] = len; out[1] = n_names; out[2] = v.n_live; out[3] = v.n_points; out[4] = n_rows; out[5] = user_len; }
@@ -314,22 +282,23 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
   if (t) RM_HIP(hipStreamSynchronize(t->stream()));
   hipStream_t st = s ? s->stream() : (t ? t->stream() : nullptr);
   if (s && s->snapshot_pack().n_points) throw std::runtime_error("snapshot: the session is not empty");
-  Parts ev(st);
+  PartTimer ev;
   // ---- one upload, the checksums and the checks; they write the check block alone
   std::vector<snap::Entry> ent;
   std::vector<uint64_t> dst;
   for (uint32_t k = 1; k < snap::kNumKinds; ++k)
     if (tb.has[k]) { ent.push_back(tb.ent[k]); dst.push_back((2 + ent.size() - 1) * 8); }
-  DevMem buf, chk_mem;
-  buf.need(len, "the snapshot does not fit in HBM");
-  chk_mem.need(32 * 8, "the snapshot does not fit in HBM");
-  const uint8_t* b = (const uint8_t*)buf.p;
-  unsigned long long* chk = (unsigned long long*)chk_mem.p;
+  DevBuf<uint8_t> buf;
+  DevBuf<unsigned long long> chk_mem;
+  buf.reserve(std::max<uint64_t>(len, 16), kSnapFull);
+  chk_mem.reserve(32, kSnapFull);
+  const uint8_t* b = buf;
+  unsigned long long* chk = chk_mem;
   unsigned long long h[32];
-  ev.tic(0);
-  RM_HIP(hipMemcpyAsync(buf.p, blob, len, hipMemcpyHostToDevice, st));
-  ev.toc(0);
-  ev.tic(1);
+  ev.tic(0, st);
+  RM_HIP(hipMemcpyAsync(buf, blob, len, hipMemcpyHostToDevice, st));
+  ev.toc(st);
+  ev.tic(1, st);
   RM_HIP(hipMemsetAsync(chk, 0, 32 * 8, st));
   launch_sum(b, ent, dst, (uint8_t*)chk, st);
   const uint64_t n_rec = tb.vehicles(), n_pts = tb.points(), n_names = tb.names(), n_rows = tb.rows();
@@ -343,7 +312,7 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
     hipLaunchKernelGGL(k_snap_check_names, dim3(grid(n_names)), dim3(256), 0, st, noff, n_names, tb.ent[snap::kDirBytes].bytes, chk);
   RM_HIP(hipGetLastError());
   RM_HIP(hipMemcpyAsync(h, chk, 32 * 8, hipMemcpyDeviceToHost, st));
-  ev.toc(1);
+  ev.toc(st);
   RM_HIP(hipStreamSynchronize(st));
   uint64_t bits = h[0];
   for (size_t k = 0; k < ent.size(); ++k)
@@ -353,15 +322,13 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
   // ---- the unpack: room first (a full HBM shows before anything is written), the names, the rest
   SessionSnap v;
   void* rows = nullptr;
-  DevMem tmp;
-  size_t tmp_bytes = 0;
+  ScanScratch scr("the snapshot's scan does not fit in HBM");
   if (s) {
     v = s->snapshot_room(n_pts);
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, v.cnt, v.off, (int)v.n_vehicles, st));
-    tmp.need(tmp_bytes, "the snapshot's scan does not fit in HBM");
+    scr.presize<false>(v.n_vehicles, st);
   }
   if (t) rows = t->snapshot_room(n_rows);
-  ev.tic(2);
+  ev.tic(2, st);
   if (d) {
     d->snapshot_insert((uint32_t)n_names, noff, b + tb.ent[snap::kDirBytes].off, tb.ent[snap::kDirBytes].bytes, chk, snap::kEDupName, st);
     RM_HIP(hipMemcpyAsync(h, chk, 8, hipMemcpyDeviceToHost, st));
@@ -374,7 +341,7 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
   try {
     if (s) {
       if (n_rec) hipLaunchKernelGGL(k_snap_scatter, dim3(grid(n_rec)), dim3(256), 0, st, recs, (uint32_t)n_rec, v);
-      RM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tmp_bytes, v.cnt, v.off, (int)v.n_vehicles, st));
+      scr.scan<uint32_t>(v.cnt, v.off, v.n_vehicles, st);
       if (n_pts) {
         RM_HIP(hipMemcpyAsync(v.lon, b + tb.ent[snap::kSessLon].off, n_pts * 4, hipMemcpyDeviceToDevice, st));
         RM_HIP(hipMemcpyAsync(v.lat, b + tb.ent[snap::kSessLat].off, n_pts * 4, hipMemcpyDeviceToDevice, st));
@@ -385,7 +352,7 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
     }
     if (t && n_rows) RM_HIP(hipMemcpyAsync(rows, b + tb.ent[snap::kTileRows].off, n_rows * snap::kRowBytes, hipMemcpyDeviceToDevice, st));
     RM_HIP(hipGetLastError());
-    ev.toc(2);
+    ev.toc(st);
     RM_HIP(hipStreamSynchronize(st));
   } catch (...) {   // written in part: every target goes back to empty (the store's rows do not count until snapshot_loaded)
     if (d) { try { d->snapshot_clear(st); } catch (...) {} }
@@ -394,7 +361,7 @@ void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, siz
   }
   if (s) s->snapshot_loaded(n_pts);
   if (t) t->snapshot_loaded(n_rows, snap::tile_meta(blob, tb).arrivals);
-  ev.read(ms);
+  read_parts(ev, ms);
   if (out) { out[0] = len; out[1] = n_names; out[2] = n_rec; out[3] = n_pts; out[4] = n_rows; out[5] = tb.ent[snap::kUser].bytes; }
 }
 

@@ -20,21 +20,11 @@
 #include <string>
 
 #include "engine.hpp"
+#include "tile_cull.hpp"
 
 namespace rm {
 
 namespace {
-
-template <class T>
-T* salloc(std::vector<void*>& list, uint64_t n) {
-  void* p = nullptr;
-  if (n == 0) n = 1;
-  RM_HIP(hipMalloc(&p, n * sizeof(T)));
-  list.push_back(p);
-  return (T*)p;
-}
-
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)((n + b - 1) / b); }
 
 // ---------------------------------------------------------------- windows
 __global__ void k_pt_keys(uint64_t n, const uint32_t* uuid, const double* time, double tbase,
@@ -203,58 +193,9 @@ __global__ void k_tile_key(uint64_t n, const TileRow* rows, const uint32_t* perm
   key[k] = which == 0 ? dec_key(t.next_id, err) : (which == 1 ? dec_key(t.id, err) : file_key(t));
 }
 
-__global__ void k_iota(uint64_t n, uint32_t* v) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) v[k] = (uint32_t)k;
-}
-
-// runs of equal (file, id, next_id) in sorted order
-__global__ void k_tile_gflags(uint64_t n, const TileRow* rows, const uint32_t* perm, uint32_t* flag) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  uint32_t f = 1;
-  if (k > 0) {
-    const TileRow& a = rows[perm[k - 1]];
-    const TileRow& b = rows[perm[k]];
-    f = (file_key(a) != file_key(b) || a.id != b.id || a.next_id != b.next_id) ? 1u : 0u;
-  }
-  flag[k] = f;
-}
-
-__global__ void k_tile_gpos(uint64_t n, const uint32_t* flag, const uint32_t* gid, uint32_t* gpos, uint32_t* hctl) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  if (flag[k]) gpos[gid[k]] = (uint32_t)k;
-  if (k + 1 == n) {
-    const uint32_t G = gid[k] + flag[k];
-    gpos[G] = (uint32_t)n;
-    hctl[1] = G;
-  }
-}
-
-// The reference's cull loop (:221-239) as a rule over the runs of one file: a run is kept
-// iff it has >= privacy rows, except that the loop's end-of-list step closes the open run
-// together with the final line, so a final run of one row shares the fate of the run
-// before it, judged on their joint size (pinned by tests/golden/tiles_golden.json).
-__global__ void k_tile_gkeep(uint32_t G, const TileRow* rows, const uint32_t* perm, const uint32_t* gpos,
-                             uint32_t privacy, uint8_t* keep) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= G) return;
-  auto fkey = [&](uint32_t x) { return file_key(rows[perm[gpos[x]]]); };
-  auto size = [&](uint32_t x) { return gpos[x + 1] - gpos[x]; };
-  auto file_last = [&](uint32_t x) { return x + 1 == G || fkey(x + 1) != fkey(x); };
-  auto file_first = [&](uint32_t x) { return x == 0 || fkey(x - 1) != fkey(x); };
-  const uint32_t sz = size(g);
-  bool k = sz >= privacy;
-  if (file_last(g) && sz == 1 && !file_first(g)) k = size(g - 1) + 1 >= privacy;
-  if (!file_last(g) && file_last(g + 1) && size(g + 1) == 1) k = sz + 1 >= privacy;
-  keep[g] = k ? 1 : 0;
-}
-
-__global__ void k_tile_kflags(uint64_t n, const uint32_t* gid, const uint32_t* gfl, const uint8_t* keep, uint32_t* flag) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) flag[k] = keep[gid[k] + gfl[k] - 1u];   // exclusive scan of run starts -> run of k
-}
+struct TileSameFile {
+  __device__ bool operator()(const TileRow& a, const TileRow& b) const { return file_key(a) == file_key(b); }
+};
 
 __global__ void k_tile_out(uint64_t n, const TileRow* rows, const uint32_t* perm, const uint32_t* flag,
                            const uint32_t* ofs, TileRow* out, uint32_t* hctl) {
@@ -277,80 +218,44 @@ void format_row(std::string& o, const TileRow& t, const TileParams& tp) {
 
 }  // namespace
 
-StageBufs::~StageBufs() {
-  for (void* p : allocs) (void)hipFree(p);
-  if (hctl) (void)hipHostFree(hctl);
-}
-
-static size_t sort_tmp_bytes(uint64_t n, hipStream_t st) {
-  size_t a = 0, b = 0;
-  RM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, a, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                            (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 64, st));
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, st));
-  return std::max(a, b);
-}
-
 void Matcher::ensure_points(uint64_t n, uint32_t n_uuids, uint32_t n_opts) {
   StageBufs& s = sb_;
-  if (!s.hctl) RM_HIP(hipHostMalloc((void**)&s.hctl, 16 * sizeof(uint32_t), hipHostMallocDefault));
+  if (!s.hctl) s.hctl.reserve(16);
   if (n <= s.cap_pts && n_uuids <= s.cap_uuids && s.p_opts && n_opts <= 64) return;
   if (n_opts > 64) throw std::runtime_error("at most 64 option sets per point batch");
-  // points and rows share nothing; drop the point buffers only
+  // points and rows share nothing; the point buffers only
   const uint64_t c = std::max<uint64_t>(n, s.cap_pts) + 64;
   const uint32_t cu = std::max<uint32_t>(n_uuids, s.cap_uuids) + 16;
-  auto drop = [&](void*& p) { if (p) { (void)hipFree(p); s.allocs.erase(std::find(s.allocs.begin(), s.allocs.end(), p)); p = nullptr; } };
-  void** ptrs[] = {(void**)&s.p_uuid, (void**)&s.p_time, (void**)&s.p_lon, (void**)&s.p_lat, (void**)&s.p_acc,
-                   (void**)&s.p_uopt, (void**)&s.p_opts, (void**)&s.k0, (void**)&s.k1, (void**)&s.v0, (void**)&s.v1,
-                   (void**)&s.flag, (void**)&s.idx, (void**)&s.wstart, (void**)&s.wcnt, (void**)&s.wofs,
-                   (void**)&s.wflag, (void**)&s.widx, (void**)&s.trace_uuid, (void**)&s.tmp};
-  for (void** p : ptrs) drop(*p);
-  std::vector<void*>& L = s.allocs;
-  s.p_uuid = salloc<uint32_t>(L, c); s.p_time = salloc<double>(L, c); s.p_lon = salloc<float>(L, c);
-  s.p_lat = salloc<float>(L, c); s.p_acc = salloc<float>(L, c); s.p_uopt = salloc<uint32_t>(L, cu);
-  s.p_opts = salloc<MatchOptions>(L, 64);
-  s.k0 = salloc<unsigned long long>(L, c); s.k1 = salloc<unsigned long long>(L, c);
-  s.v0 = salloc<uint32_t>(L, c); s.v1 = salloc<uint32_t>(L, c);
-  s.flag = salloc<uint32_t>(L, c); s.idx = salloc<uint32_t>(L, c); s.wstart = salloc<uint32_t>(L, c + 1);
-  s.wcnt = salloc<uint32_t>(L, c); s.wofs = salloc<uint32_t>(L, c); s.wflag = salloc<uint32_t>(L, c);
-  s.widx = salloc<uint32_t>(L, c); s.trace_uuid = salloc<uint32_t>(L, c);
-  s.tmp_bytes = std::max(s.tmp_bytes, sort_tmp_bytes(std::max<uint64_t>(std::max<uint64_t>(c, s.cap_rows), s.cap_tr), stream_));
-  s.tmp = salloc<char>(L, s.tmp_bytes);
+  s.cap_pts = 0;   // (a reserve that throws leaves no capacity claimed)
+  s.cap_uuids = 0;
+  s.p_uuid.reserve(c); s.p_time.reserve(c); s.p_lon.reserve(c); s.p_lat.reserve(c); s.p_acc.reserve(c);
+  s.p_uopt.reserve(cu); s.p_opts.reserve(64);
+  s.k0.reserve(c); s.k1.reserve(c); s.v0.reserve(c); s.v1.reserve(c);
+  s.flag.reserve(c); s.idx.reserve(c); s.wstart.reserve(c + 1); s.wcnt.reserve(c); s.wofs.reserve(c);
+  s.wflag.reserve(c); s.widx.reserve(c); s.trace_uuid.reserve(c);
+  s.scr.presize<true>(std::max<uint64_t>(std::max<uint64_t>(c, s.cap_rows), s.cap_tr), stream_);
   s.cap_pts = c;
   s.cap_uuids = cu;
 }
 
 void Matcher::ensure_rows(uint64_t n, uint32_t traces) {
   StageBufs& s = sb_;
-  if (!s.hctl) RM_HIP(hipHostMalloc((void**)&s.hctl, 16 * sizeof(uint32_t), hipHostMallocDefault));
-  if (!s.derr) s.derr = salloc<uint32_t>(s.allocs, 1);
+  if (!s.hctl) s.hctl.reserve(16);
+  if (!s.derr) s.derr.reserve(1);
   if (traces > s.cap_tr || !s.tcnt) {
-    auto dropt = [&](uint32_t*& p) { if (p) { (void)hipFree(p); s.allocs.erase(std::find(s.allocs.begin(), s.allocs.end(), (void*)p)); p = nullptr; } };
-    dropt(s.tcnt); dropt(s.tofs);
-    s.cap_tr = std::max<uint32_t>(traces, s.cap_tr) + 64;
-    s.tcnt = salloc<uint32_t>(s.allocs, s.cap_tr);
-    s.tofs = salloc<uint32_t>(s.allocs, s.cap_tr);
-    if (s.rows) {  // the scan scratch must cover the trace count too
-      const size_t need = sort_tmp_bytes(s.cap_tr, stream_);
-      if (need > s.tmp_bytes) {
-        (void)hipFree(s.tmp); s.allocs.erase(std::find(s.allocs.begin(), s.allocs.end(), s.tmp));
-        s.tmp_bytes = need; s.tmp = salloc<char>(s.allocs, need);
-      }
-    }
+    const uint32_t ct = std::max<uint32_t>(traces, s.cap_tr) + 64;
+    s.tcnt.reset();   // (tcnt last: the test above sees either reserve that threw)
+    s.tofs.reserve(ct); s.tcnt.reserve(ct);
+    s.cap_tr = ct;
+    if (s.rows) s.scr.presize<true>(s.cap_tr, stream_);   // the scan scratch must cover the trace count too
   }
   if (n <= s.cap_rows && s.rows) return;
   const uint64_t c = std::max<uint64_t>(n, s.cap_rows) + n / 4 + 1024;
-  auto drop = [&](void*& p) { if (p) { (void)hipFree(p); s.allocs.erase(std::find(s.allocs.begin(), s.allocs.end(), p)); p = nullptr; } };
-  void** ptrs[] = {(void**)&s.rows, (void**)&s.rows2, (void**)&s.rk, (void**)&s.rk2, (void**)&s.rperm,
-                   (void**)&s.rperm2, (void**)&s.rflag, (void**)&s.ridx, (void**)&s.gpos, (void**)&s.gkeep, (void**)&s.tmp};
-  for (void** p : ptrs) drop(*p);
-  std::vector<void*>& L = s.allocs;
-  s.rows = salloc<TileRow>(L, c); s.rows2 = salloc<TileRow>(L, c);
-  s.rk = salloc<unsigned long long>(L, c); s.rk2 = salloc<unsigned long long>(L, c);
-  s.rperm = salloc<uint32_t>(L, c); s.rperm2 = salloc<uint32_t>(L, c);
-  s.rflag = salloc<uint32_t>(L, c); s.ridx = salloc<uint32_t>(L, c);
-  s.gpos = salloc<uint32_t>(L, c + 1); s.gkeep = salloc<uint8_t>(L, c);
-  s.tmp_bytes = std::max(s.tmp_bytes, sort_tmp_bytes(std::max<uint64_t>(std::max<uint64_t>(c, s.cap_pts), s.cap_tr), stream_));
-  s.tmp = salloc<char>(L, s.tmp_bytes);
+  s.cap_rows = 0;   // (a reserve that throws leaves no capacity claimed)
+  s.rows.reserve(c); s.rows2.reserve(c); s.rk.reserve(c); s.rk2.reserve(c);
+  s.rperm.reserve(c); s.rperm2.reserve(c); s.rflag.reserve(c); s.ridx.reserve(c);
+  s.gpos.reserve(c + 1); s.gkeep.reserve(c);
+  s.scr.presize<true>(std::max<uint64_t>(std::max<uint64_t>(c, s.cap_pts), s.cap_tr), stream_);
   s.cap_rows = c;
 }
 
@@ -391,23 +296,19 @@ void Matcher::run_points(const PointsDesc& pd, const RunParams& rp) {
 }
 
 void Matcher::run_points_device(uint64_t n, double tbase, double inactivity, const MatchOptions* opts, uint32_t n_opts,
-                                uint32_t n_uopt, const RunParams& rp, hipEvent_t windows_done) {
+                                uint32_t n_uopt, const RunParams& rp, PartTimer* windows_done) {
   StageBufs& s = sb_;
   hipStream_t st = stream_;
   hipLaunchKernelGGL(k_pt_keys, dim3(grid(n)), dim3(256), 0, st, n, s.p_uuid, s.p_time, tbase, s.k0, s.v0);
-  size_t tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.k0, s.k1, s.v0, s.v1, (int)n, 0, 64, st));
+  s.scr.sort_pairs(s.k0.get(), s.k1.get(), s.v0, s.v1, n, 64, st);
   hipLaunchKernelGGL(k_win_flags, dim3(grid(n)), dim3(256), 0, st, n, s.k1, s.v1, s.p_time, inactivity, s.flag);
-  tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.flag, s.idx, (int)n, st));
+  s.scr.scan<uint32_t>(s.flag, s.idx, n, st);
   hipLaunchKernelGGL(k_win_starts, dim3(grid(n)), dim3(256), 0, st, n, s.flag, s.idx, s.wstart, s.hctl);
   RM_HIP(hipStreamSynchronize(st));
   const uint32_t W = s.hctl[0];
   hipLaunchKernelGGL(k_win_sizes, dim3(grid(W)), dim3(256), 0, st, W, s.wstart, s.wcnt, s.wflag);
-  tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.wcnt, s.wofs, (int)W, st));
-  tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.wflag, s.widx, (int)W, st));
+  s.scr.scan<uint32_t>(s.wcnt, s.wofs, W, st);
+  s.scr.scan<uint32_t>(s.wflag, s.widx, W, st);
   RM_HIP(hipMemcpyAsync(s.hctl + 4, s.wofs + (W - 1), 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipMemcpyAsync(s.hctl + 5, s.wcnt + (W - 1), 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipMemcpyAsync(s.hctl + 6, s.widx + (W - 1), 4, hipMemcpyDeviceToHost, st));
@@ -427,7 +328,7 @@ void Matcher::run_points_device(uint64_t n, double tbase, double inactivity, con
                      w.lon, w.lat, w.acc, w.trace_off, w.trace_opt, s.trace_uuid);
   const uint32_t Pu = (uint32_t)P;
   RM_HIP(hipMemcpyAsync(w.trace_off + T, &Pu, 4, hipMemcpyHostToDevice, st));
-  if (windows_done) RM_HIP(hipEventRecord(windows_done, st));
+  if (windows_done) windows_done->toc(st);
   RM_HIP(hipStreamSynchronize(st));
   run_device(rp);
 }
@@ -467,8 +368,7 @@ std::string Matcher::tiles(const TileParams& tp, TileComm* comm) {
     uint32_t* cnt = s.tcnt;
     uint32_t* ofs = s.tofs;
     hipLaunchKernelGGL(k_tile_count, dim3(grid(T, 64)), dim3(64), 0, st, a, cnt);
-    size_t tmp = s.tmp_bytes;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, cnt, ofs, (int)T, st));
+    s.scr.scan<uint32_t>(cnt, ofs, T, st);
     RM_HIP(hipMemcpyAsync(s.hctl + 8, ofs + (T - 1), 4, hipMemcpyDeviceToHost, st));
     RM_HIP(hipMemcpyAsync(s.hctl + 9, cnt + (T - 1), 4, hipMemcpyDeviceToHost, st));
     RM_HIP(hipStreamSynchronize(st));
@@ -486,8 +386,7 @@ std::string Matcher::tiles(const TileParams& tp, TileComm* comm) {
       if (Rm > R) RM_HIP(hipMemsetAsync(s.rows + R, 0, (Rm - R) * sizeof(TileRow), st));   // padding rows: pad[0] = 0
       comm->allgather(s.rows, s.rows2, Rm * sizeof(TileRow), st);
       hipLaunchKernelGGL(k_tile_own, dim3(grid(all)), dim3(256), 0, st, all, s.rows2, comm->rank, comm->nranks, s.rflag);
-      size_t tmp = s.tmp_bytes;
-      RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.rflag, s.ridx, (int)all, st));
+      s.scr.scan<uint32_t>(s.rflag, s.ridx, all, st);
       hipLaunchKernelGGL(k_tile_compact, dim3(grid(all)), dim3(256), 0, st, all, s.rows2, s.rflag, s.ridx, s.rows);
       RM_HIP(hipMemcpyAsync(s.hctl + 8, s.ridx + (all - 1), 4, hipMemcpyDeviceToHost, st));
       RM_HIP(hipMemcpyAsync(s.hctl + 9, s.rflag + (all - 1), 4, hipMemcpyDeviceToHost, st));
@@ -502,30 +401,28 @@ std::string Matcher::tiles(const TileParams& tp, TileComm* comm) {
   // ---- sort by (file, id string, next_id string): three stable LSD passes
   uint32_t* derr = s.derr;
   RM_HIP(hipMemsetAsync(derr, 0, 4, st));
-  hipLaunchKernelGGL(k_iota, dim3(grid(R)), dim3(256), 0, st, R, s.rperm);
+  hipLaunchKernelGGL(k_iota<uint64_t>, dim3(grid(R)), dim3(256), 0, st, R, s.rperm);
   uint32_t* pin = s.rperm;
   uint32_t* pout = s.rperm2;
   for (int pass = 0; pass < 3; ++pass) {
     hipLaunchKernelGGL(k_tile_key, dim3(grid(R)), dim3(256), 0, st, R, s.rows, pin, pass, s.rk, derr);
-    size_t tmp = s.tmp_bytes;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(s.tmp, tmp, s.rk, s.rk2, pin, pout, (int)R, 0, pass == 2 ? 64 : 52, st));
+    s.scr.sort_pairs(s.rk.get(), s.rk2.get(), pin, pout, R, pass == 2 ? 64 : 52, st);
     std::swap(pin, pout);
   }
   const uint32_t* perm = pin;
   // ---- runs, cull rule, compaction in sorted order
-  hipLaunchKernelGGL(k_tile_gflags, dim3(grid(R)), dim3(256), 0, st, R, s.rows, perm, s.rflag);
-  size_t tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, s.rflag, s.ridx, (int)R, st));
-  hipLaunchKernelGGL(k_tile_gpos, dim3(grid(R)), dim3(256), 0, st, R, s.rflag, s.ridx, s.gpos, s.hctl);
+  hipLaunchKernelGGL((k_cull_gflags<TileSameFile, TileRow>), dim3(grid(R)), dim3(256), 0, st, R, s.rows, perm, s.rflag);
+  s.scr.scan<uint32_t>(s.rflag, s.ridx, R, st);
+  hipLaunchKernelGGL(k_cull_gpos<uint32_t>, dim3(grid(R)), dim3(256), 0, st, R, s.rflag, s.ridx, s.gpos, s.hctl + 1);
   RM_HIP(hipMemcpyAsync(s.hctl + 12, derr, 4, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
   if (s.hctl[12]) throw std::runtime_error("segment id with more than 15 decimal digits in a tile row");
   const uint32_t G = s.hctl[1];
-  hipLaunchKernelGGL(k_tile_gkeep, dim3(grid(G)), dim3(256), 0, st, G, s.rows, perm, s.gpos, tp.privacy, s.gkeep);
+  hipLaunchKernelGGL((k_cull_gkeep<TileSameFile, false, TileRow>), dim3(grid(G)), dim3(256), 0, st, G, s.rows, perm, s.gpos,
+                     tp.privacy, s.gkeep, nullptr);
   uint32_t* kflag = pout;  // the spare permutation buffer
-  hipLaunchKernelGGL(k_tile_kflags, dim3(grid(R)), dim3(256), 0, st, R, s.ridx, s.rflag, s.gkeep, kflag);
-  tmp = s.tmp_bytes;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(s.tmp, tmp, kflag, s.rflag, (int)R, st));
+  hipLaunchKernelGGL(k_cull_kflags<uint8_t>, dim3(grid(R)), dim3(256), 0, st, R, s.ridx, s.rflag, s.gkeep, kflag);
+  s.scr.scan<uint32_t>(kflag, s.rflag, R, st);
   hipLaunchKernelGGL(k_tile_out, dim3(grid(R)), dim3(256), 0, st, R, s.rows, perm, kflag, s.rflag, s.rows2, s.hctl);
   RM_HIP(hipStreamSynchronize(st));
   const uint32_t K = s.hctl[2];

@@ -25,6 +25,7 @@
 #include <string>
 
 #include "engine.hpp"
+#include "tile_cull.hpp"
 #include "tile_text.hpp"
 
 namespace rm {
@@ -56,8 +57,6 @@ __device__ __forceinline__ SegIn load_seg(SegSrc s, uint64_t j) {
   g.length = *(const int32_t*)(p + 32); g.queue = *(const int32_t*)(p + 36);
   return g;
 }
-
-inline uint32_t grid(uint64_t n, uint32_t b = 256) { return (uint32_t)std::max<uint64_t>((n + b - 1) / b, 1); }
 
 // one atomic per block for a predicate's count; every thread of the block calls it
 __device__ __forceinline__ void block_count(unsigned long long* c, bool p) {
@@ -119,11 +118,6 @@ __global__ void k_ts_emit(SegSrc s, uint64_t n, uint64_t q, const unsigned long 
   }
 }
 
-__global__ void k_ts_iota(uint64_t n, uint32_t* v) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) v[k] = (uint32_t)k;
-}
-
 // sort key of a pass: 0 next_id, 1 id (Segment.compareTo, least significant first), 2 tile, 3 bucket
 __global__ void k_ts_key(uint64_t n, const TileStoreRow* rows, const uint32_t* perm, int which, unsigned long long* key) {
   const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,57 +130,9 @@ __device__ __forceinline__ bool same_file(const TileStoreRow& a, const TileStore
   return a.bucket == b.bucket && a.tile == b.tile;
 }
 
-// starts of the runs of equal (file, id, next_id) in sorted order
-__global__ void k_ts_gflags(uint64_t n, const TileStoreRow* rows, const uint32_t* perm, uint32_t* flag) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  uint32_t f = 1u;
-  if (k > 0) {
-    const TileStoreRow& a = rows[perm[k - 1]];
-    const TileStoreRow& b = rows[perm[k]];
-    f = (!same_file(a, b) || a.id != b.id || a.next_id != b.next_id) ? 1u : 0u;
-  }
-  flag[k] = f;
-}
-
-__global__ void k_ts_gpos(uint64_t n, const uint32_t* flag, const uint32_t* gid, uint32_t* gpos, unsigned long long* ctr) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  if (flag[k]) gpos[gid[k]] = (uint32_t)k;
-  if (k + 1 == n) {
-    const uint32_t G = gid[k] + flag[k];
-    gpos[G] = (uint32_t)n;
-    ctr[kTRuns] = G;
-  }
-}
-
-// clean() (AnonymisingProcessor.java:155-175) as a rule over the runs of one file -- the rule of
-// stages.hip k_tile_gkeep, whose Python loop is this Java loop: a run is kept iff it has >= privacy
-// rows, except that the end-of-list step (:162-165) closes the open run together with the final
-// row, so a final run of one row that is not the file's only run shares the fate of the run before
-// it, and the two are judged on their joint size.  Also counts the files held.
-__global__ void k_ts_gkeep(uint32_t G, const TileStoreRow* rows, const uint32_t* perm, const uint32_t* gpos, uint32_t privacy,
-                           uint8_t* keep, unsigned long long* ctr) {
-  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
-  bool first = false;
-  if (g < G) {
-    auto row = [&](uint32_t x) -> const TileStoreRow& { return rows[perm[gpos[x]]]; };
-    auto size = [&](uint32_t x) { return gpos[x + 1] - gpos[x]; };
-    auto file_last = [&](uint32_t x) { return x + 1 == G || !same_file(row(x + 1), row(x)); };
-    first = g == 0 || !same_file(row(g - 1), row(g));
-    const uint32_t sz = size(g);
-    bool k = sz >= privacy;
-    if (file_last(g) && sz == 1 && !first) k = size(g - 1) + 1 >= privacy;
-    if (!file_last(g) && file_last(g + 1) && size(g + 1) == 1) k = sz + 1 >= privacy;
-    keep[g] = k ? 1 : 0;
-  }
-  block_count(ctr + kTTiles, first);
-}
-
-__global__ void k_ts_kflags(uint64_t n, const uint32_t* gid, const uint32_t* gfl, const uint8_t* keep, uint32_t* flag) {
-  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k < n) flag[k] = keep[gid[k] + gfl[k] - 1u];   // exclusive scan of run starts -> run of k
-}
+struct TsSameFile {
+  __device__ bool operator()(const TileStoreRow& a, const TileStoreRow& b) const { return same_file(a, b); }
+};
 
 // the kept rows' store indices in sorted order
 __global__ void k_ts_compact(uint64_t n, const uint32_t* perm, const uint32_t* flag, const uint32_t* ofs, uint32_t* kperm,
@@ -260,133 +206,72 @@ __global__ void __launch_bounds__(64) k_ts_write(uint32_t K, const TileStoreRow*
 }  // namespace
 
 struct TileStore::Impl {
+  static constexpr const char* kFull = "tile store buffers do not fit in HBM";
   int device = 0;
   TileParams tp;
   TileText tt;
   hipStream_t st = nullptr;
-  std::vector<void*> allocs;
   // the store
-  TileStoreRow* rows = nullptr;
+  DevBuf<TileStoreRow> rows;
   uint64_t n_rows = 0, cap = 0, arrivals = 0;
   // counters
-  unsigned long long* ctr = nullptr;
-  unsigned long long* hctr = nullptr;   // pinned mirror
+  DevBuf<unsigned long long> ctr;
+  PinBuf<unsigned long long> hctr;   // pinned mirror
   // add: pinned staging and its device copy, counts and offsets
-  char* hstage = nullptr; char* dstage = nullptr; uint64_t stage_cap = 0;
-  unsigned long long* cnt = nullptr; unsigned long long* ofs = nullptr; uint64_t cnt_cap = 0;
+  PinBuf<char> hstage; DevBuf<char> dstage; uint64_t stage_cap = 0;
+  DevBuf<unsigned long long> cnt, ofs; uint64_t cnt_cap = 0;
   // flush scratch (sized by the rows held)
-  unsigned long long* k0 = nullptr; unsigned long long* k1 = nullptr;
-  uint32_t* p0 = nullptr; uint32_t* p1 = nullptr; uint32_t* flag = nullptr; uint32_t* gid = nullptr; uint32_t* gpos = nullptr;
-  uint8_t* gkeep = nullptr; uint64_t fl_cap = 0;
-  char* blob = nullptr; uint64_t blob_cap = 0;
-  void* tmp = nullptr; size_t tmp_bytes = 0;
+  DevBuf<unsigned long long> k0, k1;
+  DevBuf<uint32_t> p0, p1, flag, gid, gpos;
+  DevBuf<uint8_t> gkeep; uint64_t fl_cap = 0;
+  DevBuf<char> blob; uint64_t blob_cap = 0;
+  ScanScratch scr{kFull};
   // HIP-event pairs by part: 0 upload, 1 expand, 2 sort, 3 cull, 4 text, 5 download
-  hipEvent_t ev[6][2];
-  bool ev_ok = false, used[6] = {false, false, false, false, false, false};
+  PartTimer timer;
   double ms[6] = {0, 0, 0, 0, 0, 0};
 
-  template <class T>
-  T* alloc(uint64_t n) {
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, std::max<uint64_t>(n, 1) * sizeof(T));
-    if (e == hipErrorOutOfMemory) {
-      (void)hipGetLastError();
-      throw BatchTooLarge("tile store buffers do not fit in HBM");
-    }
-    RM_HIP(e);
-    allocs.push_back(p);
-    return (T*)p;
-  }
-  template <class T>
-  void drop(T*& p) {
-    if (!p) return;
-    (void)hipFree(p);
-    allocs.erase(std::find(allocs.begin(), allocs.end(), (void*)p));
-    p = nullptr;
+  ~Impl() {
+    if (st) (void)hipStreamDestroy(st);
   }
   void begin_call() {
-    for (int i = 0; i < 6; ++i) { ms[i] = 0.0; used[i] = false; }
+    timer.harvest(nullptr);   // (pairs a call that threw left behind)
+    for (double& x : ms) x = 0.0;
     RM_HIP(hipMemsetAsync(ctr, 0, kTNumCtr * sizeof(unsigned long long), st));
-  }
-  void tic(int part) { RM_HIP(hipEventRecord(ev[part][0], st)); }
-  void toc(int part) { RM_HIP(hipEventRecord(ev[part][1], st)); used[part] = true; }
-  void harvest() {   // after a stream synchronise
-    for (int i = 0; i < 6; ++i) {
-      if (!used[i]) continue;
-      float t = 0.f;
-      if (hipEventElapsedTime(&t, ev[i][0], ev[i][1]) == hipSuccess) ms[i] += t;
-      else (void)hipGetLastError();
-      used[i] = false;
-    }
   }
   void read_ctr() {
     RM_HIP(hipMemcpyAsync(hctr, ctr, kTNumCtr * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     RM_HIP(hipStreamSynchronize(st));
-    harvest();
-  }
-  void need_tmp(size_t bytes) {
-    if (bytes <= tmp_bytes && tmp) return;
-    char* t = (char*)tmp;
-    drop(t);
-    tmp_bytes = bytes + bytes / 2 + 256;
-    tmp = alloc<char>(tmp_bytes);
-  }
-  template <class T>
-  void scan(const T* in, T* out, uint64_t n) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, b, in, out, (int)n, st));
-    need_tmp(b);
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, b, in, out, (int)n, st));
-  }
-  void sort_pairs(const unsigned long long* kin, unsigned long long* kout, const uint32_t* vin, uint32_t* vout, uint64_t n,
-                  int bits) {
-    size_t b = 0;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, b, kin, kout, vin, vout, (int)n, 0, bits, st));
-    need_tmp(b);
-    b = tmp_bytes;
-    RM_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, b, kin, kout, vin, vout, (int)n, 0, bits, st));
+    timer.harvest(ms);
   }
   // room for `need` rows: the capacity doubles and the rows held move by a device copy
   void ensure_rows(uint64_t need) {
     if (need <= cap) return;
     uint64_t c = std::max<uint64_t>(cap, 1);
     while (c < need) c *= 2;
-    TileStoreRow* r2 = alloc<TileStoreRow>(c);
-    if (n_rows) {
-      RM_HIP(hipMemcpyAsync(r2, rows, n_rows * sizeof(TileStoreRow), hipMemcpyDeviceToDevice, st));
-      RM_HIP(hipStreamSynchronize(st));
-    }
-    drop(rows);
-    rows = r2;
+    rows.reserve(c, kFull, n_rows, st);
     cap = c;
   }
   void ensure_counts(uint64_t n) {
     if (n + 1 <= cnt_cap) return;
-    drop(cnt); drop(ofs);
     cnt_cap = 0;
     const uint64_t c = std::max<uint64_t>(n + n / 2 + 1, 4096);
-    cnt = alloc<unsigned long long>(c); ofs = alloc<unsigned long long>(c);
+    cnt.reserve(c, kFull); ofs.reserve(c, kFull);
     cnt_cap = c;
   }
   void ensure_stage(uint64_t n) {
     if (n <= stage_cap) return;
-    if (hstage) (void)hipHostFree(hstage);
-    hstage = nullptr;
-    drop(dstage);
     stage_cap = 0;
     const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
-    RM_HIP(hipHostMalloc((void**)&hstage, c * sizeof(TileSegment), hipHostMallocDefault));
-    dstage = alloc<char>(c * sizeof(TileSegment));
+    hstage.reserve(c * sizeof(TileSegment));
+    dstage.reserve(c * sizeof(TileSegment), kFull);
     stage_cap = c;
   }
   void ensure_flush(uint64_t n) {
     if (n <= fl_cap) return;
-    drop(k0); drop(k1); drop(p0); drop(p1); drop(flag); drop(gid); drop(gpos); drop(gkeep);
     fl_cap = 0;
-    k0 = alloc<unsigned long long>(n); k1 = alloc<unsigned long long>(n);
-    p0 = alloc<uint32_t>(n); p1 = alloc<uint32_t>(n); flag = alloc<uint32_t>(n); gid = alloc<uint32_t>(n);
-    gpos = alloc<uint32_t>(n + 1); gkeep = alloc<uint8_t>(n);
+    k0.reserve(n, kFull); k1.reserve(n, kFull);
+    p0.reserve(n, kFull); p1.reserve(n, kFull); flag.reserve(n, kFull); gid.reserve(n, kFull);
+    gpos.reserve(n + 1, kFull); gkeep.reserve(n, kFull);
     fl_cap = n;
   }
 
@@ -394,11 +279,11 @@ struct TileStore::Impl {
   void add_device(SegSrc src, uint64_t n, uint64_t out[4]) {
     if (n >= kTsMaxRows) throw BatchTooLarge("tile store call too large (segments >= 2^31 - 1)");
     ensure_counts(n);
-    tic(1);
+    timer.tic(1, st);
     hipLaunchKernelGGL(k_ts_count, dim3(grid(n + 1)), dim3(256), 0, st, src, n, (uint64_t)tp.quantisation, cnt, ctr);
-    scan(cnt, ofs, n + 1);
+    scr.scan<unsigned long long>(cnt, ofs, n + 1, st);
     RM_HIP(hipMemcpyAsync(ctr + kTTotal, ofs + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
-    toc(1);
+    timer.toc(st);
     RM_HIP(hipGetLastError());
     read_ctr();   // nothing of the store has changed yet: a bad segment leaves it as it was
     const uint64_t err = hctr[kTErr];
@@ -409,13 +294,13 @@ struct TileStore::Impl {
     if (n_rows + total >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
     ensure_rows(n_rows + total);
     if (total) {
-      tic(1);
+      timer.tic(1, st);
       hipLaunchKernelGGL(k_ts_emit, dim3(grid(n)), dim3(256), 0, st, src, n, (uint64_t)tp.quantisation,
                          (const unsigned long long*)ofs, rows, n_rows, cap, arrivals);
-      toc(1);
+      timer.toc(st);
       RM_HIP(hipGetLastError());
       RM_HIP(hipStreamSynchronize(st));
-      harvest();
+      timer.harvest(ms);
     }
     n_rows += total;
     arrivals += n;
@@ -425,52 +310,34 @@ struct TileStore::Impl {
 
 TileStore::TileStore(int device, const TileParams& tp, uint64_t initial_rows) : p_(new Impl) {
   Impl& s = *p_;
-  try {
-    // AnonymisingProcessor.java:73-80
-    if (tp.privacy < 1) throw std::runtime_error("tile store needs a privacy parameter of 1 or more");
-    if (tp.quantisation < 60) throw std::runtime_error("tile store needs a quantisation parameter of 60 or more");
-    if (tp.source.size() > kTtMaxSource) throw std::runtime_error("tile store source is longer than 64 bytes");
-    if (tp.mode.size() > kTtMaxMode) throw std::runtime_error("tile store mode is longer than 16 bytes");
-    for (const std::string* x : {&tp.source, &tp.mode})
-      for (char ch : *x)
-        if (ch == ',' || ch == '\n' || ch == '\r' || ch == 0) throw std::runtime_error("tile store source and mode may not contain ',' or a newline");
-    if (initial_rows >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
-    s.device = device;
-    s.tp = tp;
-    std::memset(&s.tt, 0, sizeof s.tt);
-    s.tt.quantisation = tp.quantisation;
-    s.tt.source_len = (uint32_t)tp.source.size();
-    s.tt.mode_len = (uint32_t)tp.mode.size();
-    std::memcpy(s.tt.source, tp.source.data(), tp.source.size());
-    std::memcpy(s.tt.mode, tp.mode.data(), tp.mode.size());
-    RM_HIP(hipSetDevice(device));
-    RM_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
-    for (auto& e : s.ev) { RM_HIP(hipEventCreate(&e[0])); RM_HIP(hipEventCreate(&e[1])); }
-    s.ev_ok = true;
-    s.ctr = s.alloc<unsigned long long>(kTNumCtr);
-    RM_HIP(hipHostMalloc((void**)&s.hctr, kTNumCtr * sizeof(unsigned long long), hipHostMallocDefault));
-    s.cap = std::max<uint64_t>(initial_rows, 1);
-    s.rows = s.alloc<TileStoreRow>(s.cap);
-  } catch (...) {
-    for (void* q : s.allocs) (void)hipFree(q);
-    if (s.hctr) (void)hipHostFree(s.hctr);
-    if (s.ev_ok) for (auto& e : s.ev) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
-    if (s.st) (void)hipStreamDestroy(s.st);
-    delete p_;
-    throw;
-  }
+  // AnonymisingProcessor.java:73-80
+  if (tp.privacy < 1) throw std::runtime_error("tile store needs a privacy parameter of 1 or more");
+  if (tp.quantisation < 60) throw std::runtime_error("tile store needs a quantisation parameter of 60 or more");
+  if (tp.source.size() > kTtMaxSource) throw std::runtime_error("tile store source is longer than 64 bytes");
+  if (tp.mode.size() > kTtMaxMode) throw std::runtime_error("tile store mode is longer than 16 bytes");
+  for (const std::string* x : {&tp.source, &tp.mode})
+    for (char ch : *x)
+      if (ch == ',' || ch == '\n' || ch == '\r' || ch == 0) throw std::runtime_error("tile store source and mode may not contain ',' or a newline");
+  if (initial_rows >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
+  s.device = device;
+  s.tp = tp;
+  std::memset(&s.tt, 0, sizeof s.tt);
+  s.tt.quantisation = tp.quantisation;
+  s.tt.source_len = (uint32_t)tp.source.size();
+  s.tt.mode_len = (uint32_t)tp.mode.size();
+  std::memcpy(s.tt.source, tp.source.data(), tp.source.size());
+  std::memcpy(s.tt.mode, tp.mode.data(), tp.mode.size());
+  RM_HIP(hipSetDevice(device));
+  RM_HIP(hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking));
+  s.ctr.reserve(kTNumCtr, Impl::kFull);
+  s.hctr.reserve(kTNumCtr);
+  s.cap = std::max<uint64_t>(initial_rows, 1);
+  s.rows.reserve(s.cap, Impl::kFull);
 }
 
 TileStore::~TileStore() {
-  Impl& s = *p_;
-  (void)hipSetDevice(s.device);
-  (void)hipStreamSynchronize(s.st);
-  for (auto& e : s.ev) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
-  for (void* q : s.allocs) (void)hipFree(q);
-  if (s.hctr) (void)hipHostFree(s.hctr);
-  if (s.hstage) (void)hipHostFree(s.hstage);
-  (void)hipStreamDestroy(s.st);
-  delete p_;
+  (void)hipSetDevice(p_->device);
+  (void)hipStreamSynchronize(p_->st);
 }
 
 int TileStore::device() const { return p_->device; }
@@ -505,9 +372,9 @@ void TileStore::add(const TileSegment* segs, uint64_t n, uint64_t out[4]) {
   s.ensure_stage(n);
   if (n) {
     std::memcpy(s.hstage, segs, n * sizeof(TileSegment));
-    s.tic(0);
+    s.timer.tic(0, s.st);
     RM_HIP(hipMemcpyAsync(s.dstage, s.hstage, n * sizeof(TileSegment), hipMemcpyHostToDevice, s.st));
-    s.toc(0);
+    s.timer.toc(s.st);
   }
   s.add_device(SegSrc{s.dstage, (uint32_t)sizeof(TileSegment)}, n, out);
 }
@@ -531,42 +398,44 @@ void TileStore::flush(char** blob_out, size_t* len_out, uint64_t out[5]) {
   if (R) {
     s.ensure_flush(R);
     // ---- Collections.sort over every tile at once: stable LSD passes from arrival order
-    s.tic(2);
-    hipLaunchKernelGGL(k_ts_iota, dim3(grid(R)), dim3(256), 0, st, R, s.p0);
+    s.timer.tic(2, st);
+    hipLaunchKernelGGL(k_iota<uint64_t>, dim3(grid(R)), dim3(256), 0, st, R, s.p0);
     uint32_t* pin = s.p0;
     uint32_t* pout = s.p1;
     static const int kBits[4] = {63, 63, 25, 48};   // ids <= 2^63 - 1; tile 25 bits; bucket < 2^53 / 60
     for (int pass = 0; pass < 4; ++pass) {
       hipLaunchKernelGGL(k_ts_key, dim3(grid(R)), dim3(256), 0, st, R, (const TileStoreRow*)s.rows, (const uint32_t*)pin, pass, s.k0);
-      s.sort_pairs(s.k0, s.k1, pin, pout, R, kBits[pass]);
+      s.scr.sort_pairs(s.k0.get(), s.k1.get(), pin, pout, R, kBits[pass], st);
       std::swap(pin, pout);
     }
-    s.toc(2);
+    s.timer.toc(st);
     const uint32_t* perm = pin;
     // ---- clean(): runs, keep rule per run, keep flag per row, compaction
-    s.tic(3);
-    hipLaunchKernelGGL(k_ts_gflags, dim3(grid(R)), dim3(256), 0, st, R, (const TileStoreRow*)s.rows, perm, s.flag);
-    s.scan(s.flag, s.gid, R);
-    hipLaunchKernelGGL(k_ts_gpos, dim3(grid(R)), dim3(256), 0, st, R, (const uint32_t*)s.flag, (const uint32_t*)s.gid, s.gpos, s.ctr);
-    s.toc(3);
+    s.timer.tic(3, st);
+    hipLaunchKernelGGL((k_cull_gflags<TsSameFile, TileStoreRow>), dim3(grid(R)), dim3(256), 0, st, R, (const TileStoreRow*)s.rows,
+                       perm, s.flag);
+    s.scr.scan<uint32_t>(s.flag, s.gid, R, st);
+    hipLaunchKernelGGL(k_cull_gpos<unsigned long long>, dim3(grid(R)), dim3(256), 0, st, R, (const uint32_t*)s.flag,
+                       (const uint32_t*)s.gid, s.gpos, s.ctr + kTRuns);
+    s.timer.toc(st);
     RM_HIP(hipGetLastError());
     s.read_ctr();
     const uint32_t G = (uint32_t)s.hctr[kTRuns];
     if (G == 0 || G > R) throw std::runtime_error("tile store run count out of range");
-    s.tic(3);
-    hipLaunchKernelGGL(k_ts_gkeep, dim3(grid(G)), dim3(256), 0, st, G, (const TileStoreRow*)s.rows, perm, (const uint32_t*)s.gpos,
-                       s.tp.privacy, s.gkeep, s.ctr);
+    s.timer.tic(3, st);
+    hipLaunchKernelGGL((k_cull_gkeep<TsSameFile, true, TileStoreRow>), dim3(grid(G)), dim3(256), 0, st, G,
+                       (const TileStoreRow*)s.rows, perm, (const uint32_t*)s.gpos, s.tp.privacy, s.gkeep, s.ctr + kTTiles);
     // buffers the stages before are done with, in stream order: the spare permutation buffer
-    // takes the rows' keep flags; once k_ts_kflags has read them, gid takes the kept rows'
+    // takes the rows' keep flags; once k_cull_kflags has read them, gid takes the kept rows'
     // offsets and flag their indices; the sort keys take the text lengths and offsets
     uint32_t* kflag = pout;
     uint32_t* kofs = s.gid;
     uint32_t* kperm = s.flag;
-    hipLaunchKernelGGL(k_ts_kflags, dim3(grid(R)), dim3(256), 0, st, R, (const uint32_t*)s.gid, (const uint32_t*)s.flag,
+    hipLaunchKernelGGL(k_cull_kflags<uint8_t>, dim3(grid(R)), dim3(256), 0, st, R, (const uint32_t*)s.gid, (const uint32_t*)s.flag,
                        (const uint8_t*)s.gkeep, kflag);
-    s.scan((const uint32_t*)kflag, kofs, R);
+    s.scr.scan((const uint32_t*)kflag, kofs, R, st);
     hipLaunchKernelGGL(k_ts_compact, dim3(grid(R)), dim3(256), 0, st, R, perm, (const uint32_t*)kflag, (const uint32_t*)kofs, kperm, s.ctr);
-    s.toc(3);
+    s.timer.toc(st);
     RM_HIP(hipGetLastError());
     s.read_ctr();
     K = s.hctr[kTKeptRows];
@@ -576,28 +445,27 @@ void TileStore::flush(char** blob_out, size_t* len_out, uint64_t out[5]) {
       // ---- the CSV bytes: lengths, offsets, the write, one download
       unsigned long long* len = s.k1;
       unsigned long long* off = s.k0;
-      s.tic(4);
+      s.timer.tic(4, st);
       hipLaunchKernelGGL(k_ts_len, dim3(grid(K)), dim3(256), 0, st, (uint32_t)K, (const TileStoreRow*)s.rows, (const uint32_t*)kperm,
                          s.tt, len, s.ctr);
-      s.scan((const unsigned long long*)len, off, K);
+      s.scr.scan((const unsigned long long*)len, off, K, st);
       hipLaunchKernelGGL(k_ts_total, dim3(1), dim3(64), 0, st, (uint32_t)K, (const unsigned long long*)off, (const unsigned long long*)len, s.ctr);
-      s.toc(4);
+      s.timer.toc(st);
       RM_HIP(hipGetLastError());
       s.read_ctr();
       files = s.hctr[kTFiles];
       bytes = s.hctr[kTBytes];
       if (bytes > K * (uint64_t)kTtMaxPiece) throw std::runtime_error("tile store blob size out of range");
       if (bytes > s.blob_cap) {
-        s.drop(s.blob);
         s.blob_cap = 0;
-        s.blob = s.alloc<char>(bytes + bytes / 4 + 16);   // (hipMalloc: 256-byte aligned, so blob offsets mod 16 are addresses mod 16)
+        s.blob.reserve(bytes + bytes / 4 + 16, Impl::kFull);   // (hipMalloc: 256-byte aligned, so blob offsets mod 16 are addresses mod 16)
         s.blob_cap = bytes + bytes / 4;
       }
-      s.tic(4);
+      s.timer.tic(4, st);
       hipLaunchKernelGGL(k_ts_write, dim3((uint32_t)((K + 63) / 64)), dim3(64), 0, st, (uint32_t)K, (const TileStoreRow*)s.rows,
                          (const uint32_t*)kperm, s.tt, (const unsigned long long*)off, (const unsigned long long*)len, s.blob,
                          (unsigned long long)bytes);
-      s.toc(4);
+      s.timer.toc(st);
       RM_HIP(hipGetLastError());
     }
   }
@@ -605,15 +473,15 @@ void TileStore::flush(char** blob_out, size_t* len_out, uint64_t out[5]) {
   char* host = (char*)std::malloc(bytes + 1);
   if (!host) throw std::bad_alloc();
   if (bytes) {
-    s.tic(5);
+    s.timer.tic(5, st);
     const hipError_t e = hipMemcpyAsync(host, s.blob, bytes, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) s.toc(5);
+    if (e == hipSuccess) s.timer.toc(st);
     const hipError_t e2 = e == hipSuccess ? hipStreamSynchronize(st) : e;
     if (e2 != hipSuccess) {
       std::free(host);
       RM_HIP(e2);
     }
-    s.harvest();
+    s.timer.harvest(s.ms);
   }
   host[bytes] = 0;
   s.n_rows = 0;   // the store is empty after a flush (AnonymisingProcessor.java:229, 240)

@@ -272,26 +272,17 @@ char* dup_string(const std::string& s) {
 // pinned host staging of one matcher's batch arrays (grow-only): the parse threads copy their
 // points here and the engine's uploads run at full PCIe rate
 struct HostStaging {
-  float* lon = nullptr; float* lat = nullptr; float* acc = nullptr; double* time = nullptr;
+  PinBuf<float> lon, lat, acc;
+  PinBuf<double> time;
   size_t cap = 0;
   void ensure(size_t n) {
     if (n <= cap) return;
     const size_t c = std::max(n + n / 4, cap + cap / 2) + 4096;
-    release();
-    RM_HIP(hipHostMalloc((void**)&lon, c * 4, hipHostMallocDefault));
-    RM_HIP(hipHostMalloc((void**)&lat, c * 4, hipHostMallocDefault));
-    RM_HIP(hipHostMalloc((void**)&acc, c * 4, hipHostMallocDefault));
-    RM_HIP(hipHostMalloc((void**)&time, c * 8, hipHostMallocDefault));
+    cap = 0;
+    lon.reset(); lat.reset(); acc.reset(); time.reset();   // all four go before the first is taken again
+    lon.reserve(c); lat.reserve(c); acc.reserve(c); time.reserve(c);
     cap = c;
   }
-  void release() {
-    for (void* q : {(void*)lon, (void*)lat, (void*)acc, (void*)time})
-      if (q) (void)hipHostFree(q);
-    lon = lat = acc = nullptr;
-    time = nullptr;
-    cap = 0;
-  }
-  ~HostStaging() { release(); }
 };
 
 // pageable staging of a small batch's arrays (grow-only, geometric)
@@ -488,22 +479,15 @@ void Coalescer::loop() {
 
 // a pinned host buffer, grow-only
 struct PinnedBytes {
-  char* p = nullptr;
+  PinBuf<char> p;
   size_t cap = 0;
   void ensure(size_t n) {
     if (n <= cap && p) return;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
     cap = 0;
     const size_t c = std::max<size_t>(n + n / 4, 1u << 16);
-    RM_HIP(hipHostMalloc((void**)&p, c, hipHostMallocDefault));
+    p.reserve(c);
     cap = c;
   }
-  PinnedBytes() = default;
-  PinnedBytes(const PinnedBytes&) = delete;
-  PinnedBytes& operator=(const PinnedBytes&) = delete;
-  PinnedBytes(PinnedBytes&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-  ~PinnedBytes() { if (p) (void)hipHostFree(p); }
 };
 
 struct rm_matcher {
@@ -1512,7 +1496,7 @@ int rm_num_kernels(void) { return kNumKernels; }
 struct rm_comm {
   ncclComm_t comm = nullptr;
   hipStream_t stream = nullptr;
-  void* scratch = nullptr;  // 8 bytes for host-value reductions and barriers
+  DevBuf<char> scratch;     // 8 bytes for host-value reductions and barriers (freed with the communicator)
   int device = 0;           // -1: a host communicator without a GPU (host values and barriers only)
   int rank = 0, nranks = 1;
   rm_host_allgather_fn host_fn = nullptr;   // set: every collective runs over this host transport
@@ -2177,7 +2161,7 @@ rm_comm* rm_comm_init(int nranks, int rank, const uint8_t id[128], int device) {
     c->comm = r == ncclSuccess ? res->first : nullptr;
     nccl_check(r, "ncclCommInitRank");
     RM_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    RM_HIP(hipMalloc(&c->scratch, 8));
+    c->scratch.reserve(8);
     out = c.release();
   });
   return out;
@@ -2197,7 +2181,7 @@ rm_comm* rm_comm_init_host(int nranks, int rank, rm_host_allgather_fn fn, void* 
     if (device >= 0) {
       RM_HIP(hipSetDevice(device));
       RM_HIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-      RM_HIP(hipMalloc(&c->scratch, 8));
+      c->scratch.reserve(8);
     }
     out = c.release();
   });
@@ -2211,7 +2195,6 @@ void rm_comm_destroy(rm_comm* c) {
   if (c->device >= 0) (void)hipSetDevice(c->device);
   if (c->comm) ncclCommDestroy(c->comm);
   if (c->stream) (void)hipStreamDestroy(c->stream);
-  if (c->scratch) (void)hipFree(c->scratch);
   delete c;
 }
 

@@ -1,5 +1,6 @@
-// dev_util.hpp — the host-side HIP plumbing the stages around the matcher share: device and pinned
-// buffers that free themselves, HIP-event part timers, the hipcub scan / sort scratch, grid() and
+// dev_util.hpp — the host-side HIP plumbing the engine, the matcher, the C API and the stages
+// around them share: device and pinned buffers that free themselves, HIP-event part timers, the
+// hipcub scan / sort scratch, grid() and
 // the iota / fill kernels.  Growth policy stays with the callers: a buffer is given the capacity
 // its owner computed.
 #pragma once
@@ -48,6 +49,7 @@ template <class T>
 class DevBuf {
  public:
   DevBuf() = default;
+  explicit DevBuf(uint64_t cap) { reserve(cap); }
   DevBuf(DevBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
   DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
   ~DevBuf() { reset(); }
@@ -65,7 +67,7 @@ class DevBuf {
     if (e == hipErrorOutOfMemory) {
       (void)hipGetLastError();
       if (too_large) throw BatchTooLarge(too_large);
-      throw OutOfDeviceMemory("device buffers do not fit in HBM");
+      throw OutOfDeviceMemory("out of device memory allocating " + std::to_string(std::max<uint64_t>(cap, 1) * sizeof(T)) + " bytes");
     }
     RM_HIP(e);
     if (p_) {   // (a keeping call)
@@ -92,26 +94,41 @@ class DevBuf {
   uint64_t cap_ = 0;
 };
 
-// The same in pinned host memory (contents are never kept).
+// The same in pinned host memory (contents are never kept: the old block always goes first).
 template <class T>
 class PinBuf {
  public:
   PinBuf() = default;
-  PinBuf(const PinBuf&) = delete;
-  PinBuf& operator=(const PinBuf&) = delete;
+  PinBuf(PinBuf&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  PinBuf& operator=(PinBuf&& o) noexcept { std::swap(p_, o.p_); std::swap(cap_, o.cap_); return *this; }
   ~PinBuf() { reset(); }
-  void reserve(uint64_t cap) {
+  // memory that cannot be pinned throws BatchTooLarge(too_large) where the caller names a message
+  void reserve(uint64_t cap, const char* too_large = nullptr) {
+    const hipError_t e = try_reserve(cap);
+    if (e == hipErrorOutOfMemory && too_large) throw BatchTooLarge(too_large);
+    RM_HIP(e);
+  }
+  // the same for a caller with a second size to try: a failure is returned with the error cleared
+  // and the buffer empty
+  hipError_t try_reserve(uint64_t cap) {
     reset();
-    RM_HIP(hipHostMalloc((void**)&p_, std::max<uint64_t>(cap, 1) * sizeof(T), hipHostMallocDefault));
+    const hipError_t e = hipHostMalloc((void**)&p_, std::max<uint64_t>(cap, 1) * sizeof(T), hipHostMallocDefault);
+    if (e != hipSuccess) { (void)hipGetLastError(); p_ = nullptr; return e; }
+    cap_ = cap;
+    return hipSuccess;
   }
   void reset() {
     if (p_) (void)hipHostFree(p_);
     p_ = nullptr;
+    cap_ = 0;
   }
   operator T*() const { return p_; }
+  T* get() const { return p_; }
+  uint64_t cap() const { return cap_; }
 
  private:
   T* p_ = nullptr;
+  uint64_t cap_ = 0;
 };
 
 // HIP-event pairs around the parts of a call, pooled: a part may be timed several times.
@@ -129,13 +146,16 @@ class PartTimer {
     pending_.push_back(e);
     RM_HIP(hipEventRecord(e.a, st));
   }
-  void toc(hipStream_t st) { RM_HIP(hipEventRecord(pending_.back().b, st)); }
-  // after a stream synchronise: every pair's time is added to ms[its part] (null: dropped)
-  void harvest(double* ms) {
+  void toc(hipStream_t st) {
+    if (!pending_.empty()) RM_HIP(hipEventRecord(pending_.back().b, st));
+  }
+  // after a stream synchronise: every pair's time is added to ms[its part] (null: dropped), and
+  // pairs[its part] counts it
+  void harvest(double* ms, uint64_t* pairs = nullptr) {
     for (Ev& e : pending_) {
       float t = 0.f;
       if (hipEventElapsedTime(&t, e.a, e.b) != hipSuccess) (void)hipGetLastError();   // (a part an exception cut short)
-      else if (ms) ms[e.part] += t;
+      else if (ms) { ms[e.part] += t; if (pairs) pairs[e.part] += 1; }
       free_.push_back(e.a); free_.push_back(e.b);
     }
     pending_.clear();

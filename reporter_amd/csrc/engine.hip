@@ -4964,18 +4964,13 @@ __global__ void k_fill_edge_src(const uint32_t* node_off, uint32_t n_nodes, uint
   for (uint32_t e = node_off[n]; e < node_off[n + 1]; ++e) edge_src[e] = n;
 }
 
+// n elements in a block of their own that `list` owns (OutOfDeviceMemory when HBM is full)
 template <class T>
-T* dalloc(std::vector<void*>& list, uint64_t n) {
-  void* p = nullptr;
-  if (n == 0) n = 1;
-  const hipError_t e = hipMalloc(&p, n * sizeof(T));
-  if (e == hipErrorOutOfMemory) {
-    (void)hipGetLastError();   // not sticky: clear it for the caller's next call
-    throw OutOfDeviceMemory("out of device memory allocating " + std::to_string(n * sizeof(T)) + " bytes");
-  }
-  RM_HIP(e);
-  list.push_back(p);
-  return (T*)p;
+T* dalloc(std::vector<DevBuf<char>>& list, uint64_t n) {
+  DevBuf<char> b;
+  b.reserve(std::max<uint64_t>(n, 1) * sizeof(T));
+  list.push_back(std::move(b));
+  return (T*)list.back().get();
 }
 
 // a workspace that does not fit in HBM is a batch too large for the device (serve_policy.hpp)
@@ -4989,10 +4984,17 @@ void grow_workspace(F&& f) {
 }
 
 template <class T>
-T* upload(std::vector<void*>& list, const std::vector<T>& v) {
+T* upload(std::vector<DevBuf<char>>& list, const std::vector<T>& v) {
   T* p = dalloc<T>(list, v.size());
   if (!v.empty()) RM_HIP(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   return p;
+}
+// v's bytes in a fresh block of b
+template <class T, class S>
+void upload(DevBuf<T>& b, const std::vector<S>& v) {
+  const uint64_t bytes = v.size() * sizeof(S);
+  b.reserve((bytes + sizeof(T) - 1) / sizeof(T));
+  if (bytes) RM_HIP(hipMemcpy(b.get(), v.data(), bytes, hipMemcpyHostToDevice));
 }
 
 }  // namespace
@@ -5253,10 +5255,7 @@ void Engine::k1_grid(float radius_m, DevGraph& g) const {
   g.ncx = k.ncx; g.ncy = k.ncy;
 }
 
-Engine::~Engine() {
-  (void)hipSetDevice(device_);
-  for (void* p : allocs_) (void)hipFree(p);
-}
+Engine::~Engine() { (void)hipSetDevice(device_); }   // the members free themselves on it
 
 DevGraph Engine::dev_snapshot() const {
   std::lock_guard<std::mutex> lk(ball_mu_);
@@ -5326,14 +5325,14 @@ void Engine::ensure_balls(uint32_t mode_mask) {
         if (try_gpu && build_balls_gpu(mode, r, max_keys, avail)) { built = true; break; }
         BallTables bt;
         build_balls(host_, mode, r, max_keys, threads, bt, avail / 16);
-        std::vector<void*> tmp;   // both arrays or neither
-        struct Free { std::vector<void*>& l; ~Free() { for (void* p : l) (void)hipFree(p); } } fr{tmp};
-        const uint2* hdr = (const uint2*)upload(tmp, bt.hdr);
-        const uint4* ent = (const uint4*)upload(tmp, bt.ent);
-        allocs_.insert(allocs_.end(), tmp.begin(), tmp.end());
-        tmp.clear();
-        dg_.ball_hdr[mode] = hdr;
-        dg_.ball_ent[mode] = ent;
+        DevBuf<uint2> hdr;   // both arrays or neither
+        DevBuf<uint4> ent;
+        upload(hdr, bt.hdr);
+        upload(ent, bt.ent);
+        ball_hdr_[mode] = std::move(hdr);
+        ball_ent_[mode] = std::move(ent);
+        dg_.ball_hdr[mode] = ball_hdr_[mode];
+        dg_.ball_ent[mode] = ball_ent_[mode];
         dg_.ball_radius[mode] = bt.radius_cm;
         dg_.ball_mask |= bit;
         ball_bytes_ += (uint64_t)bt.ent.size() * 4;
@@ -5381,21 +5380,20 @@ void Engine::ensure_turn_rows(uint32_t mode_mask) {
     size_t hbm_free = 0, hbm_total = 0;
     RM_HIP(hipMemGetInfo(&hbm_free, &hbm_total));
     if (slots == 0 || slots * sizeof(uint2) + kReserve > hbm_free) continue;
-    uint2* rows = nullptr;
+    DevBuf<uint2> rows;   // the engine's once the kernel has filled it
     try {
-      std::vector<void*> tmp;
-      rows = dalloc<uint2>(tmp, slots);
+      rows.reserve(slots);
     } catch (const OutOfDeviceMemory&) {
-      continue;
+      continue;   // (a mode whose rows do not fit keeps none)
     }
     const auto t0 = std::chrono::steady_clock::now();
     DevGraph g = dg_;
     hipLaunchKernelGGL(k_ball_turns, dim3(std::min<uint32_t>(std::max(1u, host_.num_nodes()), 65536u)), dim3(64), 0, 0, g,
-                       mode, rows);
+                       mode, rows.get());
     RM_HIP(hipGetLastError());
     RM_HIP(hipDeviceSynchronize());
-    allocs_.push_back(rows);
-    dg_.ball_turn[mode] = rows;
+    ball_turn_[mode] = std::move(rows);
+    dg_.ball_turn[mode] = ball_turn_[mode];
     dg_.ball_turn_mask |= bit;
     ball_bytes_ += slots * sizeof(uint2);
     turn_ms_[mode] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -5411,24 +5409,22 @@ bool Engine::build_balls_gpu(int mode, uint32_t radius_cm, uint32_t max_keys, ui
   const uint32_t N = host_.num_nodes();
   std::vector<uint32_t> inc_off, inc;
   road_incidence(host_, inc_off, inc);
-  std::vector<void*> tmp;
-  struct Free { std::vector<void*>& l; ~Free() { for (void* p : l) (void)hipFree(p); } } fr{tmp};
-  const uint32_t* d_inc_off = upload(tmp, inc_off);
-  const uint32_t* d_inc = upload(tmp, inc);
-  uint32_t* d_bits = dalloc<uint32_t>(tmp, N);
-  unsigned long long* d_cnt = dalloc<unsigned long long>(tmp, N);
-  unsigned long long* d_off = dalloc<unsigned long long>(tmp, N);
-  unsigned long long* d_stats = dalloc<unsigned long long>(tmp, 4);
+  DevBuf<uint32_t> d_inc_off, d_inc;
+  upload(d_inc_off, inc_off);
+  upload(d_inc, inc);
+  DevBuf<uint32_t> d_bits(N);
+  DevBuf<unsigned long long> d_cnt(N), d_off(N), d_stats(4);
   RM_HIP(hipMemset(d_stats, 0, 4 * sizeof(unsigned long long)));
   DevGraph g = dg_;
   const uint32_t grid = std::min<uint32_t>(N, 16384);
   hipLaunchKernelGGL(k_ball_build<false>, dim3(grid), dim3(64), 0, 0, g, mode, radius_cm, max_keys, d_inc_off,
                      d_inc, d_bits, (const uint2*)nullptr, (uint4*)nullptr, d_stats);
   hipLaunchKernelGGL(k_ball_entries, dim3((N + 255) / 256), dim3(256), 0, 0, d_bits, N, d_cnt);
+  // (hipcub directly: ScanScratch::scan would read through a const pointer, another instantiation)
   size_t tb = 0;
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt, d_off, (int)N, (hipStream_t)0));
-  void* d_tmp = dalloc<char>(tmp, tb);
-  RM_HIP(hipcub::DeviceScan::ExclusiveSum(d_tmp, tb, d_cnt, d_off, (int)N, (hipStream_t)0));
+  RM_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, d_cnt.get(), d_off.get(), (int)N, (hipStream_t)0));
+  DevBuf<char> d_tmp(tb);
+  RM_HIP(hipcub::DeviceScan::ExclusiveSum((void*)d_tmp.get(), tb, d_cnt.get(), d_off.get(), (int)N, (hipStream_t)0));
   unsigned long long st[4], last[2];
   RM_HIP(hipMemcpy(st, d_stats, sizeof st, hipMemcpyDeviceToHost));
   RM_HIP(hipMemcpy(&last[0], d_off + (N - 1), 8, hipMemcpyDeviceToHost));
@@ -5437,21 +5433,19 @@ bool Engine::build_balls_gpu(int mode, uint32_t radius_cm, uint32_t max_keys, ui
   const uint64_t total = last[0] + last[1];
   if (total > kBallMaxRows || total * 16 > avail_bytes)
     throw BallsTooLarge("route balls too large for their budget; lower the radius");
-  // header and rows join the engine's allocations only once both are filled
-  uint2* d_hdr = dalloc<uint2>(tmp, N);
-  uint4* d_ent = dalloc<uint4>(tmp, total);
+  // header and rows become the engine's only once both are filled
+  DevBuf<uint2> d_hdr(N);
+  DevBuf<uint4> d_ent(total);
   hipLaunchKernelGGL(k_ball_hdr, dim3((N + 255) / 256), dim3(256), 0, 0, d_bits, d_off, N, d_hdr);
   RM_HIP(hipMemset(d_ent, 0xff, total * sizeof(uint4)));
   hipLaunchKernelGGL(k_ball_build<true>, dim3(grid), dim3(64), 0, 0, g, mode, radius_cm, max_keys, d_inc_off,
                      d_inc, d_bits, (const uint2*)d_hdr, d_ent, d_stats);
   RM_HIP(hipGetLastError());
   RM_HIP(hipDeviceSynchronize());
-  tmp.erase(std::remove(tmp.begin(), tmp.end(), (void*)d_hdr), tmp.end());
-  tmp.erase(std::remove(tmp.begin(), tmp.end(), (void*)d_ent), tmp.end());
-  allocs_.push_back(d_hdr);
-  allocs_.push_back(d_ent);
-  dg_.ball_hdr[mode] = d_hdr;
-  dg_.ball_ent[mode] = d_ent;
+  ball_hdr_[mode] = std::move(d_hdr);
+  ball_ent_[mode] = std::move(d_ent);
+  dg_.ball_hdr[mode] = ball_hdr_[mode];
+  dg_.ball_ent[mode] = ball_ent_[mode];
   dg_.ball_radius[mode] = radius_cm;
   dg_.ball_mask |= 1u << mode;
   ball_bytes_ += total * 16;
@@ -5473,12 +5467,10 @@ void Engine::ball_lookup(int mode, uint64_t n, const uint32_t* from, const uint3
     if (from[i] >= host_.num_nodes() || road[i] >= host_.num_roads()) throw std::runtime_error("node or road out of range");
   }
   if (!((ball_built_ >> mode) & 1u) || n == 0) return;
-  std::vector<void*> tmp;
-  struct Free { std::vector<void*>& l; ~Free() { for (void* p : l) (void)hipFree(p); } } fr{tmp};
-  uint32_t* d_from = dalloc<uint32_t>(tmp, n);
-  uint32_t* d_road = dalloc<uint32_t>(tmp, n);
-  unsigned long long* d_keys = dalloc<unsigned long long>(tmp, 2 * n);
-  uint8_t* d_pred = preds ? dalloc<uint8_t>(tmp, 2 * n) : nullptr;
+  DevBuf<uint32_t> d_from(n), d_road(n);
+  DevBuf<unsigned long long> d_keys(2 * n);
+  DevBuf<uint8_t> d_pred;   // (empty without preds)
+  if (preds) d_pred.reserve(2 * n);
   RM_HIP(hipMemcpy(d_from, from, n * 4, hipMemcpyHostToDevice));
   RM_HIP(hipMemcpy(d_road, road, n * 4, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_ball_lookup, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, dg_, mode, n, d_from, d_road,
@@ -5491,18 +5483,6 @@ void Engine::ball_lookup(int mode, uint64_t n, const uint32_t* from, const uint3
 // ==========================================================================================
 // Workspace / Matcher
 
-Workspace::~Workspace() { release(); }
-void Workspace::release() {
-  for (void* p : allocs) (void)hipFree(p);
-  allocs.clear();
-  cap_points = cap_traces = cap_trans = cap_path = cap_opts = cap_segs = cap_src = cap_sort = cap_turn = 0;
-  perm = loc_cursor = pcnt = nullptr;
-  route_d = nullptr;
-  walk = nullptr;
-  cap_walk = 0;
-  loc_key = nullptr;
-}
-
 Matcher::Matcher(Engine* e) : eng_(e) {
   RM_HIP(hipSetDevice(e->device()));
   RM_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
@@ -5513,40 +5493,24 @@ void Matcher::ensure_sort(uint64_t n) {
   grow_workspace([&] {
     Workspace& w = ws_;
     if (n <= w.cap_sort && w.perm) return;
-    for (void** q : {(void**)&w.perm, (void**)&w.loc_key, (void**)&w.loc_cursor, (void**)&w.pcnt}) {
-      if (*q) {
-        (void)hipFree(*q);
-        w.allocs.erase(std::find(w.allocs.begin(), w.allocs.end(), *q));
-      }
-      *q = nullptr;
-    }
-    w.cap_sort = 0;
+    w.drop<WsSort>();
     const uint64_t c = std::max<uint64_t>(n, w.cap_points);
     if (c >= (uint64_t)INT32_MAX) throw BatchTooLarge("batch too large for the locality sort");
-    std::vector<void*>& L = w.allocs;
-    w.perm = dalloc<uint32_t>(L, c);
-    w.loc_key = dalloc<uint16_t>(L, c);                 // region bucket per slot
-    w.loc_cursor = dalloc<uint32_t>(L, kLocBuckets + 1);  // bucket counts -> cursors
-    w.pcnt = dalloc<uint32_t>(L, c);
+    w.perm.reserve(c);
+    w.loc_key.reserve(c);                  // region bucket per slot
+    w.loc_cursor.reserve(kLocBuckets + 1);   // bucket counts -> cursors
+    w.pcnt.reserve(c);
     w.cap_sort = c;
   });
 }
 
+// The buffers, the workspace and the timer's events free themselves after this body, on the
+// device it sets; the synchronise is what makes those frees safe: nothing of this matcher is in
+// flight any more.
 Matcher::~Matcher() {
   (void)hipSetDevice(eng_->device());
   if (stream_) (void)hipStreamSynchronize(stream_);
-  for (auto& ev : pending_) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-  for (auto& ev : free_ev_) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
-  ws_.release();
-  if (dl_dev_) (void)hipFree(dl_dev_);
-  if (dl_host_) (void)hipHostFree(dl_host_);
-  for (void* q : {(void*)jdev_, jspan_, (void*)jflag_, jtsp_})
-    if (q) (void)hipFree(q);
   if (stream_) (void)hipStreamDestroy(stream_);
-  if (hctl_) (void)hipHostFree(hctl_);
-  if (hpack_) (void)hipHostFree(hpack_);
-  if (dpack_) (void)hipFree(dpack_);
-  if (hoff_) (void)hipHostFree(hoff_);
 }
 
 void Matcher::ensure(uint64_t points, uint32_t traces, uint32_t nopts) {
@@ -5576,51 +5540,43 @@ void Matcher::alloc_points(uint64_t cp, uint64_t ct, uint64_t co, uint64_t keep_
                            uint64_t keep_segs, uint64_t keep_src) {
   {
     Workspace& w = ws_;
-    w.release();
+    // the whole workspace goes, pools included, before the first allocation: the grown one can
+    // take the room the old one held
+    w = Workspace{};
     // test hook: a workspace of more than RM_TEST_WS_POINTS_LIMIT points fails as out of memory
     // (tests/test_gpu_isolation.py: the grown size fails, the batch's own size must not)
     if (const char* lim = std::getenv("RM_TEST_WS_POINTS_LIMIT"); lim && *lim && cp > std::strtoull(lim, nullptr, 10))
       throw OutOfDeviceMemory("workspace above RM_TEST_WS_POINTS_LIMIT");
-    std::vector<void*>& L = w.allocs;
-    w.trace_off = dalloc<uint32_t>(L, ct + 1);
-    w.lon = dalloc<float>(L, cp); w.lat = dalloc<float>(L, cp); w.time = dalloc<double>(L, cp);
-    w.acc = dalloc<float>(L, cp); w.opts = dalloc<MatchOptions>(L, co); w.trace_opt = dalloc<uint32_t>(L, ct);
-    w.slot_trace = dalloc<uint32_t>(L, cp); w.n_states = dalloc<uint32_t>(L, ct); w.state_orig = dalloc<uint32_t>(L, cp);
-    w.state_time = dalloc<double>(L, cp);
-    w.cand_n = dalloc<uint8_t>(L, cp); w.cand_desc = dalloc<uint4>(L, cp * kMaxCand * 2);
-    w.cand_sq = dalloc<float>(L, cp * kMaxCand); w.pair_info = dalloc<uint4>(L, cp);
-    w.trans_cnt = dalloc<uint32_t>(L, cp); w.trans_off = dalloc<uint32_t>(L, cp); w.gc = dalloc<double>(L, cp);
-    w.src_cnt = dalloc<uint32_t>(L, cp); w.src_off = dalloc<uint32_t>(L, cp);
-    w.choice = dalloc<int8_t>(L, cp); w.chain_start = dalloc<uint8_t>(L, cp); w.bp = dalloc<uint8_t>(L, cp * kMaxCand);
-    w.path_off = dalloc<uint32_t>(L, cp); w.path_cnt = dalloc<uint32_t>(L, cp); w.route_dist = dalloc<uint32_t>(L, cp);
-    w.path_sab = dalloc<uint2>(L, cp);
-    w.path_inline = dalloc<uint32_t>(L, cp * kInlinePath);
-    w.trav_off = dalloc<uint32_t>(L, cp);
-    w.seg_base = dalloc<uint32_t>(L, ct); w.seg_cnt = dalloc<uint32_t>(L, ct);
-    w.rep_cnt = dalloc<uint32_t>(L, ct); w.stats = dalloc<ReportStats>(L, ct);
-    w.ctl = dalloc<uint32_t>(L, kCtlWords);
-    w.rl_paths_a = dalloc<uint32_t>(L, cp); w.rl_paths_b = dalloc<uint32_t>(L, cp);
-    w.rl_cand = dalloc<uint32_t>(L, cp);
-    w.rl_paths_c = dalloc<uint32_t>(L, cp);
-    w.trace_err = dalloc<uint32_t>(L, ct);
-    w.tot64 = dalloc<unsigned long long>(L, 4);
-    w.tot_part = dalloc<unsigned long long>(L, 2 * ((cp + 255) / 256) + 2);
+    w.trace_off.reserve(ct + 1);
+    w.lon.reserve(cp); w.lat.reserve(cp); w.time.reserve(cp);
+    w.acc.reserve(cp); w.opts.reserve(co); w.trace_opt.reserve(ct);
+    w.slot_trace.reserve(cp); w.n_states.reserve(ct); w.state_orig.reserve(cp);
+    w.state_time.reserve(cp);
+    w.cand_n.reserve(cp); w.cand_desc.reserve(cp * kMaxCand * 2);
+    w.cand_sq.reserve(cp * kMaxCand); w.pair_info.reserve(cp);
+    w.trans_cnt.reserve(cp); w.trans_off.reserve(cp); w.gc.reserve(cp);
+    w.src_cnt.reserve(cp); w.src_off.reserve(cp);
+    w.choice.reserve(cp); w.chain_start.reserve(cp); w.bp.reserve(cp * kMaxCand);
+    w.path_off.reserve(cp); w.path_cnt.reserve(cp); w.route_dist.reserve(cp);
+    w.path_sab.reserve(cp);
+    w.path_inline.reserve(cp * kInlinePath);
+    w.trav_off.reserve(cp);
+    w.seg_base.reserve(ct); w.seg_cnt.reserve(ct);
+    w.rep_cnt.reserve(ct); w.stats.reserve(ct);
+    w.ctl.reserve(kCtlWords);
+    w.rl_paths_a.reserve(cp); w.rl_paths_b.reserve(cp);
+    w.rl_cand.reserve(cp);
+    w.rl_paths_c.reserve(cp);
+    w.trace_err.reserve(ct);
+    w.tot64.reserve(4);
+    w.tot_part.reserve(2 * ((cp + 255) / 256) + 2);
     // a steady run's coarse scan buckets (k_scan_buckets): one pair per kScanGroup counting blocks
-    w.scan_bkt = dalloc<unsigned long long>(L, 2 * (scan_buckets((uint32_t)((cp + 255) / 256)) + 1));
+    w.scan_bkt.reserve(2 * (scan_buckets((uint32_t)((cp + 255) / 256)) + 1));
     w.cap_points = cp; w.cap_traces = ct; w.cap_opts = co;
-    w.gsearch = nullptr;
-    w.route = nullptr; w.route_d = nullptr; w.cap_turn = 0; w.walk = nullptr; w.cap_walk = 0; w.rl_routes_a = nullptr; w.rl_routes_b = nullptr; w.rl_routes_0 = nullptr; w.rl_routes_c = nullptr; w.path_pool = nullptr; w.segs = nullptr; w.reps = nullptr; w.src_item = nullptr; w.rec_slot = nullptr;
-    w.cap_trans = 0; w.cap_path = 0; w.cap_segs = 0; w.cap_src = 0;
     ensure_trans_raw(std::max<uint64_t>(keep_trans, 1), std::max<uint64_t>(keep_src, 1));
     ensure_path_raw(std::max<uint64_t>(keep_path, cp / 8 + 1024));
     ensure_segs_raw(std::max<uint64_t>(keep_segs, cp / 2 + 1024));
   }
-}
-
-static void free_one(Workspace& w, void* q) {
-  if (!q) return;
-  (void)hipFree(q);
-  w.allocs.erase(std::find(w.allocs.begin(), w.allocs.end(), q));
 }
 
 void Matcher::ensure_trans(uint64_t n, uint64_t n_src) { grow_workspace([&] { ensure_trans_raw(n, n_src); }); }
@@ -5634,17 +5590,12 @@ void Matcher::ensure_turns() {
     Workspace& w = ws_;
     const uint64_t want_walk = (w.cap_src / kK2Items + 2) * (kWalkPerBlock + 1);
     if (w.route_d && w.cap_turn >= w.cap_trans && w.cap_walk >= want_walk) return;
-    free_one(w, w.route_d);
-    free_one(w, w.walk);
-    w.route_d = nullptr;
-    w.walk = nullptr;
-    w.cap_turn = 0;
-    w.cap_walk = 0;
-    w.route_d = dalloc<double>(w.allocs, w.cap_trans);
+    w.drop<WsTurns>();
+    w.route_d.reserve(w.cap_trans);
     w.cap_turn = w.cap_trans;
     // one region per K2 block of the item pool: a count and kWalkPerBlock entries
+    w.walk.reserve(want_walk);
     w.cap_walk = want_walk;
-    w.walk = dalloc<uint32_t>(w.allocs, w.cap_walk);
   });
 }
 
@@ -5652,31 +5603,16 @@ void Matcher::ensure_trans_raw(uint64_t n, uint64_t n_src) {
   {
     Workspace& w = ws_;
     if (!(n <= w.cap_trans && w.route)) {
-      free_one(w, w.route);
-      free_one(w, w.route_d);
-      free_one(w, w.walk);
-      w.route = nullptr;
-      w.route_d = nullptr;
-      w.walk = nullptr;
-      w.cap_trans = 0;
-      w.cap_turn = 0;
-      w.cap_walk = 0;
+      w.drop<WsTrans>();
+      w.drop<WsTurns>();   // (sized with route: ensure_turns takes them again)
       const uint64_t c = n + n / 4 + 1024;
-      w.route = dalloc<uint32_t>(w.allocs, c);
+      w.route.reserve(c);
       w.cap_trans = c;
     }
     if (!(n_src <= w.cap_src && w.src_item)) {
-      for (uint32_t** q : {&w.src_item, &w.rl_routes_a, &w.rl_routes_b, &w.rl_routes_0, &w.rl_routes_c}) {
-        free_one(w, *q);
-        *q = nullptr;
-      }
-      w.cap_src = 0;
+      w.drop<WsSrc>();
       const uint64_t c = n_src + n_src / 4 + 1024;
-      w.src_item = dalloc<uint32_t>(w.allocs, c);
-      w.rl_routes_a = dalloc<uint32_t>(w.allocs, c);   // overflow lists hold (pair, source) items
-      w.rl_routes_b = dalloc<uint32_t>(w.allocs, c);
-      w.rl_routes_0 = dalloc<uint32_t>(w.allocs, c);
-      w.rl_routes_c = dalloc<uint32_t>(w.allocs, c);
+      for (DevBuf<uint32_t>* q : {&w.src_item, &w.rl_routes_a, &w.rl_routes_b, &w.rl_routes_0, &w.rl_routes_c}) q->reserve(c);
       w.cap_src = c;
     }
   }
@@ -5686,11 +5622,9 @@ void Matcher::ensure_path_raw(uint64_t n) {
   {
     Workspace& w = ws_;
     if (n <= w.cap_path && w.path_pool) return;
-    free_one(w, w.path_pool);
-    w.path_pool = nullptr;
-    w.cap_path = 0;
+    w.drop<WsPath>();
     const uint64_t c = n + n / 4 + 1024;
-    w.path_pool = dalloc<uint32_t>(w.allocs, c);
+    w.path_pool.reserve(c);
     w.cap_path = c;
   }
 }
@@ -5699,42 +5633,15 @@ void Matcher::ensure_segs_raw(uint64_t n) {
   {
     Workspace& w = ws_;
     if (n <= w.cap_segs && w.segs) return;
-    for (void** q : {(void**)&w.segs, (void**)&w.reps, (void**)&w.rec_slot}) {
-      free_one(w, *q);
-      *q = nullptr;
-    }
-    w.cap_segs = 0;
+    w.drop<WsSegs>();
     const uint64_t c = n + n / 4 + 1024;
-    w.segs = dalloc<SegmentRec>(w.allocs, c);
-    w.reps = dalloc<ReportRec>(w.allocs, c);
-    w.rec_slot = dalloc<uint32_t>(w.allocs, c);
+    w.segs.reserve(c);
+    w.reps.reserve(c);
+    w.rec_slot.reserve(c);
     w.cap_segs = c;
   }
 }
 
-void Matcher::tic(int k) {
-  if (!((timing_mask_ >> k) & 1u)) return;
-  Ev ev;
-  if (!free_ev_.empty()) { ev = free_ev_.back(); free_ev_.pop_back(); }
-  else { RM_HIP(hipEventCreate(&ev.a)); RM_HIP(hipEventCreate(&ev.b)); }
-  ev.k = k;
-  RM_HIP(hipEventRecord(ev.a, stream_));
-  pending_.push_back(ev);
-}
-void Matcher::toc(int k) {
-  if (!((timing_mask_ >> k) & 1u) || pending_.empty()) return;
-  RM_HIP(hipEventRecord(pending_.back().b, stream_));
-}
-void Matcher::harvest_times() {
-  for (auto& ev : pending_) {
-    float ms = 0.f;
-    RM_HIP(hipEventElapsedTime(&ms, ev.a, ev.b));
-    kms_[ev.k] += ms;
-    klaunch_[ev.k] += 1;
-    free_ev_.push_back(ev);
-  }
-  pending_.clear();
-}
 void Matcher::kernel_times(double* ms, uint64_t* launches) {
   for (int i = 0; i < kNumKernels; ++i) { ms[i] = kms_[i]; if (launches) launches[i] = klaunch_[i]; }
 }
@@ -5744,7 +5651,7 @@ void Matcher::reset_kernel_times() {
 
 void Matcher::sync() {
   RM_HIP(hipStreamSynchronize(stream_));
-  harvest_times();
+  timer_.harvest(kms_, klaunch_);
 }
 
 // delta-stepping width of the wave search tiers (SearchTargets); RM_SEARCH_DELTA_M overrides
@@ -5833,16 +5740,13 @@ void Matcher::use_ws_inputs() {
 }
 
 void Matcher::ensure_pack(uint64_t bytes) {
-  if (bytes <= pack_cap_ && hpack_ && dpack_) return;
+  if (bytes <= dpack_.cap() && hpack_ && dpack_) return;
   RM_HIP(hipStreamSynchronize(stream_));   // the previous upload has left the staging
-  if (hpack_) (void)hipHostFree(hpack_);
-  if (dpack_) (void)hipFree(dpack_);
-  hpack_ = nullptr; dpack_ = nullptr; pack_cap_ = 0;
+  hpack_.reset();
+  dpack_.reset();
   const uint64_t c = std::max<uint64_t>(bytes + bytes / 2, 1u << 20);
-  RM_HIP(hipHostMalloc((void**)&hpack_, c, hipHostMallocDefault));
-  std::vector<void*> one;
-  grow_workspace([&] { dpack_ = dalloc<char>(one, c); });
-  pack_cap_ = c;
+  hpack_.reserve(c, "pinned staging of a small batch does not fit in host memory");
+  grow_workspace([&] { dpack_.reserve(c); });
 }
 
 void Matcher::run(const HostBatch& hb, const RunParams& rp) {
@@ -5882,7 +5786,7 @@ void Matcher::run(const HostBatch& hb, const RunParams& rp) {
     std::memcpy(hpack_ + o_acc, hb.accuracy, P * 4);
     std::memcpy(hpack_ + o_time, hb.time, P * 8);
     RM_HIP(hipMemcpyAsync(dpack_, hpack_, bytes, hipMemcpyHostToDevice, st));
-    in_.trace_off = (const uint32_t*)dpack_;
+    in_.trace_off = (const uint32_t*)dpack_.get();
     in_.trace_opt = (const uint32_t*)(dpack_ + o_topt);
     in_.opts = (const MatchOptions*)(dpack_ + o_opts);
     in_.lon = (const float*)(dpack_ + o_lon);
@@ -5987,13 +5891,10 @@ __global__ void __launch_bounds__(64) k_parse_json(const uint8_t* s, const uint6
 void Matcher::json_reserve_bytes(uint64_t bytes) {
   RM_HIP(hipSetDevice(eng_->device()));
   if (bytes <= jcap_ && jdev_) return;
-  if (jdev_) { RM_HIP(hipStreamSynchronize(stream_)); (void)hipFree(jdev_); jdev_ = nullptr; jcap_ = 0; }
+  if (jdev_) RM_HIP(hipStreamSynchronize(stream_));
+  jcap_ = 0;
   const uint64_t c = std::max<uint64_t>(bytes + bytes / 4, 1u << 20);
-  grow_workspace([&] {
-    const hipError_t e = hipMalloc((void**)&jdev_, c + kJsonPad);   // windows read up to kJsonPad past a span
-    if (e == hipErrorOutOfMemory) { (void)hipGetLastError(); jdev_ = nullptr; throw OutOfDeviceMemory("JSON buffer"); }
-    RM_HIP(e);
-  });
+  grow_workspace([&] { jdev_.reserve(c + kJsonPad); });   // windows read up to kJsonPad past a span
   jcap_ = c;
 }
 
@@ -6002,14 +5903,14 @@ void Matcher::json_reserve(uint64_t points, uint32_t traces, uint32_t nopts) {
   ensure(points, traces, nopts);
   if (traces > jtcap_ || !jspan_ || !jflag_ || !jtsp_) {
     RM_HIP(hipStreamSynchronize(stream_));
-    for (void* q : {jspan_, (void*)jflag_, jtsp_})
-      if (q) (void)hipFree(q);
-    jspan_ = nullptr; jflag_ = nullptr; jtsp_ = nullptr;
+    jspan_.reset(); jflag_.reset(); jtsp_.reset();
     jtcap_ = 0;   // a failed allocation below leaves nothing recorded
     const uint32_t c = std::max<uint32_t>(traces + traces / 4 + 1u, 1024u);
-    RM_HIP(hipMalloc((void**)&jspan_, (uint64_t)c * 16u));
-    RM_HIP(hipMalloc((void**)&jflag_, (uint64_t)c * 4u));
-    RM_HIP(hipMalloc((void**)&jtsp_, (uint64_t)c * 16u));
+    grow_workspace([&] {
+      jspan_.reserve(2ull * c);
+      jflag_.reserve(c);
+      jtsp_.reserve(c);
+    });
     jtcap_ = c;
   }
 }
@@ -6030,9 +5931,9 @@ void Matcher::json_parse(const uint64_t* span, const uint32_t* trace_off, uint32
   RM_HIP(hipMemcpyAsync(jspan_, span, T * 16ull, hipMemcpyHostToDevice, stream_));
   RM_HIP(hipMemcpyAsync(w.trace_off, trace_off, (T + 1ull) * 4u, hipMemcpyHostToDevice, stream_));
   RM_HIP(hipMemsetAsync(jflag_, 0, T * 4ull, stream_));
-  hipLaunchKernelGGL(k_parse_json, dim3(std::min<uint32_t>(T, 16384u)), dim3(64), 0, stream_, (const uint8_t*)jdev_,
+  hipLaunchKernelGGL(k_parse_json, dim3(std::min<uint32_t>(T, 16384u)), dim3(64), 0, stream_, (const uint8_t*)jdev_.get(),
                      (const uint64_t*)jspan_, (const uint32_t*)w.trace_off, T, w.lon, w.lat, w.time, w.acc, jflag_,
-                     (double2*)jtsp_);
+                     jtsp_);
   RM_HIP(hipGetLastError());
   RM_HIP(hipMemcpyAsync(flags, jflag_, T * 4ull, hipMemcpyDeviceToHost, stream_));
   RM_HIP(hipMemcpyAsync(tspan, jtsp_, T * 16ull, hipMemcpyDeviceToHost, stream_));
@@ -6079,7 +5980,7 @@ void Matcher::run_parsed(const uint32_t* trace_off, uint32_t T, const MatchOptio
 // outgrows the LDS wave tier
 void Matcher::ensure_global_search() {
   if (ws_.gsearch) return;
-  ws_.gsearch = dalloc<char>(ws_.allocs, (uint64_t)kGlobalGrid * sizeof(GlobalPathSmem));
+  ws_.gsearch.reserve((uint64_t)kGlobalGrid * sizeof(GlobalPathSmem));
 }
 
 // read the control words (and nothing else) into hctl_[0..kCtlWords)
@@ -6238,7 +6139,7 @@ void Matcher::Stages::routes(const DevBatch& v) const {
   if (tg.launch) hipLaunchKernelGGL(k_routes_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
   // the global tier runs in line once its scratch exists (ensure_global_search)
   if (m.ws_.gsearch)
-    hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch);
+    hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch.get());
   m.toc(kKRoutes);
 }
 
@@ -6261,7 +6162,7 @@ void Matcher::Stages::paths(const DevBatch& v) const {
   if (chain) hipLaunchKernelGGL(k_paths_wave_s, dim3(tg.wave_s), dim3(64), 0, st, g, v);
   if (tg.launch) hipLaunchKernelGGL(k_paths_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
   if (m.ws_.gsearch)
-    hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch);
+    hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch.get());
   m.toc(kKPaths);
 }
 
@@ -6354,18 +6255,12 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
     }
   }
   if (prefetch) {
-    if (T + 1 > hoff_cap_) {
-      if (hoff_) RM_HIP(hipHostFree(hoff_));
-      hoff_ = nullptr; hoff_cap_ = 0;
-      const uint64_t c = std::max<uint64_t>(T + 1 + T / 2, 4096);
-      RM_HIP(hipHostMalloc((void**)&hoff_, c * 4, hipHostMallocDefault));
-      hoff_cap_ = c;
-    }
-    uint32_t* d_off = (uint32_t*)dl_dev_;
+    if (T + 1 > hoff_.cap()) hoff_.reserve(std::max<uint64_t>(T + 1 + T / 2, 4096));
+    uint32_t* d_off = (uint32_t*)dl_dev_.get();
     hipLaunchKernelGGL(k_seg_offsets_small, dim3(1), dim3(1024), 0, st, v, d_off);
     hipLaunchKernelGGL(k_gather_recs, dim3(std::min<uint32_t>(T, 8192u)), dim3(64), 0, st, T, (const uint32_t*)w.seg_base,
-                       (const uint32_t*)w.seg_cnt, (const uint32_t*)d_off, (const unsigned long long*)w.segs, kSegWords,
-                       (unsigned long long*)((char*)dl_dev_ + offb));
+                       (const uint32_t*)w.seg_cnt, (const uint32_t*)d_off, (const unsigned long long*)w.segs.get(), kSegWords,
+                       (unsigned long long*)(dl_dev_ + offb));
     RM_HIP(hipMemcpyAsync(hoff_, d_off, (T + 1) * 4ull, hipMemcpyDeviceToHost, st));
   }
   read_back(true);
@@ -6489,7 +6384,7 @@ void Matcher::run_device(const RunParams& rp) {
   eng_->ensure_balls(mode_mask_);
   if (turn_mask_) eng_->ensure_turn_rows(turn_mask_);
   const DevGraph g = eng_->dev_snapshot();
-  if (!hctl_) RM_HIP(hipHostMalloc((void**)&hctl_, 32 * sizeof(uint32_t), hipHostMallocDefault));
+  if (!hctl_) hctl_.reserve(32);
   seg_prefetched_ = false;
   // (a forced locality order takes the ordinary path: the small one runs in slot order)
   if (P <= small_batch_points() && locality_ <= 0 && run_small(rp, g)) return;
@@ -6597,7 +6492,7 @@ void Matcher::run_device(const RunParams& rp) {
       // routes outgrew the LDS wave tier: run them in the global tier, then K3 and paths again
       ensure_global_search();
       routes_global_done = true;
-      hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
+      hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
       launch_viterbi(T, st, v);
       RM_HIP(hipMemsetAsync(w.path_cnt, 0, P * sizeof(uint32_t), st));
       zero_ctl({kCtlPathUsed, kCtlPathsLaneToReg2, kCtlPathsReg2ToGroup});
@@ -6607,7 +6502,7 @@ void Matcher::run_device(const RunParams& rp) {
     if (!w.gsearch && hctl_[kCtlPathsWaveToGlobal]) {
       // chosen transitions whose path search outgrew the LDS wave tier
       ensure_global_search();
-      hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch);
+      hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
       scan_records();
       read_records();
     }
@@ -6650,16 +6545,12 @@ void report_segments(int device, uint32_t T, const uint32_t* seg_off, const Segm
   for (uint32_t k = 0; k < T; ++k)
     if (seg_off[k + 1] < seg_off[k]) throw std::runtime_error("segment offsets not monotone");
   const uint64_t S = seg_off[T];
-  std::vector<void*> L;
-  struct Free { std::vector<void*>& l; ~Free() { for (void* p : l) (void)hipFree(p); } } fr{L};
-  uint32_t* d_off = dalloc<uint32_t>(L, T + 1);
-  SegmentRec* d_segs = dalloc<SegmentRec>(L, S);
-  double* d_end = dalloc<double>(L, T);
-  double* d_thr = dalloc<double>(L, T);
-  uint32_t* d_rm = dalloc<uint32_t>(L, T);
-  uint32_t* d_tm = dalloc<uint32_t>(L, T);
-  ReportRec* d_reps = dalloc<ReportRec>(L, S);
-  ReportStats* d_st = dalloc<ReportStats>(L, T);
+  DevBuf<uint32_t> d_off(T + 1);
+  DevBuf<SegmentRec> d_segs(S);
+  DevBuf<double> d_end(T), d_thr(T);
+  DevBuf<uint32_t> d_rm(T), d_tm(T);
+  DevBuf<ReportRec> d_reps(S);
+  DevBuf<ReportStats> d_st(T);
   RM_HIP(hipMemcpy(d_off, seg_off, (T + 1) * 4ull, hipMemcpyHostToDevice));
   if (S) RM_HIP(hipMemcpy(d_segs, segs, S * sizeof(SegmentRec), hipMemcpyHostToDevice));
   RM_HIP(hipMemcpy(d_end, end_time, T * 8ull, hipMemcpyHostToDevice));
@@ -6796,55 +6687,32 @@ uint64_t Matcher::count_segments() {
 // grow-only pinned host buffer of the downloads: failing to pin it is a batch too large for
 // the host, which the coalescer splits (serve_policy.hpp), not a generic error
 void Matcher::grow_dl_host(size_t need) {
-  if (need <= dl_host_bytes_) return;
-  const size_t want = std::max(need, dl_host_bytes_ + dl_host_bytes_ / 2);
-  if (dl_host_) RM_HIP(hipHostFree(dl_host_));
-  dl_host_ = nullptr;
-  dl_host_bytes_ = 0;
-  void* p = nullptr;
-  size_t got = want;
-  hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-  if (e != hipSuccess && want > need) {
-    (void)hipGetLastError();
-    got = need;
-    e = hipHostMalloc(&p, need, hipHostMallocDefault);
-  }
-  if (e != hipSuccess) {
-    (void)hipGetLastError();
+  if (need <= dl_host_.cap()) return;
+  const size_t want = std::max<size_t>(need, dl_host_.cap() + dl_host_.cap() / 2);
+  hipError_t e = dl_host_.try_reserve(want);
+  if (e != hipSuccess && want > need) e = dl_host_.try_reserve(need);
+  if (e != hipSuccess)
     throw BatchTooLarge("pinned download buffer of " + std::to_string(need) + " bytes: " + hipGetErrorString(e));
-  }
-  dl_host_ = p;
-  dl_host_bytes_ = got;
 }
 
 // grow-only device buffer of the downloads (offsets, then the compacted records)
 void Matcher::grow_dl_dev(size_t dev_need) {
-  if (dev_need <= dl_dev_bytes_) return;
-  const size_t want = std::max(dev_need, dl_dev_bytes_ + dl_dev_bytes_ / 2);
-  if (dl_dev_) RM_HIP(hipFree(dl_dev_));
-  dl_dev_ = nullptr;
-  dl_dev_bytes_ = 0;
+  if (dev_need <= dl_dev_.cap()) return;
+  const size_t want = std::max<size_t>(dev_need, dl_dev_.cap() + dl_dev_.cap() / 2);
+  dl_dev_.reset();
   // test hook: allocations above RM_TEST_DOWNLOAD_ALLOC_LIMIT bytes fail as out of memory
   // (tests/test_gpu_isolation.py drives the failure and the call after it)
   const char* lim = std::getenv("RM_TEST_DOWNLOAD_ALLOC_LIMIT");
   const size_t limit = lim && *lim ? (size_t)std::strtoull(lim, nullptr, 10) : ~(size_t)0;
-  void* p = nullptr;
-  size_t got = 0;
   for (const size_t sz : {want, dev_need}) {
     if (sz > limit) continue;
-    std::vector<void*> buf;
     try {
-      dalloc<char>(buf, sz);
+      dl_dev_.reserve(sz);
+      return;
     } catch (const OutOfDeviceMemory&) {
-      continue;
     }
-    p = buf[0];
-    got = sz;
-    break;
   }
-  if (!p) throw BatchTooLarge("segment download buffer of " + std::to_string(dev_need) + " bytes does not fit in HBM");
-  dl_dev_ = p;
-  dl_dev_bytes_ = got;
+  throw BatchTooLarge("segment download buffer of " + std::to_string(dev_need) + " bytes does not fit in HBM");
 }
 
 void Matcher::download_compacted(const uint32_t* d_base, const uint32_t* d_cnt, const void* d_src, uint32_t words,
@@ -6860,7 +6728,7 @@ void Matcher::download_compacted(const uint32_t* d_base, const uint32_t* d_cnt, 
   // and the next call allocates again; running out of memory here is a batch too large for the
   // device, which the coalescer splits (serve_policy.hpp), not a generic error.
   grow_dl_host(offb);
-  uint32_t* hc = (uint32_t*)dl_host_;
+  uint32_t* hc = (uint32_t*)dl_host_.get();
   RM_HIP(hipMemcpyAsync(hc, d_cnt, T * 4ull, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
   uint64_t at = 0;
@@ -6875,14 +6743,14 @@ void Matcher::download_compacted(const uint32_t* d_base, const uint32_t* d_cnt, 
   const size_t dev_need = offb + recb + 8;
   grow_dl_dev(dev_need);
   grow_dl_host(offb + recb + 8);
-  hc = (uint32_t*)dl_host_;
+  hc = (uint32_t*)dl_host_.get();
   std::memcpy(hc, off, offb);
-  uint32_t* d_off = (uint32_t*)dl_dev_;
-  unsigned long long* d_dst = (unsigned long long*)((char*)dl_dev_ + ((offb + 7) & ~(size_t)7));
+  uint32_t* d_off = (uint32_t*)dl_dev_.get();
+  unsigned long long* d_dst = (unsigned long long*)(dl_dev_ + ((offb + 7) & ~(size_t)7));
   RM_HIP(hipMemcpyAsync(d_off, hc, offb, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_gather_recs, dim3(std::min<uint32_t>(T, 8192u)), dim3(64), 0, st, T, d_base, d_cnt, d_off,
                      (const unsigned long long*)d_src, words, d_dst);
-  char* h_dst = (char*)dl_host_ + ((offb + 7) & ~(size_t)7);
+  char* h_dst = dl_host_ + ((offb + 7) & ~(size_t)7);
   RM_HIP(hipMemcpyAsync(h_dst, d_dst, recb, hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
   std::memcpy(dst, h_dst, recb);
@@ -6900,7 +6768,7 @@ bool Matcher::download_prefetched(uint32_t* off, void* dst, const std::function<
   const size_t offb = (((size_t)T + 1) * 4 + 7) & ~(size_t)7;
   const size_t recb = (size_t)at * sizeof(SegmentRec);
   grow_dl_host(recb);
-  RM_HIP(hipMemcpyAsync(dl_host_, (const char*)dl_dev_ + offb, recb, hipMemcpyDeviceToHost, stream_));
+  RM_HIP(hipMemcpyAsync(dl_host_, dl_dev_ + offb, recb, hipMemcpyDeviceToHost, stream_));
   RM_HIP(hipStreamSynchronize(stream_));
   std::memcpy(dst, dl_host_, recb);
   return true;

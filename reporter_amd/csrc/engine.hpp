@@ -160,51 +160,73 @@ enum GateBit : uint32_t {
 };
 constexpr int kInlinePath = 8;  // path edges stored inline per slot (no allocation)
 
-struct Workspace {
-  uint64_t cap_points = 0, cap_traces = 0, cap_trans = 0, cap_path = 0, cap_opts = 0, cap_segs = 0, cap_src = 0;
+// Each group of buffers carries the capacity that sizes it, and is dropped as a whole by assigning
+// it a fresh value (Workspace::drop); every buffer is a hipMalloc of its own.
+struct WsPoints {   // sized by the batch's points, traces and option sets (Matcher::alloc_points)
+  uint64_t cap_points = 0, cap_traces = 0, cap_opts = 0;
   // inputs
-  uint32_t* trace_off = nullptr; float* lon = nullptr; float* lat = nullptr; double* time = nullptr;
-  float* acc = nullptr; MatchOptions* opts = nullptr; uint32_t* trace_opt = nullptr;
+  DevBuf<uint32_t> trace_off; DevBuf<float> lon, lat; DevBuf<double> time;
+  DevBuf<float> acc; DevBuf<MatchOptions> opts; DevBuf<uint32_t> trace_opt;
   // per slot
-  uint32_t* slot_trace = nullptr; uint32_t* n_states = nullptr; uint32_t* state_orig = nullptr;
-  double* state_time = nullptr;     // epoch time of the state at each slot (K4 interpolation)
+  DevBuf<uint32_t> slot_trace, n_states, state_orig;
+  DevBuf<double> state_time;        // epoch time of the state at each slot (K4 interpolation)
   // candidate descriptors, 2 x uint4 per (slot, rank): {road, s_cm, len_cm, spf | spr << 16},
   // {node0, node1, time_ms(s_cm) forward from node0, time_ms(len_cm - s_cm) reverse from node1}
   // (sp* = mode-capped speed of the directed edge in 0.1 km/h, 0 when the mode cannot use it)
-  uint8_t* cand_n = nullptr; uint4* cand_desc = nullptr; float* cand_sq = nullptr;
-  uint32_t* trans_cnt = nullptr; uint32_t* trans_off = nullptr; double* gc = nullptr; uint32_t* route = nullptr;
-  double* route_d = nullptr;   // per transition: turn_m + |route_m - gc| (rule 3b), batches with turn costs only
-  uint64_t cap_turn = 0;
-  uint32_t* walk = nullptr;    // K2 -> k_turn_walks: transitions whose turn weight is walked (item << 4 | target)
-  uint64_t cap_walk = 0;
-  uint4* pair_info = nullptr;  // per layer pair slot: {route bound cm, time bound ms, KA | KB << 8 | mode << 16, 0}
-  uint32_t* src_cnt = nullptr; uint32_t* src_off = nullptr; uint32_t* src_item = nullptr;
-  int8_t* choice = nullptr; uint8_t* chain_start = nullptr; uint8_t* bp = nullptr;
-  uint32_t* path_off = nullptr; uint32_t* path_cnt = nullptr; uint32_t* path_pool = nullptr; uint32_t* route_dist = nullptr;
-  uint2* path_sab = nullptr;        // per chosen transition: source / target candidate offsets on their roads (cm)
-  uint32_t* path_inline = nullptr;  // kInlinePath edges per slot
+  DevBuf<uint8_t> cand_n; DevBuf<uint4> cand_desc; DevBuf<float> cand_sq;
+  DevBuf<uint32_t> trans_cnt, trans_off; DevBuf<double> gc;
+  DevBuf<uint4> pair_info;   // per layer pair slot: {route bound cm, time bound ms, KA | KB << 8 | mode << 16, 0}
+  DevBuf<uint32_t> src_cnt, src_off;
+  DevBuf<int8_t> choice; DevBuf<uint8_t> chain_start, bp;
+  DevBuf<uint32_t> path_off, path_cnt, route_dist;
+  DevBuf<uint2> path_sab;           // per chosen transition: source / target candidate offsets on their roads (cm)
+  DevBuf<uint32_t> path_inline;     // kInlinePath edges per slot
   // per trace outputs
-  SegmentRec* segs = nullptr; uint32_t* seg_base = nullptr; uint32_t* seg_cnt = nullptr;
-  uint32_t* trav_off = nullptr;     // first traversal record of each slot (scan of path_cnt)
-  uint32_t* rec_slot = nullptr;     // K4: transition slot of each traversal record (k_rec_slot)
-  ReportRec* reps = nullptr; uint32_t* rep_cnt = nullptr; ReportStats* stats = nullptr;
-  uint32_t* ctl = nullptr;   // the control words (CtlWord) and the hand-over lists they count
-  uint32_t* rl_routes_a = nullptr; uint32_t* rl_routes_b = nullptr; uint32_t* rl_routes_0 = nullptr;
-  uint32_t* rl_paths_a = nullptr; uint32_t* rl_paths_b = nullptr; uint32_t* rl_cand = nullptr;
-  // global-memory search tier: its hand-over lists (kCtlWaveToGlobal, kCtlPathsWaveToGlobal) and scratch
-  uint32_t* rl_routes_c = nullptr; uint32_t* rl_paths_c = nullptr; void* gsearch = nullptr;
-  uint32_t* trace_err = nullptr;            // per trace: error bits (kErr*) of that trace alone
-  unsigned long long* tot64 = nullptr;      // u64 totals: [0] transitions [1] sources [2] path edges
-  unsigned long long* scan_bkt = nullptr;   // a steady run's coarse scan buckets (rm_common.hpp scan_base_lane)
-  unsigned long long* tot_part = nullptr;   // per-block partial pairs of those totals (the scans fold them)
-  // locality order (engine.hip k_loc_count / k_loc_scatter): the sorted state slots, each slot's
-  // region bucket, the bucket cursors and the item counts in sorted order; allocated on the first
-  // run that uses it (cap_sort slots)
+  DevBuf<uint32_t> seg_base, seg_cnt;
+  DevBuf<uint32_t> trav_off;        // first traversal record of each slot (scan of path_cnt)
+  DevBuf<uint32_t> rep_cnt; DevBuf<ReportStats> stats;
+  DevBuf<uint32_t> ctl;   // the control words (CtlWord) and the hand-over lists they count
+  DevBuf<uint32_t> rl_paths_a, rl_paths_b, rl_cand;
+  DevBuf<uint32_t> rl_paths_c;      // global-memory search tier: the path stage's hand-over list (kCtlPathsWaveToGlobal)
+  DevBuf<uint32_t> trace_err;               // per trace: error bits (kErr*) of that trace alone
+  DevBuf<unsigned long long> tot64;         // u64 totals: [0] transitions [1] sources [2] path edges
+  DevBuf<unsigned long long> scan_bkt;      // a steady run's coarse scan buckets (rm_common.hpp scan_base_lane)
+  DevBuf<unsigned long long> tot_part;      // per-block partial pairs of those totals (the scans fold them)
+};
+struct WsTrans {    // the transition pool
+  uint64_t cap_trans = 0;
+  DevBuf<uint32_t> route;
+};
+struct WsSrc {      // K2's sources and the routes stage's hand-over lists ((pair, source) items; c: kCtlWaveToGlobal)
+  uint64_t cap_src = 0;
+  DevBuf<uint32_t> src_item, rl_routes_a, rl_routes_b, rl_routes_0, rl_routes_c;
+};
+struct WsTurns {    // batches with turn costs only, allocated the first time one runs (Matcher::ensure_turns)
+  uint64_t cap_turn = 0, cap_walk = 0;
+  DevBuf<double> route_d;    // per transition: turn_m + |route_m - gc| (rule 3b)
+  DevBuf<uint32_t> walk;     // K2 -> k_turn_walks: transitions whose turn weight is walked (item << 4 | target)
+};
+struct WsPath {     // the path pool
+  uint64_t cap_path = 0;
+  DevBuf<uint32_t> path_pool;
+};
+struct WsSegs {     // the record pools
+  uint64_t cap_segs = 0;
+  DevBuf<SegmentRec> segs;
+  DevBuf<ReportRec> reps;
+  DevBuf<uint32_t> rec_slot;   // K4: transition slot of each traversal record (k_rec_slot)
+};
+// locality order (engine.hip k_loc_count / k_loc_scatter): the sorted state slots, each slot's
+// region bucket, the bucket cursors and the item counts in sorted order; allocated on the first
+// run that uses it (cap_sort slots)
+struct WsSort {
   uint64_t cap_sort = 0;
-  uint32_t* perm = nullptr; uint16_t* loc_key = nullptr; uint32_t* loc_cursor = nullptr; uint32_t* pcnt = nullptr;
-  std::vector<void*> allocs;
-  ~Workspace();
-  void release();
+  DevBuf<uint32_t> perm; DevBuf<uint16_t> loc_key; DevBuf<uint32_t> loc_cursor, pcnt;
+};
+struct Workspace : WsPoints, WsTrans, WsSrc, WsTurns, WsPath, WsSegs, WsSort {
+  DevBuf<char> gsearch;   // global-memory search tier: its scratch, allocated on first use
+  template <class Group>
+  void drop() { static_cast<Group&>(*this) = Group{}; }
 };
 
 // Raw per-vehicle point stream (the trace files simple_reporter's download phase writes:
@@ -649,11 +671,13 @@ class Matcher {
   void check_batch(uint32_t T, const uint32_t* trace_off, const MatchOptions* opts, uint32_t n_opts,
                    const uint32_t* trace_opt);
   void scan_options(const MatchOptions* opts, uint32_t n_opts);
-  char* jdev_ = nullptr;        // device JSON path: trace-array bytes (grow-only), per-trace spans,
-  uint64_t jcap_ = 0;           // flags and first / last times
-  void* jspan_ = nullptr;
-  uint32_t* jflag_ = nullptr;
-  void* jtsp_ = nullptr;
+  // device JSON path (grow-only): the trace-array bytes (jcap_ of them and a kJsonPad tail), and
+  // per trace (jtcap_) its span, flag and first / last times
+  DevBuf<char> jdev_;
+  uint64_t jcap_ = 0;
+  DevBuf<uint64_t> jspan_;
+  DevBuf<uint32_t> jflag_;
+  DevBuf<double2> jtsp_;
   uint32_t jtcap_ = 0;
   void ensure_trans(uint64_t n, uint64_t n_src);
   void ensure_path(uint64_t n);
@@ -667,9 +691,8 @@ class Matcher {
   void ensure_segs_raw(uint64_t n);
   void ensure_global_search();
   void read_ctl();
-  void tic(int k);
-  void toc(int k);
-  void harvest_times();
+  void tic(int k) { if ((timing_mask_ >> k) & 1u) timer_.tic(k, stream_); }
+  void toc(int k) { if ((timing_mask_ >> k) & 1u) timer_.toc(stream_); }
   // per-trace record lists (base[k], cnt[k] in units of `words` u64) compacted on the device and
   // downloaded through pinned memory into dst; off gets the T+1 offsets
   void download_compacted(const uint32_t* d_base, const uint32_t* d_cnt, const void* d_src, uint32_t words,
@@ -700,16 +723,16 @@ class Matcher {
   void ensure_pack(uint64_t bytes);
 
   Engine* eng_;
+  // Every member below frees itself after ~Matcher's body, which synchronises and destroys the
+  // stream first: none of them needs the stream to go.
+  hipStream_t stream_ = nullptr;
   InputView in_;
-  char* hpack_ = nullptr;      // pinned staging and device block of a small run()'s inputs (grow-only)
-  char* dpack_ = nullptr;
-  uint64_t pack_cap_ = 0;
-  uint32_t* hoff_ = nullptr;   // pinned: a small run's per-trace segment offsets (T + 1), prefetched
-  uint64_t hoff_cap_ = 0;
+  PinBuf<char> hpack_;         // pinned staging and device block of a small run()'s inputs (grow-only,
+  DevBuf<char> dpack_;         // both of dpack_.cap() bytes)
+  PinBuf<uint32_t> hoff_;      // pinned: a small run's per-trace segment offsets (T + 1), prefetched
   bool seg_prefetched_ = false;
-  void* dl_dev_ = nullptr;     // grow-only device / pinned host buffers of download_compacted
-  void* dl_host_ = nullptr;
-  size_t dl_dev_bytes_ = 0, dl_host_bytes_ = 0;
+  DevBuf<char> dl_dev_;        // grow-only device / pinned host buffers of download_compacted
+  PinBuf<char> dl_host_;
   DevBuf<MatchedPoint> mp_dev_;   // grow-only device buffer of matched_points
   // matched_edges: grow-only device buffers (the visits staged per trace, the per-trace counts /
   // offsets / totals, the compacted visits, the shapes), its events and the last call's sizes
@@ -719,7 +742,6 @@ class Matcher {
   uint64_t me_n_ = 0, me_v_ = 0;
   double me_ms_ = 0.0;
   bool me_ran_ = false;
-  hipStream_t stream_ = nullptr;
   Workspace ws_;
   uint32_t n_traces_ = 0;
   uint64_t n_points_ = 0, n_trans_ = 0, n_path_ = 0, seg_used_ = 0;
@@ -731,7 +753,7 @@ class Matcher {
   bool locality_used_ = false;
   void ensure_sort(uint64_t n);
   uint32_t err_bits_ = 0;
-  uint32_t* hctl_ = nullptr;  // pinned host mirror of the control words
+  PinBuf<uint32_t> hctl_;     // pinned host mirror of the control words
   StageBufs sb_;
   std::shared_ptr<LineState> ls_;
   bool from_points_ = false;
@@ -740,8 +762,7 @@ class Matcher {
   float batch_radius_ = 0.f; // the batch's largest search_radius (m): K1's grid (Engine::k1_grid)
   void ensure_points(uint64_t n, uint32_t n_uuids, uint32_t n_opts);
   void ensure_rows(uint64_t n, uint32_t traces);
-  struct Ev { hipEvent_t a, b; int k; };
-  std::vector<Ev> pending_, free_ev_;
+  PartTimer timer_;           // the stages timed by HIP events (timing_mask_), harvested by sync()
   double kms_[kNumKernels] = {0};
   uint64_t klaunch_[kNumKernels] = {0};
 };
@@ -809,7 +830,9 @@ class Engine {
   int device_;
   Graph host_;
   DevGraph dg_{};
-  std::vector<void*> allocs_;
+  std::vector<DevBuf<char>> allocs_;   // the graph's arrays, uploaded by the constructor
+  DevBuf<uint2> ball_hdr_[5], ball_turn_[5];   // per mode the route balls and turn rows built later
+  DevBuf<uint4> ball_ent_[5];                  // (a twin mode shares its twin's: dg_ alone names them)
   mutable std::mutex ball_mu_;
   uint32_t ball_radius_cm_ = 40000;   // set from auto_ball_radius_cm(graph) at construction
   uint32_t ball_built_ = 0;             // mode bits

@@ -13,10 +13,11 @@
 //                     the wave's LDS stage; k_candidates_wave takes the overflow
 //   k_trans_count     pair constants + counts; k_scan_* lay out routes and K2 items
 //   k_routes_ball2    K2, block-expanded: one lane per transition, two route-ball probes per
-//                     target; search tiers (lane / reg2 / wave LDS / global) for the hand-overs
+//                     target; the search tiers for the hand-overs: k_routes_lane, k_routes_reg2, then
+//                     k_tier_grp / k_tier_wave / k_tier_global<RoutesStage | PathsStage> (one chain, two stages)
 //   k_viterbi         K3, one 16-lane DPP row per trace: fp64 costs in registers, backtrace
 //   k_paths_ball      one lane per chosen transition: labels from the balls, walk back by the
-//                     rows' canonical predecessors (+ the search tiers)
+//                     rows' canonical predecessors (+ the search tiers: k_paths_lane, k_paths_reg2, k_tier_*)
 //   k_rec_slot / k_seg_wave   K4: one wave per trace, traversal records 64 per step, runs by ballot
 //   k_report          A8 epilogue, one wave per trace: report() + speed histogram + duration sums
 //
@@ -74,7 +75,8 @@ struct DevBatch {  // POD view of the workspace for kernels
   SegmentRec* segs; uint32_t* seg_base; uint32_t* seg_cnt;
   uint32_t* trav_off;
   ReportRec* reps; uint32_t* rep_cnt; ReportStats* stats;
-  uint32_t* rl_routes_0;  // items the K2 ball tier hands to the search tiers (count ctl[kCtlBallToSearch])
+  // the control words and the search tiers' hand-over lists (wired to the tiers by RoutesStage / PathsStage alone)
+  uint32_t* rl_routes_0;
   uint32_t* ctl; uint32_t* rl_routes_a; uint32_t* rl_routes_b; uint32_t* rl_paths_a; uint32_t* rl_paths_b;
   uint32_t* rl_cand;
   uint32_t* rl_routes_c; uint32_t* rl_paths_c;
@@ -95,17 +97,82 @@ struct DevBatch {  // POD view of the workspace for kernels
   uint32_t gate;
 };
 
+// The search tiers' hand-over chain, described once for both stages.  The routes stage (K2) and the
+// path stage hand a search that outgrows one tier to the next: ball -> lane -> reg2 -> 16-lane group
+// -> 512-slot wave -> 4096-slot wave -> global memory.  A link is what lies between two tiers: a list
+// of items and the control word that counts it.
+enum Link : int { kLinkBallToSearch = 0, kLinkLaneToReg2, kLinkReg2ToGroup, kLinkGroupToWave512, kLinkWave512ToWave4096,
+                  kLinkWaveToGlobal, kLinks };
+struct LinkDesc { CtlWord word; uint32_t* DevBatch::*list; };
+#ifndef RM_GRP_H
+#define RM_GRP_H 256
+#endif
+#ifndef RM_GRP_PATH_H
+#define RM_GRP_PATH_H 128   // path searches are single-target: smaller (C3 radius 0: 10.3 -> 7.4 ms at 128)
+#endif
+template <int H, bool PATH> struct SearchSmem;
+template <int H, int W> __device__ bool routes_search_item(SearchSmem<H, false>&, uint4*, const DevGraph&, const DevBatch&, uint32_t);
+template <int H, int W> __device__ bool paths_search_item(SearchSmem<H, true>&, uint4*, const DevGraph&, const DevBatch&, uint64_t);
+// A stage: the group tier's hash size, whether its hashes keep predecessors, its links (four lists serve the six), its
+// item routine (one item searched in H slots by W lanes; false: outgrown) and the slot a failed item is charged to
+struct RoutesStage {   // items: (pair, source) indices t
+  static constexpr int kGrpHash = RM_GRP_H;
+  static constexpr bool kPath = false;
+  static __host__ __device__ constexpr LinkDesc link(int l) {
+    constexpr LinkDesc t[kLinks] = {{kCtlBallToSearch, &DevBatch::rl_routes_0}, {kCtlLaneToReg2, &DevBatch::rl_routes_a},
+                                    {kCtlReg2ToGroup, &DevBatch::rl_routes_b},
+                                    {kCtlGroupToWave512, &DevBatch::rl_routes_a},      // again: free once reg2 has run
+                                    {kCtlWave512ToWave4096, &DevBatch::rl_routes_0},   // again: free once the lane tier has run
+                                    {kCtlWaveToGlobal, &DevBatch::rl_routes_c}};
+    return t[l];
+  }
+  template <int H, int W>
+  static __device__ __forceinline__ bool item(SearchSmem<H, false>& sm, uint4* s_src, const DevGraph& g, const DevBatch& b,
+                                              uint32_t t) { return routes_search_item<H, W>(sm, s_src, g, b, t); }
+  static __device__ __forceinline__ uint64_t fail_slot(const DevBatch& b, uint32_t t) { return b.src_item[t]; }
+};
+struct PathsStage {    // items: slots p of chosen transitions
+  static constexpr int kGrpHash = RM_GRP_PATH_H;
+  static constexpr bool kPath = true;
+  static __host__ __device__ constexpr LinkDesc link(int l) {
+    constexpr LinkDesc t[kLinks] = {{kCtlPathsBallToSearch, &DevBatch::rl_routes_0},   // the routes stage's: free once K2 has run
+                                    {kCtlPathsLaneToReg2, &DevBatch::rl_paths_a}, {kCtlPathsReg2ToGroup, &DevBatch::rl_paths_b},
+                                    {kCtlPathsGroupToWave512, &DevBatch::rl_paths_a},      // again: free once the path reg2 tier has run
+                                    {kCtlPathsWave512ToWave4096, &DevBatch::rl_routes_0},   // again: free once the path lane tier has run
+                                    {kCtlPathsWaveToGlobal, &DevBatch::rl_paths_c}};
+    return t[l];
+  }
+  template <int H, int W>
+  static __device__ __forceinline__ bool item(SearchSmem<H, true>& sm, uint4* s_src, const DevGraph& g, const DevBatch& b,
+                                              uint32_t p) { return paths_search_item<H, W>(sm, s_src, g, b, p); }
+  static __device__ __forceinline__ uint64_t fail_slot(const DevBatch&, uint32_t p) { return p; }
+};
+// Link l's length and list, and an item appended to it.  (The links are compared one by one: a constant l folds
+// away, a kernel argument becomes scalar selects -- indexing the table by it cost k_tier_grp two VGPRs; no link: link 0.)
+struct LinkIn { uint32_t n; const uint32_t* list; };
+template <class St> __device__ __forceinline__ LinkIn link_in(const DevBatch& b, int l) {
+  int w = St::link(0).word;
+  const uint32_t* list = b.*St::link(0).list;
+#pragma unroll
+  for (int k = 1; k < kLinks; ++k) if (k == l) { w = St::link(k).word; list = b.*St::link(k).list; }
+  return {b.ctl[w], list};
+}
+template <class St> __device__ __forceinline__ void link_append(const DevBatch& b, int l, uint32_t item) {
+  (b.*St::link(l).list)[atomicAdd(&b.ctl[St::link(l).word], 1u)] = item;
+}
+
 __device__ __forceinline__ bool steady_abort(const DevBatch& b) {
   return ((b.gate & kGateSteady) && (b.tot[0] > b.trans_cap || b.tot[1] > b.src_cap)) ||
-         ((b.gate & kGateRoutesTiers) && b.ctl[kCtlBallToSearch] != 0u);
+         ((b.gate & kGateRoutesTiers) && link_in<RoutesStage>(b, kLinkBallToSearch).n != 0u);
 }
 
 __device__ __forceinline__ bool small_abort(const DevBatch& b) {
   if (!b.gate) return false;
-  const uint32_t* c = b.ctl;
-  return (c[kCtlErr] & kErrPathOverflow) != 0u ||
-         ((b.gate & kGateGlobal) && (c[kCtlWaveToGlobal] | c[kCtlPathsWaveToGlobal]) != 0u) || b.tot[2] > b.seg_cap ||
-         ((b.gate & kGatePathsTiers) && c[kCtlPathsBallToSearch] != 0u) || steady_abort(b);
+  return (b.ctl[kCtlErr] & kErrPathOverflow) != 0u ||
+         ((b.gate & kGateGlobal) &&
+          (link_in<RoutesStage>(b, kLinkWaveToGlobal).n | link_in<PathsStage>(b, kLinkWaveToGlobal).n) != 0u) ||
+         b.tot[2] > b.seg_cap || ((b.gate & kGatePathsTiers) && link_in<PathsStage>(b, kLinkBallToSearch).n != 0u) ||
+         steady_abort(b);
 }
 
 // A failure that belongs to one trajectory (too many roads in a radius, a search beyond every
@@ -2569,7 +2636,7 @@ __device__ void k2_walk_one(const DevGraph& g, const DevBatch& b, uint32_t t, ui
   b.route[ro] = k2_route_turn(g, A, T, ta0, ta1, r1, r0, s1, s0, h1s, h0s, make_uint2(v1.x, v1.y),
                               make_uint2(v0.x, v0.y), g.turn_w, gc, ok, d);
   b.route_d[ro] = d;
-  if (!ok) b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
+  if (!ok) link_append<RoutesStage>(b, kLinkBallToSearch, t);
 }
 // (launched with K2's grid and n_arg, one block per K2 block: the block's region of b.walk)
 #ifndef RM_WALK_THREADS
@@ -2663,7 +2730,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
     if constexpr (TURN) turn_ok = !pi.w || ((g.ball_turn_mask >> mode) & 1u);   // no turn rows: the search tiers weigh the turns
     if (!fits || S.h1.y == 0u || S.h0.y == 0u || !turn_ok) {   // the search tiers take it (they run later)
       S.bound = kNone;
-      b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
+      link_append<RoutesStage>(b, kLinkBallToSearch, t);
     }
   }
   // the block's transitions: an exclusive scan of the items' K_B (in slot order the items' routes
@@ -2716,7 +2783,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
   // items with a route the tables could not decide: the search tiers recompute all of its routes
   __syncthreads();
   if (live && ((sm.redo[threadIdx.x >> 5] >> (threadIdx.x & 31u)) & 1u) && sm.src[threadIdx.x].bound != kNone)
-    b.rl_routes_0[atomicAdd(&b.ctl[kCtlBallToSearch], 1u)] = t;
+    link_append<RoutesStage>(b, kLinkBallToSearch, t);
   if constexpr (TURN) {   // the count of the block's region of b.walk
     if (threadIdx.x == 0) b.walk[(uint64_t)blockIdx.x * (kWalkPerBlock + 1)] = min(sm.wn, kWalkPerBlock);
   }
@@ -2726,8 +2793,16 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
 // K2 lane tier: one lane per (layer pair, source) item.  The pair constants come from
 // one dwordx4 (pair_info) and every candidate from its 32-byte descriptor.  A search
 // that outgrows the registers is queued (as its item) for the LDS lane tier.
-// With `listed`, thread q takes the q-th item the ball tier handed over (rl_routes_0, ctl[kCtlBallToSearch]).
+// With `listed`, thread q takes the q-th item the ball tier handed over (kLinkBallToSearch).
 constexpr uint64_t kListedGrid = 4096;   // blocks of a grid-stride launch over hand-over lists
+
+// K2 item t decoded: pair slot, source rank, the pair's first route, pair_info, its fields, the source's cand_desc row
+struct K2Item { uint32_t p, i, base; uint4 pi; uint32_t bound, tmax, KB; int mode; uint64_t arow; };
+__device__ __forceinline__ K2Item k2_item(const DevBatch& b, uint32_t t) {
+  const uint32_t p = b.src_item[t], i = t - b.src_off[p];
+  const uint4 pi = b.pair_info[p];
+  return {p, i, b.trans_off[p], pi, pi.x, pi.y, (pi.z >> 8) & 0xffu, (int)(pi.z >> 16), ((uint64_t)(p - 1) * kMaxCand + i) * 2};
+}
 
 // TURN: compiled with the turn-weight walks (rule 3b) only for batches with turn costs (they
 // cost the plain tier registers: scratch 12 -> 64 bytes per lane)
@@ -2735,29 +2810,23 @@ template <bool TURN>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LANE_WPE))) k_routes_lane(DevGraph g, DevBatch b, uint32_t n_items, int listed) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   // grid-stride: a listed launch is sized for every item but usually finds few hand-overs
-  const uint32_t n = listed ? b.ctl[kCtlBallToSearch] : (n_items != kNone ? n_items : (uint32_t)b.tot[1]);
+  const uint32_t n = listed ? link_in<RoutesStage>(b, kLinkBallToSearch).n : (n_items != kNone ? n_items : (uint32_t)b.tot[1]);
   __shared__ uint32_t s_res[kMaxCand][256];
   for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x) {
-  const uint32_t t = listed ? b.rl_routes_0[q] : q;
-  const uint32_t p = b.src_item[t];
-  const uint4 pi = b.pair_info[p];
-  const uint32_t i = t - b.src_off[p];
-  const uint32_t base = b.trans_off[p];
-  const uint32_t bound = pi.x, tmax = pi.y, KB = (pi.z >> 8) & 0xffu;
-  const int mode = (int)(pi.z >> 16);
-  const uint64_t arow = ((uint64_t)(p - 1) * kMaxCand + i) * 2;
-  const uint4 a0 = b.cand_desc[arow], a1 = b.cand_desc[arow + 1];
+  const uint32_t t = listed ? link_in<RoutesStage>(b, kLinkBallToSearch).list[q] : q;
+  const K2Item it = k2_item(b, t);
+  const uint4 a0 = b.cand_desc[it.arow], a1 = b.cand_desc[it.arow + 1];
   RegLabels S;
   unsigned long long rk1, rk0;
   // no early stop here: at the bounds this tier completes (tens of metres) the targets' check
   // costs more than the settles it saves (C2 --ball-radius 0: 2.1 -> 3.4 ms); tier 2 has it
-  lane_search(S, g, g.relax[mode], bound, a0, a1, rk1, rk0);
+  lane_search(S, g, g.relax[it.mode], it.bound, a0, a1, rk1, rk0);
   if (S.ovf) {
-    b.rl_routes_a[atomicAdd(&b.ctl[kCtlLaneToReg2], 1u)] = t;
+    link_append<RoutesStage>(b, kLinkLaneToReg2, t);
     continue;
   }
-  route_targets(g, b, StoreLabel<RegLabels>{S}, SearchPathLabels<RegLabels>{S}, a0, p, KB, bound, tmax,
-                (uint64_t)base + i * KB, &s_res[0][threadIdx.x], 256, TurnCtx{a1, rk1, rk0, mode, TURN, pi.w, TURN ? b.gc[p] : 0.0});
+  route_targets(g, b, StoreLabel<RegLabels>{S}, SearchPathLabels<RegLabels>{S}, a0, it.p, it.KB, it.bound, it.tmax, (uint64_t)it.base + it.i * it.KB,
+                &s_res[0][threadIdx.x], 256, TurnCtx{a1, rk1, rk0, it.mode, TURN, it.pi.w, TURN ? b.gc[it.p] : 0.0});
   }
 }
 
@@ -2770,31 +2839,24 @@ constexpr int kTier2Cap = RM_TIER2_CAP;
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_routes_reg2(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ uint32_t s_res[kMaxCand][256];
-  const uint32_t n_items = b.ctl[kCtlLaneToReg2];
-  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_items; q += gridDim.x * blockDim.x) {
-    const uint32_t t = b.rl_routes_a[q];
-    const uint32_t p = b.src_item[t];
-    const uint4 pi = b.pair_info[p];
-    const uint32_t i = t - b.src_off[p];
-    const uint32_t base = b.trans_off[p];
-    const uint32_t bound = pi.x, tmax = pi.y, KB = (pi.z >> 8) & 0xffu;
-    const int mode = (int)(pi.z >> 16);
-    const uint64_t arow = ((uint64_t)(p - 1) * kMaxCand + i) * 2;
-    const uint4 a0 = b.cand_desc[arow], a1 = b.cand_desc[arow + 1];
+  const LinkIn in = link_in<RoutesStage>(b, kLinkLaneToReg2);
+  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < in.n; q += gridDim.x * blockDim.x) {
+    const uint32_t t = in.list[q];
+    const K2Item it = k2_item(b, t);
+    const uint4 a0 = b.cand_desc[it.arow], a1 = b.cand_desc[it.arow + 1];
     RegLabelsT<kTier2Cap> S;
     unsigned long long rk1, rk0;
     // the early stop pays from bounds of a few blocks (C3's 30 s pairs); at 1 Hz bounds its
     // checks cost more than they save (C2 --ball-radius 0: 0.69 -> 1.0 ms)
-    lane_search(S, g, g.relax[mode], bound, a0, a1, rk1, rk0,
-                StopAtTargets{b.cand_desc + (uint64_t)p * kMaxCand * 2, bound >= kStopMinBoundCm ? KB : 0u, a0, 0ull, 0u});
+    lane_search(S, g, g.relax[it.mode], it.bound, a0, a1, rk1, rk0,
+                StopAtTargets{b.cand_desc + (uint64_t)it.p * kMaxCand * 2, it.bound >= kStopMinBoundCm ? it.KB : 0u, a0, 0ull, 0u});
     if (S.ovf) {
-      const uint32_t x = atomicAdd(&b.ctl[kCtlReg2ToGroup], 1u);
-      b.rl_routes_b[x] = t;
+      link_append<RoutesStage>(b, kLinkReg2ToGroup, t);
       continue;
     }
-    route_targets(g, b, StoreLabel<RegLabelsT<kTier2Cap>>{S}, SearchPathLabels<RegLabelsT<kTier2Cap>>{S}, a0, p, KB,
-                  bound, tmax, (uint64_t)base + i * KB, &s_res[0][threadIdx.x], 256,
-                  TurnCtx{a1, rk1, rk0, mode, b.route_d != nullptr, pi.w, b.route_d ? b.gc[p] : 0.0});
+    route_targets(g, b, StoreLabel<RegLabelsT<kTier2Cap>>{S}, SearchPathLabels<RegLabelsT<kTier2Cap>>{S}, a0, it.p, it.KB,
+                  it.bound, it.tmax, (uint64_t)it.base + it.i * it.KB, &s_res[0][threadIdx.x], 256,
+                  TurnCtx{a1, rk1, rk0, it.mode, b.route_d != nullptr, it.pi.w, b.route_d ? b.gc[it.p] : 0.0});
   }
 }
 
@@ -3000,7 +3062,7 @@ __device__ void path_walk_ball(const DevGraph& g, const DevBatch& b, uint64_t p,
 }
 
 // path ball tier: one lane per chosen transition whose bound fits the ball radius; the
-// others go to the search tiers (rl_routes_0 reused after K2, count ctl[kCtlPathsBallToSearch])
+// others go to the search tiers (PathsStage's kLinkBallToSearch)
 #ifndef RM_PATHS_WPE
 #define RM_PATHS_WPE 1
 #endif
@@ -3038,7 +3100,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
     if (rk0 != kKeyInf) h0 = x0;
   }
   if (!fits || h1.y == 0u || h0.y == 0u) {
-    b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsBallToSearch], 1u)] = (uint32_t)p;
+    link_append<PathsStage>(b, kLinkBallToSearch, (uint32_t)p);
     return;
   }
   const BallPathLabels lab{g.ball_ent[mode], h1, h0, rk1, rk0, g.ball_road_mask};
@@ -3051,7 +3113,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
   const unsigned long long key = route_key_vals(a0, b0, b1, lab0, lab1, &combo);
   const uint32_t lim = ball_exact_limit(bound, g.ball_radius[mode], rk1, rk0);
   if (lim != kNone && (key == kKeyInf || key_dist(key) > lim)) {   // not decided by the tables
-    b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsBallToSearch], 1u)] = (uint32_t)p;
+    link_append<PathsStage>(b, kLinkBallToSearch, (uint32_t)p);
     return;
   }
   path_walk_ball(g, b, p, lab, mode, a0, a1, b0, b1, key, combo, (int)kBallMaxKeys, r1, r0);
@@ -3064,10 +3126,10 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
   const uint64_t q0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   uint64_t p = q0;
   if (listed) {   // grid-stride over the ball tier's hand-overs
-    const uint32_t n = b.ctl[kCtlPathsBallToSearch];
-    for (uint64_t q = q0; q < n; q += (uint64_t)gridDim.x * blockDim.x) {
+    const LinkIn in = link_in<PathsStage>(b, kLinkBallToSearch);
+    for (uint64_t q = q0; q < in.n; q += (uint64_t)gridDim.x * blockDim.x) {
       RegLabels S;
-      if (!lane_path(g, b, b.rl_routes_0[q], S, kLaneCap)) b.rl_paths_a[atomicAdd(&b.ctl[kCtlPathsLaneToReg2], 1u)] = b.rl_routes_0[q];
+      if (!lane_path(g, b, in.list[q], S, kLaneCap)) link_append<PathsStage>(b, kLinkLaneToReg2, in.list[q]);
     }
     return;
   } else {
@@ -3084,23 +3146,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_LAN
     if (b.chain_start[p] || b.choice[p] < 0) return;
   }
   RegLabels S;
-  if (!lane_path(g, b, p, S, kLaneCap)) {
-    const uint32_t q = atomicAdd(&b.ctl[kCtlPathsLaneToReg2], 1u);
-    b.rl_paths_a[q] = (uint32_t)p;
-  }
+  if (!lane_path(g, b, p, S, kLaneCap)) link_append<PathsStage>(b, kLinkLaneToReg2, (uint32_t)p);
 }
 
 // path second register tier
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k_paths_reg2(DevGraph g, DevBatch b) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  const uint32_t n_items = b.ctl[kCtlPathsLaneToReg2];
-  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n_items; q += gridDim.x * blockDim.x) {
-    const uint32_t p = b.rl_paths_a[q];
+  const LinkIn in = link_in<PathsStage>(b, kLinkLaneToReg2);
+  for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < in.n; q += gridDim.x * blockDim.x) {
+    const uint32_t p = in.list[q];
     RegLabelsT<kTier2Cap> S;
-    if (!lane_path(g, b, p, S, kTier2Cap)) {
-      const uint32_t x = atomicAdd(&b.ctl[kCtlPathsReg2ToGroup], 1u);
-      b.rl_paths_b[x] = p;
-    }
+    if (!lane_path(g, b, p, S, kTier2Cap)) link_append<PathsStage>(b, kLinkReg2ToGroup, p);
   }
 }
 
@@ -3108,10 +3164,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
 // K2 wave tier: one wave per (pair, source) item that outgrew both lane tiers; the
 // source is searched alone in a hash of H (source, node) labels.  Returns false when the
 // search outgrew the hash (the caller hands the item to the next tier).
-template <int H, int W = kWave>
+template <int H, int W>
 __device__ bool routes_search_item(SearchSmem<H, false>& sm, uint4* s_src, const DevGraph& g, const DevBatch& b,
                                    uint32_t t) {
   const int lane = grp_lane<W>();
+  // (written out, not k2_item: its 32-bit row arithmetic changes the wave and global tiers' VGPR counts)
   const uint64_t p = b.src_item[t];
   const uint4 pi = b.pair_info[p];
   const uint32_t i = t - b.src_off[p];
@@ -3152,61 +3209,11 @@ __device__ bool routes_search_item(SearchSmem<H, false>& sm, uint4* s_src, const
 }
 
 // LDS tiers (round 4).  With early termination most searches end a few blocks past their targets
-// and touch tens of nodes: the group tier runs four of them per wave, 16 lanes and a kGrpH-slot
+// and touch tens of nodes: the group tier runs four of them per wave, 16 lanes and a kGrpHash-slot
 // hash each (four searches in the LDS of one); what outgrows it goes to the 512-slot wave tier
-// (10 KB, 16 waves per CU), then to the 4096-slot one (80 KB, 2 waves per CU).  Hand-over lists:
-// group tier <- rl_routes_b (ctl[kCtlReg2ToGroup]) -> rl_routes_a (ctl[kCtlGroupToWave512], free once tier 2 has run) -> 512
-// tier -> rl_routes_0 (ctl[kCtlWave512ToWave4096], free once the lane tier has run) -> 4096 tier -> rl_routes_c.
-#ifndef RM_GRP_H
-#define RM_GRP_H 256
-#endif
-#ifndef RM_GRP_PATH_H
-#define RM_GRP_PATH_H 128   // path searches are single-target: smaller (C3 radius 0: 10.3 -> 7.4 ms at 128)
-#endif
-constexpr int kGrpH = RM_GRP_H;
-constexpr int kGrpPathH = RM_GRP_PATH_H;
+// (10 KB, 16 waves per CU), then to the 4096-slot one (80 KB, 2 waves per CU): k_tier_* below.
 constexpr int kGrpW = 16;
 constexpr uint32_t kGrpGrid = 4096;   // blocks of the group tiers (grid-stride over their lists)
-// short: a small run's short hand-over chain (Matcher::run_small, round 6): the group tier takes
-// the ball tier's hand-overs (rl_routes_0, ctl[kCtlBallToSearch]) itself and the 4096-slot tier takes the group
-// tier's; the lane, second register and 512-slot tiers are not launched (three launches fewer;
-// every tier is exact, so the routes are the same)
-__global__ void __launch_bounds__(64) k_routes_grp(DevGraph g, DevBatch b, int short_chain) {
-  if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kGrpH, false> sm[kWave / kGrpW];
-  __shared__ uint4 s_src[kWave / kGrpW][2];
-  const int gi = threadIdx.x / kGrpW;
-  const uint32_t n_items = short_chain ? b.ctl[kCtlBallToSearch] : b.ctl[kCtlReg2ToGroup];
-  const uint32_t* list = short_chain ? b.rl_routes_0 : b.rl_routes_b;
-  for (uint32_t item = blockIdx.x * (kWave / kGrpW) + gi; item < n_items; item += gridDim.x * (kWave / kGrpW)) {
-    const uint32_t t = list[item];
-    if (!routes_search_item<kGrpH, kGrpW>(sm[gi], s_src[gi], g, b, t) && grp_lane<kGrpW>() == 0)
-      b.rl_routes_a[atomicAdd(&b.ctl[kCtlGroupToWave512], 1u)] = t;
-  }
-}
-
-__global__ void __launch_bounds__(64) k_routes_wave_s(DevGraph g, DevBatch b) {
-  if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kMidH, false> sm;
-  __shared__ uint4 s_src[2];
-  const uint32_t n_items = b.ctl[kCtlGroupToWave512];
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t t = b.rl_routes_a[item];
-    if (!routes_search_item<kMidH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[kCtlWave512ToWave4096], 1u)] = t;
-  }
-}
-
-__global__ void __launch_bounds__(64) k_routes_wave(DevGraph g, DevBatch b, int short_chain) {
-  if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kBigH, false> sm;
-  __shared__ uint4 s_src[2];
-  const uint32_t n_items = short_chain ? b.ctl[kCtlGroupToWave512] : b.ctl[kCtlWave512ToWave4096];   // (short: the group tier's hand-overs)
-  const uint32_t* list = short_chain ? b.rl_routes_a : b.rl_routes_0;
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t t = list[item];
-    if (!routes_search_item<kBigH>(sm, s_src, g, b, t) && threadIdx.x == 0) b.rl_routes_c[atomicAdd(&b.ctl[kCtlWaveToGlobal], 1u)] = t;
-  }
-}
 
 // Global-memory tier (routes and paths): searches that outgrew the 4096-slot LDS hash (route
 // bounds of many kilometres: sparse sampling with a large breakage_distance) run here with a
@@ -3214,19 +3221,7 @@ __global__ void __launch_bounds__(64) k_routes_wave(DevGraph g, DevBatch b, int 
 // only (trace_err), never the batch.
 constexpr int kGlobalH = 1 << 17;
 constexpr int kGlobalGrid = 32;
-using GlobalRouteSmem = SearchSmem<kGlobalH, false>;
-using GlobalPathSmem = SearchSmem<kGlobalH, true>;
-
-__global__ void __launch_bounds__(64) k_routes_global(DevGraph g, DevBatch b, GlobalPathSmem* scratch) {
-  if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ uint4 s_src[2];
-  GlobalRouteSmem& sm = *reinterpret_cast<GlobalRouteSmem*>(scratch + blockIdx.x);
-  const uint32_t n_items = b.ctl[kCtlWaveToGlobal];
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t t = b.rl_routes_c[item];
-    if (!routes_search_item<kGlobalH>(sm, s_src, g, b, t) && threadIdx.x == 0) trace_fail(b, b.src_item[t], kErrSearchOverflow);
-  }
-}
+using GlobalPathSmem = SearchSmem<kGlobalH, true>;   // (the scratch holds kGlobalGrid of the larger, the path stage's)
 
 // ------------------------------------------------------------------------------------------
 // K3 k_viterbi: 16 lanes per trace, 4 traces per wave; lane j owns candidate j of the
@@ -4087,7 +4082,7 @@ void launch_viterbi(uint32_t T, hipStream_t st, const DevBatch& v) {
 // k_paths wave tiers: one wave per chosen transition whose search outgrew the lane tier;
 // re-run the search for (i*, j*), compute canonical predecessors and write the
 // directed-edge path.  Returns false when the search outgrew the hash (next tier).
-template <int H, int W = kWave>
+template <int H, int W>
 __device__ bool paths_search_item(SearchSmem<H, true>& sm, uint4* s_src, const DevGraph& g, const DevBatch& b,
                                   uint64_t p) {
   const int lane = grp_lane<W>();
@@ -4177,54 +4172,46 @@ __device__ bool paths_search_item(SearchSmem<H, true>& sm, uint4* s_src, const D
   return true;
 }
 
-// path tiers, as the route tiers: group tier <- rl_paths_b (ctl[kCtlPathsReg2ToGroup]) -> rl_paths_a (ctl[kCtlPathsGroupToWave512]) ->
-// 512 tier -> rl_routes_0 (ctl[kCtlPathsWave512ToWave4096], free once the path lane tier has run) -> 4096 tier -> rl_paths_c
-// (short_chain: the path ball tier's hand-overs, rl_routes_0 / ctl[kCtlPathsBallToSearch], as k_routes_grp's)
-__global__ void __launch_bounds__(64) k_paths_grp(DevGraph g, DevBatch b, int short_chain) {
+// The search tiers' kernels, for either stage St: each takes link `in` in a grid-stride loop and appends what outgrows
+// its hash to its own link.  A small run's short chain (round 6) launches the group tier on kLinkBallToSearch and the
+// 4096-slot tier on kLinkGroupToWave512, and no lane, reg2 or 512-slot tier (every tier is exact: the same results).
+template <class St>
+__global__ void __launch_bounds__(64) k_tier_grp(DevGraph g, DevBatch b, int in) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kGrpPathH, true> sm[kWave / kGrpW];
+  __shared__ SearchSmem<St::kGrpHash, St::kPath> sm[kWave / kGrpW];
   __shared__ uint4 s_src[kWave / kGrpW][2];
   const int gi = threadIdx.x / kGrpW;
-  const uint32_t n_items = short_chain ? b.ctl[kCtlPathsBallToSearch] : b.ctl[kCtlPathsReg2ToGroup];
-  const uint32_t* list = short_chain ? b.rl_routes_0 : b.rl_paths_b;
-  for (uint32_t item = blockIdx.x * (kWave / kGrpW) + gi; item < n_items; item += gridDim.x * (kWave / kGrpW)) {
-    const uint32_t p = list[item];
-    if (!paths_search_item<kGrpPathH, kGrpW>(sm[gi], s_src[gi], g, b, p) && grp_lane<kGrpW>() == 0)
-      b.rl_paths_a[atomicAdd(&b.ctl[kCtlPathsGroupToWave512], 1u)] = p;
+  const LinkIn li = link_in<St>(b, in);
+  for (uint32_t item = blockIdx.x * (kWave / kGrpW) + gi; item < li.n; item += gridDim.x * (kWave / kGrpW)) {
+    const uint32_t t = li.list[item];
+    if (!St::template item<St::kGrpHash, kGrpW>(sm[gi], s_src[gi], g, b, t) && grp_lane<kGrpW>() == 0)
+      link_append<St>(b, kLinkGroupToWave512, t);
   }
 }
 
-__global__ void __launch_bounds__(64) k_paths_wave_s(DevGraph g, DevBatch b) {
+template <class St, int H>
+__global__ void __launch_bounds__(64) k_tier_wave(DevGraph g, DevBatch b, int in) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kMidH, true> sm;
+  __shared__ SearchSmem<H, St::kPath> sm;
   __shared__ uint4 s_src[2];
-  const uint32_t n_items = b.ctl[kCtlPathsGroupToWave512];
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t p = b.rl_paths_a[item];
-    if (!paths_search_item<kMidH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_routes_0[atomicAdd(&b.ctl[kCtlPathsWave512ToWave4096], 1u)] = p;
+  const LinkIn li = link_in<St>(b, in);
+  for (uint32_t item = blockIdx.x; item < li.n; item += gridDim.x) {
+    const uint32_t t = li.list[item];
+    if (!St::template item<H, kWave>(sm, s_src, g, b, t) && threadIdx.x == 0)
+      link_append<St>(b, H == kMidH ? kLinkWave512ToWave4096 : kLinkWaveToGlobal, t);
   }
 }
 
-__global__ void __launch_bounds__(64) k_paths_wave(DevGraph g, DevBatch b, int short_chain) {
-  if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
-  __shared__ SearchSmem<kBigH, true> sm;
-  __shared__ uint4 s_src[2];
-  const uint32_t n_items = short_chain ? b.ctl[kCtlPathsGroupToWave512] : b.ctl[kCtlPathsWave512ToWave4096];
-  const uint32_t* list = short_chain ? b.rl_paths_a : b.rl_routes_0;
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t p = list[item];
-    if (!paths_search_item<kBigH>(sm, s_src, g, b, p) && threadIdx.x == 0) b.rl_paths_c[atomicAdd(&b.ctl[kCtlPathsWaveToGlobal], 1u)] = p;
-  }
-}
-
-__global__ void __launch_bounds__(64) k_paths_global(DevGraph g, DevBatch b, GlobalPathSmem* scratch) {
+template <class St>
+__global__ void __launch_bounds__(64) k_tier_global(DevGraph g, DevBatch b, GlobalPathSmem* scratch) {
   if (steady_abort(b)) return;   // a steady run whose pools the batch outgrew (Matcher::run_steady)
   __shared__ uint4 s_src[2];
-  GlobalPathSmem& sm = scratch[blockIdx.x];
-  const uint32_t n_items = b.ctl[kCtlPathsWaveToGlobal];
-  for (uint32_t item = blockIdx.x; item < n_items; item += gridDim.x) {
-    const uint32_t p = b.rl_paths_c[item];
-    if (!paths_search_item<kGlobalH>(sm, s_src, g, b, p) && threadIdx.x == 0) trace_fail(b, p, kErrSearchOverflow);
+  SearchSmem<kGlobalH, St::kPath>& sm = *reinterpret_cast<SearchSmem<kGlobalH, St::kPath>*>(scratch + blockIdx.x);
+  const LinkIn li = link_in<St>(b, kLinkWaveToGlobal);
+  for (uint32_t item = blockIdx.x; item < li.n; item += gridDim.x) {
+    const uint32_t t = li.list[item];
+    if (!St::template item<kGlobalH, kWave>(sm, s_src, g, b, t) && threadIdx.x == 0)
+      trace_fail(b, St::fail_slot(b, t), kErrSearchOverflow);
   }
 }
 
@@ -6036,10 +6023,16 @@ void Matcher::zero_hist(const RunParams& rp) {
 // The three ways to run a batch -- run_small, run_steady and the ordinary rest of run_device --
 // launch the same stages through Matcher::Stages (k1, routes, paths, k4) and differ in
 // this plan (and in their scans and read-backs, which stay with them: DESIGN.md §5).
-struct TierGrids {   // one stage's hand-over tiers
+// A stage's hand-over tiers (kTierLane: the lane tier over the ball tier's hand-overs): each one's
+// full grid, the link it reads and the items a block takes per pass of its grid-stride loop
+enum Tier : int { kTierLane = 0, kTierReg2, kTierGrp, kTierWave512, kTierWave4096, kTiers };
+struct TierLaunch { uint32_t full; Link in; uint32_t per_block; };
+constexpr TierLaunch kTierLaunch[kTiers] = {{(uint32_t)kListedGrid, kLinkBallToSearch, 256}, {kReg2Grid, kLinkLaneToReg2, 256},
+                                            {kGrpGrid, kLinkReg2ToGroup, kWave / kGrpW}, {kMidGrid, kLinkGroupToWave512, 1},
+                                            {1024, kLinkWave512ToWave4096, 1}};
+struct TierGrids {
   bool launch;       // false: none is launched (a steady run whose last two runs handed nothing over)
-  uint32_t listed;   // the lane tier over the ball tier's hand-overs (at most the stage's lane grid)
-  uint32_t reg2, grp, wave_s, wave;
+  uint32_t grid[kTiers];   // (kTierLane: at most the stage's lane grid)
 };
 struct LaunchPlan {
   bool k1_wave_all;        // K1 takes every state a wave each: no lane tier
@@ -6057,8 +6050,15 @@ struct LaunchPlan {
 
 // the hand-over tiers' grids of a run that does not know the lists' lengths
 static TierGrids tier_grids(uint64_t P) {
-  return {true, (uint32_t)kListedGrid, tier_grid(P, kReg2Grid), tier_grid(P, kGrpGrid), tier_grid(P, kMidGrid),
-          tier_grid(P, 1024)};
+  TierGrids tg{true, {}};
+  for (int k = 0; k < kTiers; ++k) tg.grid[k] = k == kTierLane ? kTierLaunch[k].full : tier_grid(P, kTierLaunch[k].full);
+  return tg;
+}
+
+template <class St> static uint32_t handed_over(const uint32_t* ctl) {   // a stage's hand-over words or-ed, the global tier's aside
+  uint32_t any = 0;
+  for (int l = kLinkBallToSearch; l < kLinkWaveToGlobal; ++l) any |= ctl[St::link(l).word];
+  return any;
 }
 
 bool Matcher::route_balls(const DevGraph& g) const { return (mode_mask_ & g.ball_mask) != 0u; }
@@ -6071,6 +6071,7 @@ struct Matcher::Stages {
   void k1(const DevBatch& v) const;
   void routes(const DevBatch& v) const;
   void paths(const DevBatch& v) const;
+  template <class St> void search_tiers(const DevBatch& v, const TierGrids& tg) const;
   void k4(const RunParams& rp, const DevBatch& v, uint32_t total) const;
 };
 
@@ -6109,6 +6110,7 @@ void Matcher::Stages::routes(const DevBatch& v) const {
   const bool chain = tg.launch && !pl.short_chain;   // every tier
   const uint32_t item_grid = (uint32_t)((pl.src_cover + kK2Items - 1) / kK2Items);
   const uint32_t lane_grid = (uint32_t)((pl.src_cover + 255) / 256);
+  const auto lane = v.route_d ? k_routes_lane<true> : k_routes_lane<false>;
   m.tic(kKRoutes);
   if (pl.n_src != kNone) hipLaunchKernelGGL(k_src_items, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, v);
   if (pl.src_cover && balls) {
@@ -6123,24 +6125,29 @@ void Matcher::Stages::routes(const DevBatch& v) const {
     } else {
       hipLaunchKernelGGL(k_routes_ball2<false>, dim3(item_grid), dim3(kK2Threads), 0, st, g, vk, pl.n_src);
     }
-    if (chain) {
-      const uint32_t lg = std::min(lane_grid, tg.listed);
-      if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-      else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lg), dim3(256), 0, st, g, v, 0u, 1);
-    }
+    if (chain) hipLaunchKernelGGL(lane, dim3(std::min(lane_grid, tg.grid[kTierLane])), dim3(256), 0, st, g, v, 0u, 1);
   } else if (pl.src_cover) {
-    if (v.route_d) hipLaunchKernelGGL(k_routes_lane<true>, dim3(lane_grid), dim3(256), 0, st, g, v, pl.n_src, 0);
-    else hipLaunchKernelGGL(k_routes_lane<false>, dim3(lane_grid), dim3(256), 0, st, g, v, pl.n_src, 0);
+    hipLaunchKernelGGL(lane, dim3(lane_grid), dim3(256), 0, st, g, v, pl.n_src, 0);
   }
-  const int sc = pl.short_chain ? 1 : 0;
-  if (chain) hipLaunchKernelGGL(k_routes_reg2, dim3(tg.reg2), dim3(256), 0, st, g, v);
-  if (tg.launch) hipLaunchKernelGGL(k_routes_grp, dim3(tg.grp), dim3(64), 0, st, g, v, sc);
-  if (chain) hipLaunchKernelGGL(k_routes_wave_s, dim3(tg.wave_s), dim3(64), 0, st, g, v);
-  if (tg.launch) hipLaunchKernelGGL(k_routes_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
+  search_tiers<RoutesStage>(v, tg);
+  m.toc(kKRoutes);
+}
+
+// the tiers after a stage's lane tier: reg2, group, 512- and 4096-slot waves, global memory
+template <class St>
+void Matcher::Stages::search_tiers(const DevBatch& v, const TierGrids& tg) const {
+  hipStream_t st = m.stream_;
+  const bool chain = tg.launch && !pl.short_chain;   // every tier
+  // the short chain: the group tier takes the ball tier's hand-overs, the 4096-slot tier the group tier's
+  const int grp_in = pl.short_chain ? kLinkBallToSearch : kLinkReg2ToGroup, mid_in = kLinkGroupToWave512;
+  const int big_in = pl.short_chain ? kLinkGroupToWave512 : kLinkWave512ToWave4096;
+  if (chain) hipLaunchKernelGGL(St::kPath ? k_paths_reg2 : k_routes_reg2, dim3(tg.grid[kTierReg2]), dim3(256), 0, st, g, v);
+  if (tg.launch) hipLaunchKernelGGL(k_tier_grp<St>, dim3(tg.grid[kTierGrp]), dim3(64), 0, st, g, v, grp_in);
+  if (chain) hipLaunchKernelGGL((k_tier_wave<St, kMidH>), dim3(tg.grid[kTierWave512]), dim3(64), 0, st, g, v, mid_in);
+  if (tg.launch) hipLaunchKernelGGL((k_tier_wave<St, kBigH>), dim3(tg.grid[kTierWave4096]), dim3(64), 0, st, g, v, big_in);
   // the global tier runs in line once its scratch exists (ensure_global_search)
   if (m.ws_.gsearch)
-    hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch.get());
-  m.toc(kKRoutes);
+    hipLaunchKernelGGL(k_tier_global<St>, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch.get());
 }
 
 // the path stage, as the routes stage
@@ -6152,17 +6159,11 @@ void Matcher::Stages::paths(const DevBatch& v) const {
   m.tic(kKPaths);
   if (m.route_balls(g)) {
     hipLaunchKernelGGL(k_paths_ball, dim3(count_grid), dim3(256), 0, st, g, v);
-    if (chain) hipLaunchKernelGGL(k_paths_lane, dim3(std::min(count_grid, tg.listed)), dim3(256), 0, st, g, v, 1);
+    if (chain) hipLaunchKernelGGL(k_paths_lane, dim3(std::min(count_grid, tg.grid[kTierLane])), dim3(256), 0, st, g, v, 1);
   } else {
     hipLaunchKernelGGL(k_paths_lane, dim3(count_grid), dim3(256), 0, st, g, v, 0);
   }
-  const int sc = pl.short_chain ? 1 : 0;
-  if (chain) hipLaunchKernelGGL(k_paths_reg2, dim3(tg.reg2), dim3(256), 0, st, g, v);
-  if (tg.launch) hipLaunchKernelGGL(k_paths_grp, dim3(tg.grp), dim3(64), 0, st, g, v, sc);
-  if (chain) hipLaunchKernelGGL(k_paths_wave_s, dim3(tg.wave_s), dim3(64), 0, st, g, v);
-  if (tg.launch) hipLaunchKernelGGL(k_paths_wave, dim3(tg.wave), dim3(64), 0, st, g, v, sc);
-  if (m.ws_.gsearch)
-    hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)m.ws_.gsearch.get());
+  search_tiers<PathsStage>(v, tg);
   m.toc(kKPaths);
 }
 
@@ -6327,12 +6328,13 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   pl.n_src = kNone;
   pl.src_cover = src_cover;
   pl.short_chain = false;
-  pl.routes = {!skip_routes, sgrid(kListedGrid, kCtlBallToSearch, 256), sgrid(kReg2Grid, kCtlLaneToReg2, 256),
-               sgrid(kGrpGrid, kCtlReg2ToGroup, kWave / kGrpW), sgrid(kMidGrid, kCtlGroupToWave512, 1),
-               sgrid(1024, kCtlWave512ToWave4096, 1)};
-  pl.paths = {!skip_paths, sgrid(kListedGrid, kCtlPathsBallToSearch, 256), sgrid(kReg2Grid, kCtlPathsLaneToReg2, 256),
-              sgrid(kGrpGrid, kCtlPathsReg2ToGroup, kWave / kGrpW), sgrid(kMidGrid, kCtlPathsGroupToWave512, 1),
-              sgrid(1024, kCtlPathsWave512ToWave4096, 1)};
+  const auto stage_grids = [&](bool launch, auto stage) {
+    TierGrids tg{launch, {}};
+    for (const TierLaunch& t : kTierLaunch) tg.grid[&t - kTierLaunch] = sgrid(t.full, decltype(stage)::link(t.in).word, t.per_block);
+    return tg;
+  };
+  pl.routes = stage_grids(!skip_routes, RoutesStage{});
+  pl.paths = stage_grids(!skip_paths, PathsStage{});
 
   tic(kKStates);
   hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
@@ -6464,6 +6466,7 @@ void Matcher::run_device(const RunParams& rp) {
   const auto zero_ctl = [&](std::initializer_list<CtlWord> words) {
     for (CtlWord c : words) RM_HIP(hipMemsetAsync(w.ctl + c, 0, sizeof(uint32_t), st));
   };
+  const auto pw = [](Link l) { return PathsStage::link(l).word; };   // the path stage's word of link l
   const auto clear_path_overflow = [&] {
     uint32_t flags = hctl_[kCtlErr] & ~kErrPathOverflow;
     RM_HIP(hipMemcpyAsync(w.ctl + kCtlErr, &flags, sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -6482,7 +6485,7 @@ void Matcher::run_device(const RunParams& rp) {
   };
   for (int attempt = 0;; ++attempt) {
     if (attempt)   // the first attempt starts from the zeroed control words
-      zero_ctl({kCtlPathsBallToSearch, kCtlPathsWaveToGlobal, kCtlPathsGroupToWave512, kCtlPathsWave512ToWave4096});
+      zero_ctl({pw(kLinkBallToSearch), pw(kLinkWaveToGlobal), pw(kLinkGroupToWave512), pw(kLinkWave512ToWave4096)});
     s.paths(v);
     tic(kKSegments);
     scan_records();
@@ -6492,17 +6495,17 @@ void Matcher::run_device(const RunParams& rp) {
       // routes outgrew the LDS wave tier: run them in the global tier, then K3 and paths again
       ensure_global_search();
       routes_global_done = true;
-      hipLaunchKernelGGL(k_routes_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
+      hipLaunchKernelGGL(k_tier_global<RoutesStage>, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
       launch_viterbi(T, st, v);
       RM_HIP(hipMemsetAsync(w.path_cnt, 0, P * sizeof(uint32_t), st));
-      zero_ctl({kCtlPathUsed, kCtlPathsLaneToReg2, kCtlPathsReg2ToGroup});
+      zero_ctl({kCtlPathUsed, pw(kLinkLaneToReg2), pw(kLinkReg2ToGroup)});
       clear_path_overflow();
       continue;
     }
     if (!w.gsearch && hctl_[kCtlPathsWaveToGlobal]) {
       // chosen transitions whose path search outgrew the LDS wave tier
       ensure_global_search();
-      hipLaunchKernelGGL(k_paths_global, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
+      hipLaunchKernelGGL(k_tier_global<PathsStage>, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
       scan_records();
       read_records();
     }
@@ -6510,7 +6513,7 @@ void Matcher::run_device(const RunParams& rp) {
     if (attempt > 3) throw BatchTooLarge("path pool overflow persists");
     ensure_path((uint64_t)hctl_[kCtlPathUsed]);
     v.path_pool = w.path_pool; v.path_cap = w.cap_path;
-    zero_ctl({kCtlPathUsed, kCtlPathsLaneToReg2, kCtlPathsReg2ToGroup});
+    zero_ctl({kCtlPathUsed, pw(kLinkLaneToReg2), pw(kLinkReg2ToGroup)});
     clear_path_overflow();
   }
   const uint64_t seg_total = tot[2];
@@ -6651,12 +6654,8 @@ void Matcher::keep_ctl() {
   count_clean(steady_ctl_);
 }
 void Matcher::count_clean(const uint32_t* c) {
-  const uint32_t routes = c[kCtlBallToSearch] | c[kCtlLaneToReg2] | c[kCtlReg2ToGroup] | c[kCtlGroupToWave512] |
-                          c[kCtlWave512ToWave4096];
-  const uint32_t paths = c[kCtlPathsBallToSearch] | c[kCtlPathsLaneToReg2] | c[kCtlPathsReg2ToGroup] |
-                         c[kCtlPathsGroupToWave512] | c[kCtlPathsWave512ToWave4096];
-  clean_routes_ = routes ? 0u : std::min(clean_routes_ + 1u, 2u);
-  clean_paths_ = paths ? 0u : std::min(clean_paths_ + 1u, 2u);
+  clean_routes_ = handed_over<RoutesStage>(c) ? 0u : std::min(clean_routes_ + 1u, 2u);
+  clean_paths_ = handed_over<PathsStage>(c) ? 0u : std::min(clean_paths_ + 1u, 2u);
 }
 
 void Matcher::run_stats(uint64_t* out4) const {

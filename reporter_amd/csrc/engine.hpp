@@ -120,18 +120,18 @@ extern const char* const kKernelNames[kNumKernels];
 constexpr int kCtlWords = 16;
 // The control words (Workspace::ctl, zeroed by k_states; Matcher::ctl_words returns them in this
 // order).  A hand-over count is named after the tier that writes it, as BatchMatcher.route_tiers():
-// it is the length of the list the next tier reads.
+// it is the length of the list the next tier reads (which list: engine.hip, RoutesStage / PathsStage).
 enum CtlWord : int {
   kCtlPathUsed = 0,             // path pool used
-  kCtlBallToSearch = 1,         // K2 ball tier -> search tiers (rl_routes_0)
+  kCtlBallToSearch = 1,         // K2 ball tier -> search tiers
   kCtlErr = 2,                  // error flags (kErr*)
-  kCtlLaneToReg2 = 3,           // routes: lane tier -> reg2 (list A)
+  kCtlLaneToReg2 = 3,           // routes: lane tier -> reg2
   kCtlPathsLaneToReg2 = 4,      // paths: the same
-  kCtlReg2ToGroup = 5,          // routes: reg2 -> group tier (list B)
+  kCtlReg2ToGroup = 5,          // routes: reg2 -> group tier
   kCtlPathsReg2ToGroup = 6,     // paths: the same
   kCtlK1LaneToWave = 7,         // K1 lane tier -> wave tier
-  kCtlPathsBallToSearch = 8,    // path ball tier -> search tiers (rl_routes_0 again)
-  kCtlWaveToGlobal = 9,         // routes: 4096-slot wave tier -> global-memory tier (list C)
+  kCtlPathsBallToSearch = 8,    // path ball tier -> search tiers
+  kCtlWaveToGlobal = 9,         // routes: 4096-slot wave tier -> global-memory tier
   kCtlPathsWaveToGlobal = 10,   // paths: the same
   kCtlGroupToWave512 = 11,      // routes: group tier -> 512-slot wave tier
   kCtlPathsGroupToWave512 = 12, // paths: the same

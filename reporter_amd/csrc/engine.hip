@@ -1908,7 +1908,7 @@ __device__ __forceinline__ void lane_search(L& S, const DevGraph& g, const uint4
 // routes from source a0 to the KB targets of pair slot p; results staged in LDS
 // (res[j * stride]) and stored after the last load (a store before a load-use costs a
 // full round trip: gfx9 loads and stores share vmcnt)
-// labels for the path walk: label of node x, which is the `side` endpoint (0: node0,
+// labels for the canonical walk: label of node x, which is the `side` endpoint (0: node0,
 // 1: node1) of `road` (the ball tier probes by road; the search tiers ignore both)
 template <class L>
 struct SearchPathLabels {
@@ -1916,53 +1916,89 @@ struct SearchPathLabels {
   __device__ unsigned long long operator()(uint32_t x, uint32_t, uint32_t) const { return s.label(x); }
 };
 
-// Turn weight (rule 3b) of the route of combination `combo` from source (a0, a1) to target
-// (b0, b1) in a search with labels `lab` (exit root keys rk1 / rk0): the canonical path walked back
-// from the entry node as the path stage walks it, one turn per node, the exit node's arriving edge
-// being the source road in the exit's direction.  0 for the direct combinations; ok false when a
-// predecessor is missing (not reached for a valid route).
+// ---- The canonical walk.  A route's canonical path is walked back from the target's entry node
+// to one of the source's two exits; at each node it takes the canonical predecessor.  The path
+// stage writes its edges (canonical_path) and the routes stage sums its turn weights
+// (canonical_turns) through one cursor each, so both walk the same path by construction.
+//
+// Canonical predecessor of node x (label lx): the smallest-id usable in-edge (u -> x) with
+// label(u) + key(edge) == lx, in ascending edge id: its record `rec` (edge, u, road|rev, length)
+// and u's label `plu`.  Each in-edge is one self-contained record: one round trip before its
+// label probe instead of three dependent loads (in_edge -> edges -> edge_src).  Probing several
+// in-edges at once was slower: most nodes find the tight edge first, and the extra probes and
+// registers cost more than the overlap (C2 paths 0.32 -> 0.39 ms).
 template <class PL>
-__device__ __forceinline__ uint32_t search_turn_walk(const DevGraph& g, const PL& lab, int mode, const uint4& a0,
-                                                     const uint4& a1, const uint4& b0, const uint4& b1,
-                                                     unsigned long long rk1, unsigned long long rk0, int combo, bool& ok) {
-  ok = true;
-  if (combo < 2) return 0u;
-  const uint32_t acc = mode_access(mode);
-  const uint32_t side = combo == 2 ? 0u : 1u;
-  uint32_t hs = head_start(g.road_head[b0.x], side);   // the entry edge leaves its node with this heading
-  uint32_t x = side ? b1.y : b1.x;
-  unsigned long long lx = lab(x, b0.x, side);
-  const uint32_t hwa = g.road_head[a0.x];
-  uint32_t U = 0;
-  for (uint32_t guard = 0; guard < (1u << 20); ++guard) {
-    if (lx == kKeyInf) break;
-    if (x == a1.y && lx == rk1) return U + g.turn_w[turn_degree(head_back(hwa, 0u), hs)];   // exit forward: node1
-    if (x == a1.x && lx == rk0) return U + g.turn_w[turn_degree(head_back(hwa, 1u), hs)];   // exit reverse: node0
-    bool found = false;
-    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-    unsigned long long plu = kKeyInf;
-    for (uint32_t q = g.in_off[x], q1 = g.in_off[x + 1]; q < q1; ++q) {
-      const uint4 r = g.in_rec[q];
-      const uint32_t inf = g.in_info[q];
-      if (!edge_ok(inf, acc)) continue;
-      const unsigned long long lu = lab(r.y, r.z >> 1, r.z & 1u);
-      if (lu != kKeyInf && lu + make_key(r.w, time_ms_dev(r.w, mode_speed_dkph(mode, inf & 0xffffu))) == lx) {
-        rec = r; plu = lu; found = true;
-        break;
-      }
+__device__ __forceinline__ bool find_pred(const DevGraph& g, const PL& lab, uint32_t acc, int mode, uint32_t x,
+                                          unsigned long long lx, uint4& rec, unsigned long long& plu) {
+  for (uint32_t q = g.in_off[x], q1 = g.in_off[x + 1]; q < q1; ++q) {
+    const uint4 r = g.in_rec[q];
+    const uint32_t inf = g.in_info[q];
+    if (!edge_ok(inf, acc)) continue;
+    // r.y is the edge's start: node0 of its road when the edge runs forward
+    const unsigned long long lu = lab(r.y, r.z >> 1, r.z & 1u);
+    if (lu != kKeyInf && lu + make_key(r.w, time_ms_dev(r.w, mode_speed_dkph(mode, inf & 0xffffu))) == lx) {
+      rec = r;
+      plu = lu;
+      return true;
     }
-    if (!found) break;
+  }
+  return false;
+}
+
+// A cursor is a position on the walk: node x with label lx.  start() puts it on the entry node,
+// the `side` endpoint of `road`; step() moves it to the canonical predecessor and gives the
+// in-edge taken, false when there is none (not reached for a valid route).
+// The search tiers' cursor, over any path-label functor (SearchPathLabels, HashPathLabel).
+template <class PL>
+struct SearchCursor {
+  const PL lab;
+  uint32_t x;
+  unsigned long long lx;
+  __device__ __forceinline__ void start(uint32_t node, uint32_t road, uint32_t side) {
+    x = node;
+    lx = lab(node, road, side);
+  }
+  __device__ __forceinline__ bool step(const DevGraph& g, uint32_t acc, int mode, uint4& rec) {
+    unsigned long long plu = kKeyInf;
+    if (!find_pred(g, lab, acc, mode, x, lx, rec, plu)) return false;
+    x = rec.y;
+    lx = plu;
+    return true;
+  }
+};
+
+// Turn weight (rule 3b) of a route that enters the target road `rb` at its `side` endpoint, node
+// `entry` (combinations 2 and 3: the direct ones have no turns and are the caller's), from the
+// source on the road with heading word `hwa`, exit nodes n1a / n0a and exit root keys rk1 / rk0:
+// one turn per node of the canonical path, the exit node's arriving edge being the source road in
+// the exit's direction.  ok false when a predecessor is missing or the walk outruns `limit` steps
+// (not reached for a valid route).
+template <class Cursor>
+__device__ __forceinline__ uint32_t canonical_turns(const DevGraph& g, Cursor& c, int mode, uint32_t hwa, uint32_t n1a,
+                                                    uint32_t n0a, unsigned long long rk1, unsigned long long rk0,
+                                                    uint32_t rb, uint32_t entry, uint32_t side, uint32_t limit, bool& ok) {
+  ok = true;
+  const uint32_t acc = mode_access(mode);
+  uint32_t hs = head_start(g.road_head[rb], side);   // the entry edge leaves its node with this heading
+  c.start(entry, rb, side);
+  uint32_t U = 0;
+  for (uint32_t guard = 0; guard < limit; ++guard) {
+    if (c.lx == kKeyInf) break;
+    if (c.x == n1a && c.lx == rk1) return U + g.turn_w[turn_degree(head_back(hwa, 0u), hs)];   // exit forward: node1
+    if (c.x == n0a && c.lx == rk0) return U + g.turn_w[turn_degree(head_back(hwa, 1u), hs)];   // exit reverse: node0
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    if (!c.step(g, acc, mode, rec)) break;
     const uint32_t hw = g.road_head[rec.z >> 1], rev = rec.z & 1u;
     U += g.turn_w[turn_degree(head_back(hw, rev), hs)];
     hs = head_start(hw, rev);
-    x = rec.y;
-    lx = plu;
   }
   ok = false;
   return 0u;
 }
+// iterations of the search tiers' turn walk (far beyond any route: a guard against a broken label store)
+constexpr uint32_t kSearchTurnSteps = 1u << 20;
 
-// the turn weights of a search's routes (rule 3b): what search_turn_walk needs besides the labels
+// the turn weights of a search's routes (rule 3b): what canonical_turns needs besides the labels
 struct TurnCtx {
   uint4 a1;                      // the source's second descriptor word (its road's endpoints)
   unsigned long long rk1, rk0;   // exit root keys
@@ -1994,9 +2030,12 @@ __device__ __forceinline__ void route_targets(const DevGraph& g, const DevBatch&
       res[((j0 + x) & (kMaxCand - 1)) * stride] = r;
       if (tc.on && j0 + x < KB) {   // a batch with turn costs (rare in a search tier): stored straight away
         bool ok = true;
-        const uint32_t u = (r == kRouteInvalid || !tc.factor)
-                               ? 0u
-                               : search_turn_walk(g, plab, tc.mode, a0, tc.a1, t0[x], t1[x], tc.rk1, tc.rk0, combo, ok);
+        uint32_t u = 0u;
+        if (r != kRouteInvalid && tc.factor && combo >= 2) {
+          SearchCursor<PL> c{plab};
+          u = canonical_turns(g, c, tc.mode, g.road_head[a0.x], tc.a1.y, tc.a1.x, tc.rk1, tc.rk0, t0[x].x,
+                              combo == 2 ? t1[x].x : t1[x].y, combo == 2 ? 0u : 1u, kSearchTurnSteps, ok);
+        }
         if (!ok) trace_fail(b, p, kErrRounds);
         b.route_d[ob + j0 + x] = route_term(r, u, tc.factor, tc.gc);
       }
@@ -2195,78 +2234,60 @@ struct BallPathLabels {
   }
 };
 
-// One step of the ball-tier walk back from node x (label lx, rows r1/r0 of a road with x at
-// `side`): x's canonical predecessor in the two-exit search.  Where exactly one exit gives x
-// its label, the tight in-edges of the two-exit search are that exit's own and the canonical
-// one is the predecessor stored in its row; on a tie between the exits they are the union of
-// both, and the canonical one the smaller stored index (in_rec is in edge-id order).  Only
-// when that index was not stored (7 or more in-edges before it) are the in-edges scanned.
-// Returns false when no predecessor exists (not reached for a valid route).
-__device__ __forceinline__ bool ball_pred_step(const DevGraph& g, const BallPathLabels& lab, uint32_t acc, int mode,
-                                               uint32_t x, unsigned long long lx, const uint4& r1, const uint4& r0,
-                                               uint32_t side, uint4& rec, unsigned long long& plu) {
-  const uint32_t q0 = g.in_off[x];
-  const unsigned long long k1 = side ? row_key1(r1) : row_key0(r1), k0 = side ? row_key1(r0) : row_key0(r0);
-  uint32_t idx = kBallPredNone;
-  if (lab.rk1 != kKeyInf && k1 != kKeyInf && lab.rk1 + k1 == lx) idx = min(idx, ball_pred(r1.x, side, lab.rm));
-  if (lab.rk0 != kKeyInf && k0 != kKeyInf && lab.rk0 + k0 == lx) idx = min(idx, ball_pred(r0.x, side, lab.rm));
-  if (idx < kBallPredNone) {
-    rec = g.in_rec[q0 + idx];
-    plu = kKeyInf;   // the caller reads the predecessor's label from its rows
+// The canonical walk's cursor over the route tables (SearchCursor's interface): the two-exit
+// search's labels come from both exits' rows r1 / r0 of a road that has x at `side`, one probe
+// pair per walked node instead of one per examined in-edge.  It starts on the target road's
+// rows, which the caller has probed for the route key, and ignores start()'s road.
+struct TableCursor {
+  const BallPathLabels& lab;
+  const uint4 &r1_0, &r0_0;   // the target road's rows
+  uint4 r1, r0;
+  uint32_t side, x;
+  unsigned long long lx;
+  __device__ __forceinline__ unsigned long long label() const {
+    return side ? ball_label(lab.rk1, row_key1(r1), lab.rk0, row_key1(r0))
+                : ball_label(lab.rk1, row_key0(r1), lab.rk0, row_key0(r0));
+  }
+  __device__ __forceinline__ void start(uint32_t node, uint32_t, uint32_t side_) {
+    x = node;
+    side = side_;
+    r1 = r1_0;
+    r0 = r0_0;
+    lx = label();
+  }
+  // Where exactly one exit gives x its label, the tight in-edges of the two-exit search are that
+  // exit's own and the canonical one is the predecessor stored in its row; on a tie between the
+  // exits they are the union of both, and the canonical one the smaller stored index (in_rec is
+  // in edge-id order).  Only when that index was not stored (7 or more in-edges before it) are
+  // the in-edges scanned.
+  __device__ __forceinline__ bool step(const DevGraph& g, uint32_t acc, int mode, uint4& rec) {
+    const unsigned long long k1 = side ? row_key1(r1) : row_key0(r1), k0 = side ? row_key1(r0) : row_key0(r0);
+    uint32_t idx = kBallPredNone;
+    if (lab.rk1 != kKeyInf && k1 != kKeyInf && lab.rk1 + k1 == lx) idx = min(idx, ball_pred(r1.x, side, lab.rm));
+    if (lab.rk0 != kKeyInf && k0 != kKeyInf && lab.rk0 + k0 == lx) idx = min(idx, ball_pred(r0.x, side, lab.rm));
+    if (idx < kBallPredNone) {
+      rec = g.in_rec[g.in_off[x] + idx];
+    } else {
+      unsigned long long plu;   // (not used: the predecessor's label comes from its rows, as after a stored index)
+      if (!find_pred(g, lab, acc, mode, x, lx, rec, plu)) return false;
+    }
+    x = rec.y;
+    side = rec.z & 1u;   // the edge's start: node0 of its road when it runs forward
+    lab.rows(rec.z >> 1, r1, r0);
+    lx = label();
     return true;
   }
-  for (uint32_t q = q0, q1 = g.in_off[x + 1]; q < q1; ++q) {
-    const uint4 r = g.in_rec[q];
-    const uint32_t inf = g.in_info[q];
-    if (!edge_ok(inf, acc)) continue;
-    const unsigned long long lu = lab(r.y, r.z >> 1, r.z & 1u);
-    if (lu != kKeyInf && lu + make_key(r.w, time_ms_dev(r.w, mode_speed_dkph(mode, inf & 0xffffu))) == lx) {
-      rec = r;
-      plu = lu;
-      return true;
-    }
-  }
-  return false;
-}
-
-// Turn weight of a route the tables answer, by walking its two-exit canonical path back through
-// the tables (ball_pred_step, as the path stage walks): for the routes whose turn row cannot give it
-// -- a tie between the exits at the entry node (the canonical path may mix both exits' trees: a
-// source at a node whose route runs along its own road ties there), or a row without its sum.
-// x: the entry node (at `side` of road rb), r1 / r0: both exits' rows of rb.  ok false: no path.
-__device__ uint32_t ball_turn_walk(const DevGraph& g, const BallPathLabels& lab, const K2Turn& T, uint32_t rb,
-                                   uint32_t x, uint32_t side, uint4 r1, uint4 r0, bool& ok) {
-  const uint32_t acc = mode_access((int)T.mode);
-  uint32_t hs = head_start(g.road_head[rb], side);
-  unsigned long long lx = side ? ball_label(lab.rk1, row_key1(r1), lab.rk0, row_key1(r0))
-                               : ball_label(lab.rk1, row_key0(r1), lab.rk0, row_key0(r0));
-  uint32_t U = 0;
-  ok = true;
-  for (uint32_t guard = 0; guard <= 2u * kBallMaxKeysHost + 2u; ++guard) {
-    if (lx == kKeyInf) break;
-    if (x == T.n1 && lx == lab.rk1) return U + g.turn_w[turn_degree(head_back(T.hw, 0u), hs)];
-    if (x == T.n0 && lx == lab.rk0) return U + g.turn_w[turn_degree(head_back(T.hw, 1u), hs)];
-    uint4 rec;
-    unsigned long long plu;
-    if (!ball_pred_step(g, lab, acc, (int)T.mode, x, lx, r1, r0, side, rec, plu)) break;
-    const uint32_t hw = g.road_head[rec.z >> 1], rev = rec.z & 1u;
-    U += g.turn_w[turn_degree(head_back(hw, rev), hs)];
-    hs = head_start(hw, rev);
-    x = rec.y;
-    side = rev;   // the edge's start: node0 of its road when it runs forward
-    lab.rows(rec.z >> 1, r1, r0);
-    lx = side ? ball_label(lab.rk1, row_key1(r1), lab.rk0, row_key1(r0))
-              : ball_label(lab.rk1, row_key0(r1), lab.rk0, row_key0(r0));
-  }
-  ok = false;
-  return 0u;
-}
+};
+// iterations of the tables' turn walk: for the routes whose turn row cannot give the weight -- a
+// tie between the exits at the entry node (the canonical path may mix both exits' trees: a source
+// at a node whose route runs along its own road ties there), or a row without its sum
+constexpr uint32_t kTableTurnSteps = 2u * kBallMaxKeysHost + 3u;
 
 // A route the tables answer in a batch with turn costs (rule 3b, TURN), and its distance term
 // d = turn_m + |route_m - gc| (route_term).  The turn weight: when one exit gives the entry node
 // its label strictly, that exit's turn row holds the weight of the path from the exit node on and
 // the heading it leaves the exit node with, and the turn at the exit node is from the source road;
-// otherwise (a tie, or a row without its sum) ball_turn_walk.
+// otherwise (a tie, or a row without its sum) canonical_turns through the tables.
 // pt1 / pt0: both exits' turn rows at the first-probe slots h1s / h0s, loaded with the probes (a
 // route resolved past a collision reloads its row); tw: the turn weights in LDS
 __device__ __forceinline__ uint32_t k2_route_turn(const DevGraph& g, const K2Src& S, const K2Turn& T, const uint4& t0,
@@ -2300,8 +2321,10 @@ __device__ __forceinline__ uint32_t k2_route_turn(const DevGraph& g, const K2Src
       U = tw[turn_degree(head_back(T.hw, e1 ? 0u : 1u), w >> kTurnHeadShift)] + (w & kTurnTMask);
     } else {
       const BallPathLabels lab{(const uint4*)S.ent, S.h1, S.h0, S.rk1, S.rk0, g.ball_road_mask};
+      TableCursor c{lab, r1, r0};
       bool ok = true;
-      U = ball_turn_walk(g, lab, T, t0.x, side ? t1.y : t1.x, side, r1, r0, ok);
+      U = canonical_turns(g, c, (int)T.mode, T.hw, T.n1, T.n0, S.rk1, S.rk0, t0.x, side ? t1.y : t1.x, side,
+                          kTableTurnSteps, ok);
       if (!ok) exact = false;
     }
   }
@@ -2582,7 +2605,7 @@ __device__ __forceinline__ void k2_phase2_turn1(const DevGraph& g, SM& sm, const
 
 // The turn weights K2 left to walk (each K2 block's region of b.walk), one lane each: the item again as
 // k_routes_ball2's phase 1 forms it, the route with both exits' turn rows at their first-probe
-// slots, and the walk through the tables (k2_route_turn / ball_turn_walk).  A route the tables
+// slots, and the walk through the tables (k2_route_turn / canonical_turns).  A route the tables
 // cannot decide hands its item to the search tiers, which run next.
 // one walked turn weight: item t's route to its pair's target j (ro: its route index, known to the
 // marker scan; kNone: from the item)
@@ -2860,41 +2883,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) k
   }
 }
 
-// path of one chosen transition (slot p) with a lane-resident search: canonical
-// predecessors (smallest-id tight in-edge from a labelled node) walked back from the
-// entry node.  Returns false when the search outgrew its label store (caller queues p).
-// Canonical predecessor of node x (label lx): the smallest-id usable in-edge (u -> x) with
-// label(u) + key(edge) == lx, in ascending edge id.  Each in-edge is one self-contained record
-// (edge, source node, road|rev, length; info word): one round trip before its label probe
-// instead of three dependent loads (in_edge -> edges -> edge_src).  Probing several in-edges
-// at once was slower: most nodes find the tight edge first, and the extra probes and
-// registers cost more than the overlap (C2 paths 0.32 -> 0.39 ms).
-template <class PL>
-__device__ __forceinline__ bool find_pred(const DevGraph& g, const PL& lab, uint32_t acc, int mode, uint32_t x,
-                                          unsigned long long lx, uint32_t& pe, uint32_t& pu, unsigned long long& plu) {
-  for (uint32_t q = g.in_off[x], q1 = g.in_off[x + 1]; q < q1; ++q) {
-    const uint4 r = g.in_rec[q];
-    const uint32_t inf = g.in_info[q];
-    if (!edge_ok(inf, acc)) continue;
-    // r.y is the edge's start: node0 of its road when the edge runs forward
-    const unsigned long long lu = lab(r.y, r.z >> 1, r.z & 1u);
-    if (lu != kKeyInf && lu + make_key(r.w, time_ms_dev(r.w, mode_speed_dkph(mode, inf & 0xffffu))) == lx) {
-      pe = r.x; pu = r.y; plu = lu;
-      return true;
-    }
-  }
-  return false;
-}
-
-// Walk the chosen transition's route back from its entry node by canonical predecessors
-// (smallest-id usable in-edge from a labelled node whose label + edge key equals the
-// node's label) and write its edges.  `key`/`combo` are the transition's route key and
-// combination (route_key_vals).
-template <class PL>
-__device__ __forceinline__ void path_walk(const DevGraph& g, const DevBatch& b, uint64_t p, const PL& lab, int mode,
-                                          const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1,
-                                          unsigned long long rk1, unsigned long long rk0, unsigned long long key,
-                                          int combo, int cap) {
+// Walk the chosen transition's (slot p) route back from its entry node along the canonical path
+// (cursor c: the search tiers' labels or the route tables) and write its edges.  `key`/`combo` are
+// the transition's route key and combination (route_key_vals), rk1 / rk0 the exit root keys; a
+// walk of more than `cap` steps fails.
+template <class Cursor>
+__device__ __forceinline__ void canonical_path(const DevGraph& g, const DevBatch& b, uint64_t p, Cursor& c, int mode,
+                                               const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1,
+                                               unsigned long long rk1, unsigned long long rk0, unsigned long long key,
+                                               int combo, int cap) {
   const uint32_t acc = mode_access(mode);
   const uint32_t n1a = a1.y, n0a = a1.x;
   uint32_t* inl = b.path_inline + p * kInlinePath;
@@ -2910,26 +2907,23 @@ __device__ __forceinline__ void path_walk(const DevGraph& g, const DevBatch& b, 
   // order) and stored after the walk: a store inside the walk would make every following
   // load wait for it (shared vmcnt).
   const uint32_t entry_e = combo == 2 ? g.road_fwd[b0.x] : g.road_rev[b0.x];
-  const uint32_t v0 = combo == 2 ? b1.x : b1.y;
-  uint32_t n = 1, x = v0;
-  unsigned long long lx = lab(v0, b0.x, combo == 2 ? 0u : 1u);
+  const uint32_t v0 = combo == 2 ? b1.x : b1.y, side0 = combo == 2 ? 0u : 1u;
+  uint32_t n = 1;
+  c.start(v0, b0.x, side0);
   uint32_t pr[kInlinePath];
 #pragma unroll
   for (int q = 0; q < kInlinePath; ++q) pr[q] = entry_e;
   for (int guard = 0;; ++guard) {
-    if (lx == kKeyInf || guard > cap) { trace_fail(b, p, kErrRounds); return; }
-    if ((x == n1a && lx == rk1) || (x == n0a && lx == rk0)) break;
-    uint32_t pe = kNone, pu = 0;
-    unsigned long long plu = kKeyInf;
-    if (!find_pred(g, lab, acc, mode, x, lx, pe, pu, plu)) { trace_fail(b, p, kErrRounds); return; }
+    if (c.lx == kKeyInf || guard > cap) { trace_fail(b, p, kErrRounds); return; }
+    if ((c.x == n1a && c.lx == rk1) || (c.x == n0a && c.lx == rk0)) break;
+    uint4 rec = make_uint4(kNone, 0u, 0u, 0u);   // (set: left unset, k_paths_lane's stage measured 3 % slower)
+    if (!c.step(g, acc, mode, rec)) { trace_fail(b, p, kErrRounds); return; }
 #pragma unroll
     for (int q = kInlinePath - 1; q > 0; --q) pr[q] = pr[q - 1];
-    pr[0] = pe;
+    pr[0] = rec.x;
     ++n;
-    x = pu;
-    lx = plu;
   }
-  const uint32_t exit_e = (x == n1a) ? g.road_fwd[a0.x] : g.road_rev[a0.x];
+  const uint32_t exit_e = (c.x == n1a) ? g.road_fwd[a0.x] : g.road_rev[a0.x];
 #pragma unroll
   for (int q = kInlinePath - 1; q > 0; --q) pr[q] = pr[q - 1];
   pr[0] = exit_e;
@@ -2951,18 +2945,17 @@ __device__ __forceinline__ void path_walk(const DevGraph& g, const DevBatch& b, 
   uint32_t* dst = b.path_pool + at;
   dst[n - 1] = entry_e;
   dst[0] = exit_e;
-  x = v0;
-  lx = lab(v0, b0.x, combo == 2 ? 0u : 1u);
+  c.start(v0, b0.x, side0);
   for (uint32_t q = n - 2; q >= 1; --q) {
-    uint32_t pe = kNone, pu = 0;
-    unsigned long long plu = kKeyInf;
-    if (!find_pred(g, lab, acc, mode, x, lx, pe, pu, plu)) break;   // found on the first walk
-    dst[q] = pe; x = pu; lx = plu;
+    uint4 rec = make_uint4(kNone, 0u, 0u, 0u);   // (set: left unset, k_paths_lane's stage measured 3 % slower)
+    if (!c.step(g, acc, mode, rec)) break;   // found on the first walk
+    dst[q] = rec.x;
   }
 }
 
-// path of one chosen transition (slot p) with a lane-resident search.  Returns false when
-// the search outgrew its label store (caller queues p).
+// path of one chosen transition (slot p) with a lane-resident search: its canonical path
+// through the search's labels.  Returns false when the search outgrew its label store (caller
+// queues p).
 template <class L>
 __device__ __forceinline__ bool lane_path(const DevGraph& g, const DevBatch& b, uint64_t p, L& S, int cap) {
   const uint4 pi = b.pair_info[p];
@@ -2976,89 +2969,9 @@ __device__ __forceinline__ bool lane_path(const DevGraph& g, const DevBatch& b, 
   if (S.ovf) return false;
   int combo = -1;
   const unsigned long long key = route_key(StoreLabel<L>{S}, a0, b0, b1, &combo);
-  path_walk(g, b, p, SearchPathLabels<L>{S}, mode, a0, a1, b0, b1, rk1, rk0, key, combo, cap);
+  SearchCursor<SearchPathLabels<L>> c{{S}};
+  canonical_path(g, b, p, c, mode, a0, a1, b0, b1, rk1, rk0, key, combo, cap);
   return true;
-}
-
-// path_walk for the ball tier: canonical predecessors from the rows (ball_pred_step), one
-// probe pair per walked node instead of one per examined in-edge
-// (r1_0 / r0_0: both exits' rows of the target road, already probed for the route key)
-__device__ void path_walk_ball(const DevGraph& g, const DevBatch& b, uint64_t p, const BallPathLabels& lab, int mode,
-                               const uint4& a0, const uint4& a1, const uint4& b0, const uint4& b1,
-                               unsigned long long key, int combo, int cap, const uint4& r1_0, const uint4& r0_0) {
-  const uint32_t acc = mode_access(mode);
-  const uint32_t n1a = a1.y, n0a = a1.x;
-  const unsigned long long rk1 = lab.rk1, rk0 = lab.rk0;
-  uint32_t* inl = b.path_inline + p * kInlinePath;
-  if (combo <= 1) {
-    b.route_dist[p] = key_dist(key);
-    b.path_sab[p] = make_uint2(a0.y, b0.y);
-    inl[0] = combo == 0 ? g.road_fwd[a0.x] : g.road_rev[a0.x];
-    b.path_cnt[p] = 1;
-    b.path_off[p] = 0;
-    return;
-  }
-  const uint32_t entry_e = combo == 2 ? g.road_fwd[b0.x] : g.road_rev[b0.x];
-  const uint32_t v0 = combo == 2 ? b1.x : b1.y, side0 = combo == 2 ? 0u : 1u;
-  auto label_at = [&](const uint4& r1, const uint4& r0, uint32_t side) {
-    return side ? ball_label(rk1, row_key1(r1), rk0, row_key1(r0)) : ball_label(rk1, row_key0(r1), rk0, row_key0(r0));
-  };
-  const unsigned long long lx0 = label_at(r1_0, r0_0, side0);
-  // first walk: edges shifted into registers (front = travel order), stored after the walk
-  uint32_t n = 1, x = v0, side = side0;
-  unsigned long long lx = lx0;
-  uint4 r1 = r1_0, r0 = r0_0;
-  uint32_t pr[kInlinePath];
-#pragma unroll
-  for (int q = 0; q < kInlinePath; ++q) pr[q] = entry_e;
-  for (int guard = 0;; ++guard) {
-    if (lx == kKeyInf || guard > cap) { trace_fail(b, p, kErrRounds); return; }
-    if ((x == n1a && lx == rk1) || (x == n0a && lx == rk0)) break;
-    uint4 rec;
-    unsigned long long plu;
-    if (!ball_pred_step(g, lab, acc, mode, x, lx, r1, r0, side, rec, plu)) { trace_fail(b, p, kErrRounds); return; }
-#pragma unroll
-    for (int q = kInlinePath - 1; q > 0; --q) pr[q] = pr[q - 1];
-    pr[0] = rec.x;
-    ++n;
-    x = rec.y;
-    side = rec.z & 1u;   // the edge's start: node0 of its road when it runs forward
-    lab.rows(rec.z >> 1, r1, r0);
-    lx = label_at(r1, r0, side);
-  }
-  const uint32_t exit_e = (x == n1a) ? g.road_fwd[a0.x] : g.road_rev[a0.x];
-#pragma unroll
-  for (int q = kInlinePath - 1; q > 0; --q) pr[q] = pr[q - 1];
-  pr[0] = exit_e;
-  ++n;
-  b.route_dist[p] = key_dist(key);
-  b.path_sab[p] = make_uint2(a0.y, b0.y);
-  b.path_cnt[p] = n;
-  if (n <= (uint32_t)kInlinePath) {
-#pragma unroll
-    for (int q = 0; q < kInlinePath; ++q)
-      if ((uint32_t)q < n) inl[q] = pr[q];
-    b.path_off[p] = 0;
-    return;
-  }
-  // long path: pool slot, second walk writing in travel order
-  const uint32_t at = atomicAdd(&b.ctl[kCtlPathUsed], n);
-  if ((uint64_t)at + n > b.path_cap) { atomicOr(&b.ctl[kCtlErr], kErrPathOverflow); b.path_off[p] = kNone; return; }
-  b.path_off[p] = at;
-  uint32_t* dst = b.path_pool + at;
-  dst[n - 1] = entry_e;
-  dst[0] = exit_e;
-  x = v0; side = side0; r1 = r1_0; r0 = r0_0; lx = lx0;
-  for (uint32_t q = n - 2; q >= 1; --q) {
-    uint4 rec;
-    unsigned long long plu;
-    if (!ball_pred_step(g, lab, acc, mode, x, lx, r1, r0, side, rec, plu)) break;   // found on the first walk
-    dst[q] = rec.x;
-    x = rec.y;
-    side = rec.z & 1u;
-    lab.rows(rec.z >> 1, r1, r0);
-    lx = label_at(r1, r0, side);
-  }
 }
 
 // path ball tier: one lane per chosen transition whose bound fits the ball radius; the
@@ -3116,7 +3029,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
     link_append<PathsStage>(b, kLinkBallToSearch, (uint32_t)p);
     return;
   }
-  path_walk_ball(g, b, p, lab, mode, a0, a1, b0, b1, key, combo, (int)kBallMaxKeys, r1, r0);
+  TableCursor c{lab, r1, r0};
+  canonical_path(g, b, p, c, mode, a0, a1, b0, b1, rk1, rk0, key, combo, (int)kBallMaxKeys);
 }
 
 // path lane tier: one lane per chosen transition, labels in registers.  With `listed`,
@@ -3195,10 +3109,12 @@ __device__ bool routes_search_item(SearchSmem<H, false>& sm, uint4* s_src, const
       b.route[base + i * KB + j] = out;
       if (turn) {   // the route's turn weight (rule 3b) from the same labels
         bool wok = true;
-        const uint32_t u = (out == kRouteInvalid || !pi.w)
-                               ? 0u
-                               : search_turn_walk(g, HashPathLabel<H, false>{sm}, mode, s_src[0], s_src[1], t0, t1, rk1, rk0,
-                                                  combo, wok);
+        uint32_t u = 0u;
+        if (out != kRouteInvalid && pi.w && combo >= 2) {
+          SearchCursor<HashPathLabel<H, false>> c{{sm}};
+          u = canonical_turns(g, c, mode, g.road_head[s_src[0].x], s_src[1].y, s_src[1].x, rk1, rk0, t0.x,
+                              combo == 2 ? t1.x : t1.y, combo == 2 ? 0u : 1u, kSearchTurnSteps, wok);
+        }
         if (!wok) trace_fail(b, p, kErrRounds);
         b.route_d[base + i * KB + j] = route_term(out, u, pi.w, gcp);
       }
@@ -4876,7 +4792,7 @@ __global__ void k_ball_lookup(DevGraph g, int mode, uint64_t n, const uint32_t* 
 // Turn row word of endpoint `side` of row e (road r) in the table of node x (rm_common.hpp
 // kTurnTMask): the canonical route x -> v walked back from v through the table's own rows -- the
 // predecessor stored in the row, or when that index was not stored a scan of v's in-edges for the
-// first usable tight one (as ball_pred_step) -- summing the turn at every node but x; at x the
+// first usable tight one (as TableCursor::step) -- summing the turn at every node but x; at x the
 // heading the route leaves x with.  kTurnNone when v is outside the ball or the sum does not fit.
 __device__ uint32_t ball_turn_word(const DevGraph& g, int mode, uint32_t x, const uint2& h, const uint4* ent, uint32_t rm,
                                    uint4 e, uint32_t side) {

@@ -3162,6 +3162,11 @@ constexpr int kVitChunk = 16;     // layers per staged chunk (one per lane of th
 #endif
 constexpr int kVitRoutes = RM_VIT_ROUTES;  // routes per staged chunk and group
 constexpr int kVitBt = 64;        // layers per backtrace staging block
+constexpr double kInfD = __builtin_huge_val();   // +inf: an invalid route, an unreachable candidate
+// control words of a backtrace (vit_backtrace): the walking lane's report to its trace's lanes
+struct VitWalk {
+  uint32_t nch, done, w, pad;     // choices made in this block, the chain is traced, the next row's winner
+};
 struct VitGroup {
   // LDS per wave bounds K3's residency (C2: 2,500 waves over 256 CUs need <= 14.5 KB per
   // wave for one round), so the backtrace staging aliases the chunk's routes; a backtrace
@@ -3176,10 +3181,7 @@ struct VitGroup {
   uint4 bpo[kVitChunk + 1];       // this chunk's back-pointer rows (16 x u8); + a spare row
   uint8_t cs[kVitChunk + 1];      // this chunk's chain-start flags (+ spare)
   uint8_t ch[kVitBt];             // choices of one backtrace block
-  uint32_t nch, done, w, pad;
-#if defined(RM_VIT_PAD) && RM_VIT_PAD > 0
-  uint32_t padv[RM_VIT_PAD];      // A/B of the four groups' LDS bank alignment
-#endif
+  VitWalk walk;
 };
 
 static_assert(sizeof(VitGroup) >= (kVitRoutes + 15 + 7 * 16 + 1) * sizeof(double), "K3 prefetch reads (8 source rows) stay inside VitGroup");
@@ -3232,68 +3234,107 @@ __device__ __forceinline__ void vit_min(double& best, int& arg, double cj, const
   }
 }
 
+// ------------------------------------------------------------------------------------------
+// K3, the pieces both kernels share (k_viterbi here, k_viterbi_w below): what surrounds the
+// layer recurrence and must agree with the oracle bit for bit.  A trace owns L lanes, 16 in
+// k_viterbi and the whole wave in k_viterbi_w.
+template <int CTRL>
+__device__ __forceinline__ double dpp_d(double v) {
+  const unsigned long long u = __double_as_longlong(v);
+  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
+  return __longlong_as_double(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
+}
 
+// minimum over each aligned group of W lanes, in every lane of the group (all lanes active)
+template <int W>
+__device__ __forceinline__ double group_min(double c) {
+  c = __builtin_fmin(c, dpp_d<0xB1>(c));                      // quad_perm [1,0,3,2]
+  c = __builtin_fmin(c, dpp_d<0x4E>(c));                      // quad_perm [2,3,0,1]
+  if constexpr (W >= 8) c = __builtin_fmin(c, dpp_d<0x141>(c));   // row_half_mirror (x <-> 7-x)
+  if constexpr (W >= 16) c = __builtin_fmin(c, dpp_d<0x140>(c));  // row_mirror (x <-> 15-x)
+  return c;
+}
+
+// Winner of a chain's last layer: the lowest cost, ties to the lowest candidate.  The one rule
+// this section keeps twice, because a k_viterbi that calls vit_winner is slower: 0.238 against
+// 0.228 ms for a lone C2 trace, with the layer loop's instructions unchanged ("What the
+// two K3 kernels share").  Both need whole 16-lane rows active.
+// k_viterbi_w: lane j of the wave holds the cost of candidate j (in: j is a candidate)
+__device__ __forceinline__ uint32_t vit_winner(double cost, bool in) {
+  const double c = in ? cost : kInfD;
+  const double m = group_min<16>(c);
+  const uint32_t eq = (uint32_t)(__ballot(in && c == m) & 0xffffull);
+  return (uint32_t)__builtin_ctz(eq | 0x10000u);
+}
 __device__ __forceinline__ double shfl_xor_d(double v, int m, int width) {
   const unsigned long long u = __double_as_longlong(v);
   const int lo = __shfl_xor((int)(uint32_t)u, m, width), hi = __shfl_xor((int)(uint32_t)(u >> 32), m, width);
   return __longlong_as_double(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
 }
-
-// back-pointer rows and chain-start flags of chunk layers [0, n) to HBM (layer l at slot l0 + l;
-// csm: the chunk's chain-start flags as a wave mask, bit `lane` = layer j of lane j's group)
-__device__ __forceinline__ void vit_flush_m(const DevBatch& b, const VitGroup& gs, uint64_t l0, uint32_t n, int j,
-                                            unsigned long long csm) {
-  if ((uint32_t)j < n) {
-    *reinterpret_cast<uint4*>(b.bp + (l0 + j) * kMaxCand) = gs.bpo[j];
-    b.chain_start[l0 + j] = __builtin_amdgcn_inverse_ballot_w64(csm) ? 1 : 0;
-  }
-}
-
-// Backtrace of the chain ending at layer `end` (lane j holds cost j of that layer, K
-// candidates).  Winner = lowest cost, ties to the lowest j.  Rows are staged 64 layers
-// per block (four coalesced loads per lane); lane 0 of the group walks them in LDS and
-// the block's choices leave as one store per lane.
-__device__ void backtrace_chain(const DevBatch& b, VitGroup& gs, uint32_t o, uint32_t end, uint32_t K, int j, double cj) {
-  double bc = (j < (int)K) ? cj : __longlong_as_double(0x7ff0000000000000ll);
+// k_viterbi: lane j of the group holds cost j of K candidates; a butterfly on (cost, j) pairs
+__device__ __forceinline__ uint32_t vit_winner_shfl(double cj, uint32_t K, int j) {
+  double bc = (j < (int)K) ? cj : kInfD;
   int bj = (j < (int)K) ? j : 1 << 20;
   for (int m = 1; m < 16; m <<= 1) {
     const double oc = shfl_xor_d(bc, m, 16);
     const int oj = __shfl_xor(bj, m, 16);
     if (oc < bc || (oc == bc && oj < bj)) { bc = oc; bj = oj; }
   }
-  uint32_t w = (uint32_t)bj;
+  return (uint32_t)bj;
+}
+
+// back-pointer rows (bpo) and chain-start flags of chunk layers [0, n) to HBM: layer l at slot
+// l0 + l, by lane l of the trace (csm: the flags as a wave mask, this lane's bit for its layer;
+// read under the branch -- formed by the caller, k_viterbi paid 0.004 ms a lone trace for it)
+__device__ __forceinline__ void vit_flush(const DevBatch& b, const uint4* bpo, uint64_t l0, uint32_t n, int lane,
+                                          unsigned long long csm) {
+  if ((uint32_t)lane < n) {
+    *reinterpret_cast<uint4*>(b.bp + (l0 + lane) * kMaxCand) = bpo[lane];
+    b.chain_start[l0 + lane] = __builtin_amdgcn_inverse_ballot_w64(csm) ? 1 : 0;
+  }
+}
+
+// Backtrace of the chain that ends at layer `end` with candidate w (its winner), by the L lanes
+// of its trace (lane: 0 .. L-1).  Rows are staged kVitBt layers per block into bst (kVitBt / L
+// coalesced loads per lane); lane 0 walks them in LDS, and the block's choices (ch) leave as one
+// store per lane and row.
+template <int L>
+__device__ void vit_backtrace(const DevBatch& b, uint4* bst, uint8_t* ch, VitWalk& wk, uint32_t o, uint32_t end,
+                              uint32_t w, int lane) {
+  constexpr int R = kVitBt / L;
   __threadfence_block();  // this wave's bp stores are visible to its loads
   int t = (int)end;
   for (;;) {
-    uint4 row[kVitBt / 16];
+    uint4 row[R];
 #pragma unroll
-    for (int x = 0; x < kVitBt / 16; ++x) {   // every row load in flight before the LDS stores
-      const int lay = t - (j + 16 * x);
+    for (int x = 0; x < R; ++x) {   // every row load in flight before the LDS stores
+      const int lay = t - (lane + L * x);
       row[x] = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
       if (lay >= 0) row[x] = *reinterpret_cast<const uint4*>(b.bp + (uint64_t)(o + lay) * kMaxCand);
     }
 #pragma unroll
-    for (int x = 0; x < kVitBt / 16; ++x) gs.bst[j + 16 * x] = row[x];
+    for (int x = 0; x < R; ++x) bst[lane + L * x] = row[x];
     wave_sync();
-    if (j == 0) {
+    if (lane == 0) {
       uint32_t l = 0, done = 0;
       for (; l < (uint32_t)kVitBt && t - (int)l >= 0;) {
-        gs.ch[l] = (uint8_t)w;
-        const uint32_t nb = reinterpret_cast<const uint8_t*>(&gs.bst[l])[w];
+        ch[l] = (uint8_t)w;
+        const uint32_t nb = reinterpret_cast<const uint8_t*>(&bst[l])[w];
         ++l;
         if (nb == 255u) { done = 1; break; }
         w = nb;
       }
       if (t - (int)l < 0) done = 1;
-      gs.nch = l; gs.done = done; gs.w = w;
+      wk.nch = l; wk.done = done; wk.w = w;
     }
     wave_sync();
-    const uint32_t n = gs.nch;
+    const uint32_t n = wk.nch;
 #pragma unroll
-    for (int x = 0; x < kVitBt / 16; ++x)
-      if ((uint32_t)(j + 16 * x) < n) b.choice[o + t - (j + 16 * x)] = (int8_t)gs.ch[j + 16 * x];
-    const bool done = gs.done != 0;
-    w = gs.w;
+    for (int x = 0; x < R; ++x)
+      if ((uint32_t)(lane + L * x) < n) b.choice[o + t - (lane + L * x)] = (int8_t)ch[lane + L * x];
+    const bool done = wk.done != 0;
+    w = wk.w;
     t -= (int)n;
     wave_sync();
     if (done) break;
@@ -3305,15 +3346,17 @@ struct VitLayerDesc {
   double gc;
 };
 
-// the loads behind a VitLayerDesc, kept raw: k_viterbi_w loads them a chunk ahead and forms the
-// description (vit_cook) only when it lays that chunk out, so nothing waits on them early
+// the loads behind a VitLayerDesc, kept raw: the kernels load them a chunk ahead and form the
+// description (vit_cook) only when they lay that chunk out, so nothing waits on them early.
+// Layer s0 + j of the trace, clamped to its last; an empty trace (or a lane past the batch)
+// reads layer 0 of the batch.
 struct VitLayerRaw {
   uint32_t kb, ka, off;
   double gc;
 };
 __device__ __forceinline__ VitLayerRaw vit_raw(const DevBatch& b, uint32_t o, uint32_t S, uint32_t s0, int j) {
-  const uint64_t lq = o + min(s0 + (uint32_t)j, S - 1);
-  const uint64_t lp = lq == o ? o : lq - 1;
+  const uint64_t lq = S ? o + min(s0 + (uint32_t)j, S - 1) : 0u;
+  const uint64_t lp = (S == 0 || lq == o) ? lq : lq - 1;
   VitLayerRaw r;
   r.kb = b.cand_n[lq];
   r.ka = b.cand_n[lp];
@@ -3321,6 +3364,7 @@ __device__ __forceinline__ VitLayerRaw vit_raw(const DevBatch& b, uint32_t o, ui
   r.gc = b.gc[lq];
   return r;
 }
+// layer s0 + j of a trace: candidate count, route count, route offset, gc
 __device__ __forceinline__ VitLayerDesc vit_cook(const VitLayerRaw& r, uint32_t S, uint32_t s0, int j) {
   const uint32_t sl = s0 + j;
   const bool vq = sl < S;
@@ -3332,21 +3376,40 @@ __device__ __forceinline__ VitLayerDesc vit_cook(const VitLayerRaw& r, uint32_t 
   return d;
 }
 
-// layer s0 + j of a trace: candidate count, route count, route offset, gc
-__device__ __forceinline__ VitLayerDesc vit_describe(const DevBatch& b, uint32_t o, uint32_t S, uint32_t s0, int j) {
-  const uint32_t sl = s0 + j;
-  const bool vq = sl < S;
-  const uint64_t lq = o + min(sl, S - 1);
-  const uint64_t lp = lq == o ? o : lq - 1;
-  const uint32_t kb_raw = b.cand_n[lq], ka_raw = b.cand_n[lp];
-  const double g_raw = b.gc[lq];
-  VitLayerDesc d;
-  d.off = b.trans_off[lq];
-  d.kb = vq ? kb_raw : 0u;
-  d.cnt = (vq && sl >= 1) ? ka_raw * d.kb : 0u;
-  d.gc = (vq && sl >= 1) ? g_raw : 0.0;
-  return d;
+// a route's centimetres as fp64 metres, +inf when invalid: the form the recurrences stage
+__device__ __forceinline__ double vit_metres(uint32_t cm) {
+  return cm == kRouteInvalid ? kInfD : (double)cm * 0.01;
 }
+
+// The chunk's routes back into LDS from HBM after a backtrace, which staged through route_m
+// (rare: a chain broke inside the chunk).  L lanes per trace, N routes per lane.
+template <bool TURN, int L, int N>
+__device__ __forceinline__ void vit_restage(double* route_m, const DevBatch& b, uint32_t rbase, uint32_t nroutes,
+                                            int lane) {
+  const uint32_t* rp = b.route + rbase;
+  const double* dp = b.route_d + rbase;   // (formed, never read, without turn costs)
+#pragma unroll
+  for (int x = 0; x < N; ++x) {
+    const uint32_t q = (uint32_t)(lane + L * x);
+    if (q < nroutes) {
+      // with turn costs (rule 3b) the staged value is the distance term route_d
+      if constexpr (TURN) route_m[q] = dp[q];
+      else route_m[q] = vit_metres(rp[q]);
+    }
+  }
+}
+
+// A chunk's routes (with turn costs: its distance terms) and emission rows, loaded into
+// registers one chunk ahead: NR route registers and NS emission vectors per lane.
+// (the emission row as a native vector: HIP's float4 is a union-backed class, which the
+// compiler kept in scratch across the chunk loop -- one more wait per chunk)
+typedef float v3_f4 __attribute__((ext_vector_type(4)));
+template <bool TURN, int NR, int NS>
+struct VitRegs {
+  uint32_t rv[TURN ? 1 : NR];
+  double rd[TURN ? NR : 1];
+  v3_f4 sv[NS];
+};
 
 // ------------------------------------------------------------------------------------------
 // K3 (round 2, v3): one wave per trace, one lane per transition.  A layer's K_A x K_B
@@ -3376,14 +3439,14 @@ struct Vit3Smem {
   union {
     double route_m[kV3Routes + 2];           // [kV3Routes] = +inf: the route of an idle lane
     struct {
-      uint4 bst[kWave];                      // backtrace staging (64 back-pointer rows)
-      uint8_t ch[kWave];
+      uint4 bst[kVitBt];                     // backtrace staging (64 back-pointer rows)
+      uint8_t ch[kVitBt];                    // choices of one backtrace block
     } bt;
   };
   float sq[kV3Chunk][kMaxCand];
   double cost[2][kMaxCand];                  // previous / next layer costs (ping-pong)
   uint4 bpo[kV3Chunk];                       // this chunk's back-pointer rows
-  uint32_t nch, done, w, pad;
+  VitWalk walk;
 };
 static_assert(sizeof(Vit3Smem) <= 5120, "K3 v3 must keep 8 waves per SIMD (32 per CU) within LDS");
 
@@ -3392,24 +3455,6 @@ struct V3Chunk {
   uint32_t kbrel;   // lane t < C: K_B of layer s0 + t | offset of its routes in the chunk << 8
   double gc;        // lane t < C: gc of layer s0 + t
 };
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_d(double v) {
-  const unsigned long long u = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xf, 0xf, false);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-
-// minimum over each aligned group of W lanes, in every lane of the group (all lanes active)
-template <int W>
-__device__ __forceinline__ double group_min(double c) {
-  c = __builtin_fmin(c, dpp_d<0xB1>(c));                      // quad_perm [1,0,3,2]
-  c = __builtin_fmin(c, dpp_d<0x4E>(c));                      // quad_perm [2,3,0,1]
-  if constexpr (W >= 8) c = __builtin_fmin(c, dpp_d<0x141>(c));   // row_half_mirror (x <-> 7-x)
-  if constexpr (W >= 16) c = __builtin_fmin(c, dpp_d<0x140>(c));  // row_mirror (x <-> 15-x)
-  return c;
-}
 
 __device__ __forceinline__ double readlane_d(double v, uint32_t l) {
   const unsigned long long u = __double_as_longlong(v);
@@ -3446,19 +3491,9 @@ __device__ __forceinline__ V3Chunk v3_layout(const VitLayerDesc& d, uint32_t s0,
 // nroutes): a conditional load leaves a register merge behind it, and the copy that merge
 // needs makes the wave wait for the load at once -- measured, each chunk then paid the full
 // memory latency before its first layer (C1's 1,000-layer trace: 0.52 ms in K3).
-// (the emission row as a native vector: HIP's float4 is a union-backed class, which the
-// compiler kept in scratch across the chunk loop -- one more wait per chunk)
-typedef float v3_f4 __attribute__((ext_vector_type(4)));
-template <bool TURN>
-struct V3Regs {
-  uint32_t rv[TURN ? 1 : kV3Regs];
-  double rd[TURN ? kV3Regs : 1];
-  v3_f4 sv;
-};
-
 template <bool TURN>
 __device__ __forceinline__ void v3_load(const DevBatch& b, uint32_t o, uint32_t S, const V3Chunk& c, int lane,
-                                        V3Regs<TURN>& r) {
+                                        VitRegs<TURN, kV3Regs, 1>& r) {
   const uint32_t rlast = c.nroutes ? c.nroutes - 1u : 0u;
 #pragma unroll
   for (int x = 0; x < kV3Regs; ++x) {
@@ -3469,68 +3504,20 @@ __device__ __forceinline__ void v3_load(const DevBatch& b, uint32_t o, uint32_t 
   const uint32_t s0 = min(c.s0, S - 1u);
   const uint32_t C = max(min(c.C, S - s0), 1u);
   const v3_f4* src = reinterpret_cast<const v3_f4*>(b.cand_sq) + (uint64_t)(o + s0) * (kMaxCand / 4);
-  r.sv = src[min((uint32_t)lane, C * (kMaxCand / 4) - 1u)];
+  r.sv[0] = src[min((uint32_t)lane, C * (kMaxCand / 4) - 1u)];
 }
 
 template <bool TURN>
-__device__ __forceinline__ void v3_stage_routes(Vit3Smem& sm, const V3Chunk& c, int lane, const V3Regs<TURN>& r) {
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+__device__ __forceinline__ void v3_stage_routes(Vit3Smem& sm, const V3Chunk& c, int lane,
+                                                const VitRegs<TURN, kV3Regs, 1>& r) {
 #pragma unroll
   for (int x = 0; x < kV3Regs; ++x)
     if ((uint32_t)(lane + kWave * x) < c.nroutes) {
       // with turn costs (rule 3b) the staged value is the distance term route_d (turn_m +
       // |route_m - gc|, +inf when invalid) in place of the route's metres
       if constexpr (TURN) sm.route_m[lane + kWave * x] = r.rd[x];
-      else sm.route_m[lane + kWave * x] = r.rv[x] == kRouteInvalid ? INF : (double)r.rv[x] * 0.01;
+      else sm.route_m[lane + kWave * x] = vit_metres(r.rv[x]);
     }
-}
-
-// back-pointer rows / chain flags (csm: bit l = layer l starts a chain) of chunk layers [0, n) to HBM
-__device__ __forceinline__ void v3_flush(const DevBatch& b, const Vit3Smem& sm, uint64_t l0, uint32_t n, int lane,
-                                         uint32_t csm) {
-  if ((uint32_t)lane < n) {
-    *reinterpret_cast<uint4*>(b.bp + (l0 + lane) * kMaxCand) = sm.bpo[lane];
-    b.chain_start[l0 + lane] = (uint8_t)((csm >> lane) & 1u);
-  }
-}
-
-// Backtrace of the chain ending at layer `end` whose costs are sm.cost[cb][0..K): winner =
-// lowest cost, ties to the lowest j; rows staged 64 layers at a time, lane 0 walks them.
-__device__ void v3_backtrace(const DevBatch& b, Vit3Smem& sm, uint32_t o, uint32_t end, uint32_t K, int cb, int lane) {
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
-  const double c = (uint32_t)lane < K ? sm.cost[cb][lane & 15] : INF;
-  const double m = group_min<16>(c);
-  const uint32_t eq = (uint32_t)(__ballot((uint32_t)lane < K && c == m) & 0xffffull);
-  uint32_t w = (uint32_t)__builtin_ctz(eq | 0x10000u);
-  __threadfence_block();  // this wave's bp stores are visible to its loads
-  int t = (int)end;
-  for (;;) {
-    const int lay = t - lane;
-    uint4 row = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-    if (lay >= 0) row = *reinterpret_cast<const uint4*>(b.bp + (uint64_t)(o + lay) * kMaxCand);
-    sm.bt.bst[lane] = row;
-    wave_sync();
-    if (lane == 0) {
-      uint32_t l = 0, done = 0;
-      for (; l < (uint32_t)kWave && t - (int)l >= 0;) {
-        sm.bt.ch[l] = (uint8_t)w;
-        const uint32_t nb = reinterpret_cast<const uint8_t*>(&sm.bt.bst[l])[w];
-        ++l;
-        if (nb == 255u) { done = 1; break; }
-        w = nb;
-      }
-      if (t - (int)l < 0) done = 1;
-      sm.nch = l; sm.done = done; sm.w = w;
-    }
-    wave_sync();
-    const uint32_t n = sm.nch;
-    if ((uint32_t)lane < n) b.choice[o + t - lane] = (int8_t)sm.bt.ch[lane];
-    const bool done = sm.done != 0;
-    w = sm.w;
-    t -= (int)n;
-    wave_sync();
-    if (done) break;
-  }
 }
 
 // one pass of layer t over targets [j0, j0 + 64/W): lane = (target j0 + lane/W, source lane%W);
@@ -3539,7 +3526,6 @@ template <int W, bool TURN>
 __device__ __forceinline__ unsigned long long v3_pass(Vit3Smem& sm, int lane, uint32_t j0, uint32_t KB, uint32_t KA,
                                                       uint32_t rel, double gcl, double inv_beta, double inv2s2, int cb,
                                                       uint32_t t, double em4) {
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
   const uint32_t i = (uint32_t)lane & (W - 1), j = j0 + ((uint32_t)lane / W);
   const bool valid = i < KA && j < KB;
   const uint32_t at = valid ? rel + i * KB + j : (uint32_t)kV3Routes;
@@ -3551,16 +3537,16 @@ __device__ __forceinline__ unsigned long long v3_pass(Vit3Smem& sm, int lane, ui
   const double d = TURN ? rm : fabs(rm - gcl);
   const double c = __builtin_fma(d, inv_beta, ci);
   const double m = group_min<W>(c);
-  const unsigned long long eq = __ballot(c == m && m < INF);
+  const unsigned long long eq = __ballot(c == m && m < kInfD);
   const uint32_t g = (uint32_t)(eq >> ((uint32_t)lane & ~(uint32_t)(W - 1))) & ((1u << W) - 1u);
   const bool head = i == 0u && j < KB;
   // a group has an arg-min exactly when its minimum is finite (some lane equals it); the values
   // are formed in every lane and only the heads store
-  const bool fin = m < INF;
+  const bool fin = m < kInfD;
   const unsigned long long any = __ballot(head && fin);
   // W = 4 (one pass, j = lane / 4): the emission was read a layer ahead, off this layer's chain
   const double em = W == 4 ? em4 : (double)sm.sq[t][min(j, (uint32_t)kMaxCand - 1u)] * inv2s2;
-  const double nc = fin ? m + em : INF;
+  const double nc = fin ? m + em : kInfD;
   const uint8_t bpj = fin ? (uint8_t)__builtin_ctz(g | 0x10000u) : (uint8_t)255;
   if (head) {
     sm.cost[cb ^ 1][j] = nc;
@@ -3580,13 +3566,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT3
   const double inv2s2 = 1.0 / (2.0 * (double)op.sigma_z * (double)op.sigma_z);
   const double inv_beta = 1.0 / (double)op.beta;
   const double brk = (double)op.breakage_distance;
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
-  if (lane < 2 * kMaxCand) (&sm.cost[0][0])[lane] = INF;
-  if (lane == 0) sm.route_m[kV3Routes] = INF;
+  if (lane < 2 * kMaxCand) (&sm.cost[0][0])[lane] = kInfD;
+  if (lane == 0) sm.route_m[kV3Routes] = kInfD;
   if (S == 0) return;
   // chunk 0: describe, lay out, load; then describe chunk 1
-  V3Chunk cur = v3_layout(vit_describe(b, o, S, 0, lane & 15), 0, S, lane);
-  V3Regs<TURN> rg;
+  V3Chunk cur = v3_layout(vit_cook(vit_raw(b, o, S, 0, lane & 15), S, 0, lane & 15), 0, S, lane);
+  VitRegs<TURN, kV3Regs, 1> rg;
   v3_load<TURN>(b, o, S, cur, lane, rg);
   VitLayerRaw dn = vit_raw(b, o, S, cur.C, lane & 15);   // (past S: clamped; vit_cook gives kb 0)
   bool prev_ok = false;
@@ -3594,7 +3579,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT3
   int cb = 0;
   for (;;) {
     v3_stage_routes<TURN>(sm, cur, lane, rg);
-    if ((uint32_t)lane < cur.C * (kMaxCand / 4)) reinterpret_cast<v3_f4*>(&sm.sq[0][0])[lane] = rg.sv;
+    if ((uint32_t)lane < cur.C * (kMaxCand / 4)) reinterpret_cast<v3_f4*>(&sm.sq[0][0])[lane] = rg.sv[0];
     // the next chunk's routes and emission rows load while this chunk runs (unconditionally:
     // past the trace's end they are never staged)
     const uint32_t s1 = cur.s0 + cur.C;
@@ -3645,21 +3630,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT3
       if (s > 0 && prev_ok && (KB == 0 || start)) {
         // the chain ending at layer s - 1 is complete: its rows [.., s) must be in HBM
         wave_sync();
-        v3_flush(b, sm, o + cur.s0, t, lane, csm);
-        v3_backtrace(b, sm, o, s - 1, prevK, cb, lane);
+        vit_flush(b, sm.bpo, o + cur.s0, t, lane, csm);
+        vit_backtrace<kWave>(b, sm.bt.bst, sm.bt.ch, sm.walk, o, s - 1,
+                             vit_winner(sm.cost[cb][lane & 15], (uint32_t)lane < prevK), lane);
         if (t + 1 < cur.C) {   // the backtrace staged through route_m: bring the chunk back
-          const double INF = __longlong_as_double(0x7ff0000000000000ll);
-          const uint32_t* rp = b.route + cur.rbase;
-          const double* dp = b.route_d + cur.rbase;
-          __asm__ volatile("" : "+s"(rp), "+s"(dp));   // rare path: keep its addresses out of the loop's registers
-#pragma unroll
-          for (int x = 0; x < kV3Regs; ++x) {
-            const uint32_t q = (uint32_t)(lane + kWave * x);
-            if (q < cur.nroutes) {
-              if constexpr (TURN) sm.route_m[q] = dp[q];
-              else sm.route_m[q] = rp[q] == kRouteInvalid ? INF : (double)rp[q] * 0.01;
-            }
-          }
+          // rare path: keep its addresses out of the loop's registers.  The pin stands here and not
+          // in vit_restage because rbase is scalar only in this kernel (per group in k_viterbi);
+          // without it this kernel takes 94 VGPRs for 92 and the restage's loads lose their
+          // scalar base.
+          uint32_t rb = cur.rbase;
+          __asm__ volatile("" : "+s"(rb));
+          vit_restage<TURN, kWave, kV3Regs>(sm.route_m, b, rb, cur.nroutes, lane);
         }
       }
       if (KB == 0) {
@@ -3670,7 +3651,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT3
         continue;
       }
       if (start && lane < kMaxCand)   // a chain starts: cost = emission, back-pointers none
-        sm.cost[cb ^ 1][lane] = (uint32_t)lane < KB ? (double)sm.sq[t][lane] * inv2s2 : INF;
+        sm.cost[cb ^ 1][lane] = (uint32_t)lane < KB ? (double)sm.sq[t][lane] * inv2s2 : kInfD;
       csm |= (start ? 1u : 0u) << t;
       wave_sync();
       prev_ok = true;
@@ -3678,51 +3659,34 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT3
       cb ^= 1;
     }
     wave_sync();
-    v3_flush(b, sm, o + cur.s0, cur.C, lane, csm);
+    vit_flush(b, sm.bpo, o + cur.s0, cur.C, lane, csm);
     wave_sync();
     if (!has_next) break;
     cur = nx;
   }
   if (prev_ok) {
     wave_sync();
-    v3_backtrace(b, sm, o, S - 1, prevK, cb, lane);
+    vit_backtrace<kWave>(b, sm.bt.bst, sm.bt.ch, sm.walk, o, S - 1,
+                         vit_winner(sm.cost[cb][lane & 15], (uint32_t)lane < prevK), lane);
   }
 }
 
 // ------------------------------------------------------------------------------------------
-// K3 k_viterbi, the chunk pipeline (round 5).  Round 4's kernel loaded a chunk's routes and
-// emission rows at the chunk's start and waited for them there (one HBM round trip per chunk of
-// ~10 layers, under 2-3 waves per SIMD), and it guarded each of its 16 route loads and stores by
-// its own per-lane branch (~650 instructions per chunk: ~40 % of the kernel's).  Now the next
-// chunk is laid out and its routes and emission rows are loaded into registers while this chunk
-// runs (the chunk after that is described then), every load is unconditional (vit_load), and
-// staging writes every entry (past the chunk: routes / rows never selected -- a source past prevK
-// costs +inf, a target past K_B is discarded).  The layer's bookkeeping (chain starts, breaks,
-// the backtrace trigger, chain-start flags) is wave masks on the scalar unit.  C2: 0.65 -> 0.51 ms.
-template <bool TURN>
-struct VitRegs {
-  uint32_t rv[TURN ? 1 : kVitRoutes / 16];
-  double rd[TURN ? kVitRoutes / 16 : 1];
-  v3_f4 sv[4];
-};
+// K3 k_viterbi, the chunk pipeline.  The next chunk is laid out and its routes and emission rows
+// are loaded into registers while this chunk runs (the chunk after that is described then): loaded
+// at the chunk's start they cost one HBM round trip per chunk of ~10 layers, under 2-3 waves per
+// SIMD.  Every load is unconditional (vit_load) and staging writes every entry (past the chunk:
+// routes / rows never selected -- a source past prevK costs +inf, a target past K_B is discarded):
+// a per-lane branch around each of the 16 route loads and stores was ~650 instructions per chunk,
+// ~40 % of the kernel's.  The layer's bookkeeping (chain starts, breaks, the backtrace trigger,
+// chain-start flags) is wave masks on the scalar unit.  C2: 0.65 -> 0.51 ms.
+constexpr int kVitRegs = kVitRoutes / 16;   // route registers per lane for the next chunk
 
 struct VitChunk {
   uint32_t s0, C, nroutes, rbase;   // group-uniform (C: the smallest over the wave's live groups)
   uint32_t kb, rel;                 // lane j < C: K_B of layer s0 + j, its routes' offset in the chunk
   double gc;
 };
-
-// vit_raw for any trace: an empty trace (or a lane past the batch) reads layer 0 of the batch
-__device__ __forceinline__ VitLayerRaw vit_raw_any(const DevBatch& b, uint32_t o, uint32_t S, uint32_t s0, int j) {
-  const uint64_t lq = S ? o + min(s0 + (uint32_t)j, S - 1) : 0u;
-  const uint64_t lp = (S == 0 || lq == o) ? lq : lq - 1;
-  VitLayerRaw r;
-  r.kb = b.cand_n[lq];
-  r.ka = b.cand_n[lp];
-  r.off = b.trans_off[lq];
-  r.gc = b.gc[lq];
-  return r;
-}
 
 __device__ __forceinline__ VitChunk vit_layout(const VitLayerDesc& d, uint32_t s0, uint32_t S, int j, int gb) {
   // inclusive scan of the route counts inside the 16-lane row by DPP row_shr adds (bound_ctrl:
@@ -3754,44 +3718,23 @@ __device__ __forceinline__ VitChunk vit_layout(const VitLayerDesc& d, uint32_t s
 // <= 256 routes / 16 rows from there, inside the pools' slack (the route pools hold >= 1,024
 // entries past the batch's routes, the point arrays >= 64 points past its points: ensure /
 // ensure_trans_raw).  What lies past the chunk is staged but never selected.
-// Round 6: the loads past the chunk's routes and rows are clamped to its last
-// route / row (the same lines again) instead of reading kVitRoutes routes and 16 rows whatever the
-// chunk holds -- C2 K3 moved 1.73x its algorithmic bytes.  Still one unconditional load per slot
-// (a v_min, no branch, no register merge).
-#ifndef RM_VIT_CLAMP
-#define RM_VIT_CLAMP 0
-#endif
+// (Clamping them to the chunk's last route / row saved a quarter of K3's bytes and cost time: the
+// clamp's v_min per load lands in the issue-bound layer loop.  DESIGN.md, "K3 chunk loads".)
 template <bool TURN>
-__device__ __forceinline__ void vit_load(const DevBatch& b, uint32_t o, const VitChunk& c, int j, VitRegs<TURN>& r) {
-#if RM_VIT_CLAMP
-  const uint32_t rl = c.nroutes ? c.nroutes - 1u : 0u;                  // the chunk's last route
-  const uint32_t sl = c.C ? c.C * (kMaxCand / 4) - 1u : 0u;             // ... and its last row quarter
-  if constexpr (TURN) {
-    const double* rp = b.route_d + c.rbase;
-#pragma unroll
-    for (int x = 0; x < kVitRoutes / 16; ++x) r.rd[x] = rp[min((uint32_t)(16 * x + j), rl)];
-  } else {
-    const uint32_t* rp = b.route + c.rbase;
-#pragma unroll
-    for (int x = 0; x < kVitRoutes / 16; ++x) r.rv[x] = rp[min((uint32_t)(16 * x + j), rl)];
-  }
-  const v3_f4* src = reinterpret_cast<const v3_f4*>(b.cand_sq) + (uint64_t)(c.C ? o + c.s0 : 0u) * (kMaxCand / 4);
-#pragma unroll
-  for (int x = 0; x < 4; ++x) r.sv[x] = src[min((uint32_t)(16 * x + j), sl)];
-#else
+__device__ __forceinline__ void vit_load(const DevBatch& b, uint32_t o, const VitChunk& c, int j,
+                                         VitRegs<TURN, kVitRegs, 4>& r) {
   if constexpr (TURN) {
     const double* rp = b.route_d + c.rbase + j;
 #pragma unroll
-    for (int x = 0; x < kVitRoutes / 16; ++x) r.rd[x] = rp[16 * x];
+    for (int x = 0; x < kVitRegs; ++x) r.rd[x] = rp[16 * x];
   } else {
     const uint32_t* rp = b.route + c.rbase + j;
 #pragma unroll
-    for (int x = 0; x < kVitRoutes / 16; ++x) r.rv[x] = rp[16 * x];
+    for (int x = 0; x < kVitRegs; ++x) r.rv[x] = rp[16 * x];
   }
   const v3_f4* src = reinterpret_cast<const v3_f4*>(b.cand_sq) + (uint64_t)(c.C ? o + c.s0 : 0u) * (kMaxCand / 4) + j;
 #pragma unroll
   for (int x = 0; x < 4; ++x) r.sv[x] = src[16 * x];
-#endif
 }
 
 template <bool TURN>
@@ -3808,27 +3751,26 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT_
   const double inv2s2 = 1.0 / (2.0 * (double)op.sigma_z * (double)op.sigma_z);
   const double inv_beta = 1.0 / (double)op.beta;
   const double brk = (double)op.breakage_distance;
-  const double INF = __longlong_as_double(0x7ff0000000000000ll);
   // wave masks (all lanes of a group alike): the group's previous layer had candidates (pok)
   unsigned long long pok = 0ull;
   uint32_t prevK = 0;
-  double cj = INF;   // cost of candidate j of the previous layer
+  double cj = kInfD;   // cost of candidate j of the previous layer
   bool fok = false;  // the trace has ended with a chain (fK candidates, costs fcj) still to trace back
   uint32_t fK = 0;
-  double fcj = INF;
+  double fcj = kInfD;
   // chunk 0: describe, lay out, load; then describe chunk 1
-  VitChunk cur = vit_layout(vit_cook(vit_raw_any(b, o, S, 0, j), S, 0, j), 0, S, j, gb);
-  VitRegs<TURN> rg;
+  VitChunk cur = vit_layout(vit_cook(vit_raw(b, o, S, 0, j), S, 0, j), 0, S, j, gb);
+  VitRegs<TURN, kVitRegs, 4> rg;
   vit_load<TURN>(b, o, cur, j, rg);
-  VitLayerRaw dn = vit_raw_any(b, o, S, cur.C, j);
+  VitLayerRaw dn = vit_raw(b, o, S, cur.C, j);
   for (;;) {
     if (__ballot(cur.s0 < S) == 0ull) break;
     const uint32_t C = cur.C, nroutes = cur.nroutes, rbase = cur.rbase;
     // ---- this chunk -> LDS (its loads were issued a chunk ago); every entry written
 #pragma unroll
-    for (int x = 0; x < kVitRoutes / 16; ++x) {
+    for (int x = 0; x < kVitRegs; ++x) {
       if constexpr (TURN) gs.route_m[j + 16 * x] = rg.rd[x];
-      else gs.route_m[j + 16 * x] = rg.rv[x] == kRouteInvalid ? INF : (double)rg.rv[x] * 0.01;
+      else gs.route_m[j + 16 * x] = vit_metres(rg.rv[x]);
     }
 #pragma unroll
     for (int x = 0; x < 4; ++x) reinterpret_cast<v3_f4*>(&gs.sq[0][0])[j + 16 * x] = rg.sv[x];
@@ -3840,7 +3782,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT_
       const uint32_t s1 = cur.s0 + C;
       cur = vit_layout(vit_cook(dn, S, s1, j), s1, S, j, gb);
       vit_load<TURN>(b, o, cur, j, rg);
-      dn = vit_raw_any(b, o, S, s1 + cur.C, j);
+      dn = vit_raw(b, o, S, s1 + cur.C, j);
     }
     const uint32_t s0 = cur.s0 - C;   // (cur is the next chunk from here on)
     wave_sync();
@@ -3881,7 +3823,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT_
         const uint32_t tn = min(t + 1u, (uint32_t)kVitChunk - 1u);
         KBn = gs.kb[tn]; reln = gs.rel[tn]; gcn = gs.gc[tn]; sqn = gs.sq[tn][j];
       }
-      double best = INF;
+      double best = kInfD;
       int arg = -1;
       {
         const uint32_t jj = min((uint32_t)j, KB ? KB - 1u : 0u);
@@ -3922,28 +3864,21 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT_
       const unsigned long long kbm = __builtin_amdgcn_ballot_w64(KB == 0u);
       const unsigned long long btm = pok & (kbm | stm);   // the chain that ends at s - 1 is complete
       if (btm != 0ull) {
+        // btm is alike in the 16 lanes of a group (pok, kbm and stm all are), so whole groups
+        // enter the branch: the winner's shuffles read active lanes only
         if (__builtin_amdgcn_inverse_ballot_w64(btm)) {
           wave_sync();
-          vit_flush_m(b, gs, o + s0, t, j, csm);
-          backtrace_chain(b, gs, o, s0 + t - 1, prevK, j, cj);
+          vit_flush(b, gs.bpo, o + s0, t, j, csm);
+          vit_backtrace<16>(b, gs.bst, gs.ch, gs.walk, o, s0 + t - 1, vit_winner_shfl(cj, prevK, j), j);
         }
         // the backtrace staged through route_m: bring the chunk's routes back (rare path)
-        const uint32_t* rp = b.route + rbase;
-        const double* rdp = b.route_d ? b.route_d + rbase : nullptr;
-#pragma unroll
-        for (int x = 0; x < kVitRoutes / 16; ++x) {
-          const uint32_t q = (uint32_t)j + 16u * x;
-          if (q < nroutes) {
-            if constexpr (TURN) gs.route_m[q] = rdp[q];
-            else gs.route_m[q] = rp[q] == kRouteInvalid ? INF : (double)rp[q] * 0.01;
-          }
-        }
+        vit_restage<TURN, 16, kVitRegs>(gs.route_m, b, rbase, nroutes, j);
         wave_sync();
 #pragma unroll
         for (int x = 0; x < 8; ++x) rmn[x] = dpn[x * kbn];
       }
       const bool start = __builtin_amdgcn_inverse_ballot_w64(stm);
-      const double em = __builtin_amdgcn_inverse_ballot_w64(vm) ? (double)sqv * inv2s2 : INF;
+      const double em = __builtin_amdgcn_inverse_ballot_w64(vm) ? (double)sqv * inv2s2 : kInfD;
       const double nc = start ? em : best + em;
       const uint32_t bpj = __builtin_amdgcn_inverse_ballot_w64(stm | ~hm) ? 255u : (uint32_t)arg;
       reinterpret_cast<uint8_t*>(&gs.bpo[t])[j] = (uint8_t)bpj;
@@ -3953,10 +3888,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(RM_VIT_
       prevK = KB;
     }
     wave_sync();
-    vit_flush_m(b, gs, o + s0, C, j, csm);
+    vit_flush(b, gs.bpo, o + s0, C, j, csm);
     wave_sync();
   }
-  if (fok | __builtin_amdgcn_inverse_ballot_w64(pok)) backtrace_chain(b, gs, o, S - 1, fok ? fK : prevK, j, fok ? fcj : cj);
+  if (fok | __builtin_amdgcn_inverse_ballot_w64(pok))   // (both alike in a group's lanes: whole groups again)
+    vit_backtrace<16>(b, gs.bst, gs.ch, gs.walk, o, S - 1, vit_winner_shfl(fok ? fcj : cj, fok ? fK : prevK, j), j);
 }
 
 // Small batches (the coalesced service: tens to hundreds of traces) take the one-wave-per-trace

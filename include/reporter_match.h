@@ -288,7 +288,8 @@ int rm_runner_route_tiers(rm_runner* r, uint64_t out[10]);
  * way, [2] steady runs that did not launch the routes stage's hand-over tiers, [3] likewise the
  * path stage's */
 int rm_runner_run_stats(rm_runner* r, uint64_t out[4]);
-/* the steady scans' block bases on the host (test hook for rm_common.hpp scan_base_lane): part
+/* the steady scans' block bases on the host (test hook for rm_common.hpp scan_base_lane, which
+ * engine.hip's BaseBuckets sums over an apply block's lanes): part
  * holds nb pairs of block partials, base receives nb pairs of exclusive prefixes, formed as a
  * block of `lanes` threads forms them from the coarse buckets and its group's partials */
 int rm_scan_block_bases(const uint64_t* part, uint32_t nb, uint32_t lanes, uint64_t* base);

@@ -175,6 +175,15 @@ __device__ __forceinline__ bool small_abort(const DevBatch& b) {
          steady_abort(b);
 }
 
+// The same test on the host, from the control words and totals a run without read-backs brings
+// down at its end (Matcher::read_back): the device gated the run off, and the caller runs the
+// batch again the ordinary way.  (A steady run adds its own terms, as steady_abort and the skipped
+// tiers' gates do above: Matcher::run_steady.)
+static bool small_aborted(const DevBatch& b, const uint32_t* ctl, const unsigned long long* tot) {
+  return (ctl[kCtlErr] & kErrPathOverflow) != 0u ||
+         ((b.gate & kGateGlobal) && (ctl[kCtlWaveToGlobal] | ctl[kCtlPathsWaveToGlobal]) != 0u) || tot[2] > b.seg_cap;
+}
+
 // A failure that belongs to one trajectory (too many roads in a radius, a search beyond every
 // tier's capacity, a path that cannot be rebuilt) marks that trace only, as the reference fails
 // one request (py/reporter_service.py:244-245) or skips one window (py/simple_reporter.py:169-173).
@@ -1046,28 +1055,31 @@ __global__ void __launch_bounds__(64) k_candidates_wave(DevGraph g, DevBatch b, 
 // ------------------------------------------------------------------------------------------
 // u64 sums of two per-lane values: the u32 exclusive scans that lay out routes and records
 // would wrap silently past 2^32, so the host checks these totals instead of off + cnt.
-// Each 256-thread block writes its pair of partials to part[2 * block]; k_scan_parts turns
-// them into block offsets and totals.  (One same-address u64 atomic per block serialises at
-// ~12 ns across the 8 XCDs: 23 k blocks of C2 cost 0.57 ms that way.)
-__device__ __forceinline__ void block_sum2_u64(unsigned long long a, unsigned long long c, unsigned long long* part) {
-  __shared__ unsigned long long sa[4], sc[4];
+// Each 256-thread block writes its pair of partials to part[2 * block]; the layout scans' middle
+// and apply passes (below) turn them into block offsets and totals.  (One same-address u64 atomic
+// per block serialises at ~12 ns across the 8 XCDs: 23 k blocks of C2 cost 0.57 ms that way.)
+// block_sum_pair: the sums over a block of 256 of a u64 pair, in every lane (it holds a barrier).
+__device__ __forceinline__ ulonglong2 block_sum_pair(unsigned long long a, unsigned long long c) {
+  __shared__ unsigned long long s[4][2];
 #pragma unroll
   for (int d = 32; d > 0; d >>= 1) {
-    a += __shfl_down(a, d, 64);
-    c += __shfl_down(c, d, 64);
+    a += __shfl_down(a, d, 64); c += __shfl_down(c, d, 64);
   }
-  if ((threadIdx.x & 63) == 0) { sa[threadIdx.x >> 6] = a; sc[threadIdx.x >> 6] = c; }
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { s[wv][0] = a; s[wv][1] = c; }
   __syncthreads();
-  if (threadIdx.x == 0)
-    reinterpret_cast<ulonglong2*>(part)[blockIdx.x] =
-        make_ulonglong2(sa[0] + sa[1] + sa[2] + sa[3], sc[0] + sc[1] + sc[2] + sc[3]);
+  return make_ulonglong2(s[0][0] + s[1][0] + s[2][0] + s[3][0], s[0][1] + s[1][1] + s[2][1] + s[3][1]);
+}
+__device__ __forceinline__ void block_sum2_u64(unsigned long long a, unsigned long long c, unsigned long long* part) {
+  const ulonglong2 s = block_sum_pair(a, c);
+  if (threadIdx.x == 0) reinterpret_cast<ulonglong2*>(part)[blockIdx.x] = s;
 }
 
 // Exclusive scans of per-slot counts from the block partials the counting kernels already
-// produce (k_trans_count: pairs per 256 slots, k_sum_u64: per 1024): k_scan_parts turns the
-// partial pairs into block offsets in place (one block) and writes the u64 totals; the apply
-// kernels scan each block locally and add its offset.  Three short passes instead of a
-// generic device scan per array.
+// produce (k_trans_count: pairs per 256 slots, k_sum_u64: per 1024): on an ordinary run
+// k_scan_parts turns the partial pairs into block offsets in place (one block) and writes the u64
+// totals; the apply kernels (k_trans_apply, k_path_apply) scan each block locally and add its
+// offset.  Three short passes instead of a generic device scan per array.
 __device__ __forceinline__ void block_excl_scan2(unsigned long long a, unsigned long long c, unsigned long long& ea,
                                                  unsigned long long& ec, unsigned long long* sa, unsigned long long* sc,
                                                  int nwaves) {
@@ -1163,48 +1175,6 @@ __global__ void __launch_bounds__(1024) k_scan_parts(unsigned long long* part, u
   if (threadIdx.x == 1023) { out[0] = ea; out[1] = ec; }
 }
 
-// one count of each array per thread, blocks of 256 (k_trans_count's partials)
-__global__ void __launch_bounds__(256) k_scan_apply2(const uint32_t* a, const uint32_t* c, uint64_t n,
-                                                     const unsigned long long* part, uint32_t* ao, uint32_t* co) {
-  // (block256_excl_scan_u32 written out: through the helper the two stores' addresses are formed
-  // together, at two more VGPRs)
-  __shared__ uint32_t sa[4], sc[4];
-  const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const ulonglong2 base = reinterpret_cast<const ulonglong2*>(part)[blockIdx.x];
-  const uint32_t va = p < n ? a[p] : 0u, vc = p < n ? c[p] : 0u;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  uint32_t ia = va, ic = vc;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t ta = __shfl_up(ia, d, 64), tc = __shfl_up(ic, d, 64);
-    if (lane >= d) { ia += ta; ic += tc; }
-  }
-  if (lane == 63) { sa[wv] = ia; sc[wv] = ic; }
-  __syncthreads();
-  uint32_t ba = 0, bc = 0;
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    ba += w < wv ? sa[w] : 0u;
-    bc += w < wv ? sc[w] : 0u;
-  }
-  if (p < n) {
-    ao[p] = (uint32_t)base.x + ba + ia - va;
-    co[p] = (uint32_t)base.y + bc + ic - vc;
-  }
-}
-
-// four counts per thread, blocks of 256 (k_sum_u64's partials)
-__global__ void __launch_bounds__(256) k_scan_apply4(const uint32_t* a, uint64_t n, const unsigned long long* part,
-                                                     uint32_t* ao) {
-  __shared__ unsigned long long sa[4], sc[4];
-  const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
-  uint32_t v[4];
-  load_counts4(a, i, n, v);
-  unsigned long long ea, ec;
-  block_excl_scan2((unsigned long long)v[0] + v[1] + v[2] + v[3], 0ull, ea, ec, sa, sc, 4);
-  store_offsets4(ao, i, n, (uint32_t)(part[2 * blockIdx.x] + ea), v);
-}
-
 __global__ void __launch_bounds__(256) k_perm_src_count(DevBatch b, uint32_t* pcnt, unsigned long long* part) {
   const uint64_t r = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   uint32_t c = 0;
@@ -1264,87 +1234,28 @@ __global__ void k_src_items(DevBatch b) {
   for (uint32_t i = 0; i < n; ++i) b.src_item[at + i] = (uint32_t)p;
 }
 
-// ---- small runs (Matcher::run_small): one kernel in place of k_scan_parts + an apply pass (+
-// k_src_items / k_rec_slot).  A small batch has at most a few hundred partials, so each block
-// folds the partials before its own (and block 0 all of them, for the totals) instead of
-// waiting for a separate one-block scan: three launches fewer per stage, ~5 us each.
-__device__ __forceinline__ void block_prefix_parts(const unsigned long long* part, uint32_t nb, uint32_t upto,
-                                                   unsigned long long* pre, unsigned long long* all) {
-  __shared__ unsigned long long s[4][4];
-  unsigned long long a = 0, c = 0, ta = 0, tc = 0;
-  const ulonglong2* pp = reinterpret_cast<const ulonglong2*>(part);
-  for (uint32_t q = threadIdx.x; q < nb; q += blockDim.x) {
-    const ulonglong2 v = pp[q];
-    ta += v.x; tc += v.y;
-    if (q < upto) { a += v.x; c += v.y; }
-  }
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    a += __shfl_down(a, d, 64); c += __shfl_down(c, d, 64);
-    ta += __shfl_down(ta, d, 64); tc += __shfl_down(tc, d, 64);
-  }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s[wv][0] = a; s[wv][1] = c; s[wv][2] = ta; s[wv][3] = tc; }
-  __syncthreads();
-  for (int j = 0; j < 4; ++j) {
-    unsigned long long x = 0;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) x += s[w][j];
-    if (j < 2) pre[j] = x; else all[j - 2] = x;
-  }
-}
-
-// k_scan_apply2 + k_src_items over k_trans_count's partials (blocks of 256 pairs); totals to tot[0..1]
-__global__ void __launch_bounds__(256) k_trans_apply_small(DevBatch b, const unsigned long long* part, uint32_t nb,
-                                                           unsigned long long* tot) {
-  unsigned long long pre[2], all[2];
-  block_prefix_parts(part, nb, blockIdx.x, pre, all);
-  if (blockIdx.x == 0 && threadIdx.x == 0) { tot[0] = all[0]; tot[1] = all[1]; }
-  const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-  const uint32_t v[2] = {p < b.P ? b.trans_cnt[p] : 0u, p < b.P ? b.src_cnt[p] : 0u};
-  uint32_t e[2];
-  block256_excl_scan_u32(v, e);
-  if (p < b.P) {
-    const uint32_t at = (uint32_t)pre[1] + e[1];
-    b.trans_off[p] = (uint32_t)pre[0] + e[0];
-    b.src_off[p] = at;
-    for (uint32_t i = 0; i < v[1]; ++i) b.src_item[at + i] = (uint32_t)p;
-  }
-}
-
-// k_scan_apply4 + k_rec_slot over k_sum_u64's partials (blocks of 1024 slots); total to tot[2].
-// Records past seg_cap are not written (the run is then gated off: small_abort).
-__global__ void __launch_bounds__(256) k_path_apply_small(DevBatch b, const unsigned long long* part, uint32_t nb,
-                                                          unsigned long long* tot, uint32_t* rec_slot) {
-  unsigned long long pre[2], all[2];
-  block_prefix_parts(part, nb, blockIdx.x, pre, all);
-  if (blockIdx.x == 0 && threadIdx.x == 0) tot[2] = all[0];
-  __shared__ unsigned long long sa[4], sc[4];
-  const uint64_t n = b.P;
-  const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
-  uint32_t v[4] = {0u, 0u, 0u, 0u};
-  for (uint64_t x = i; x < n && x < i + 4; ++x) v[x - i] = b.path_cnt[x];
-  unsigned long long ea, ec;
-  block_excl_scan2((unsigned long long)v[0] + v[1] + v[2] + v[3], 0ull, ea, ec, sa, sc, 4);
-  uint64_t o = pre[0] + ea;
-  for (uint64_t x = i; x < n && x < i + 4; ++x) {
-    b.trav_off[x] = (uint32_t)o;
-    const uint32_t c = v[x - i];
-    for (uint32_t q = 0; q < c; ++q)
-      if (o + q < b.seg_cap) rec_slot[o + q] = (uint32_t)x;
-    o += c;
-  }
-}
-
-// ---- steady runs (Matcher::run_steady): the same two fused passes for a batch of any size.  A
-// block cannot fold 23 k partials, so k_scan_buckets first sums every kScanGroup partials into
-// one coarse bucket (one wave per bucket, every bucket written: ~3 us on C2's 367 buckets) and an
-// apply block's base is the buckets before its group plus the partials before it inside the group
-// (rm_common.hpp scan_base_lane; C2: at most 366 + 63 pairs, L2-resident).  The last block's base
-// plus its own sum is the total.  No block waits for another, and the one-block k_scan_parts
-// between the passes (24 us of a C2 step, twice) and the separate fill passes (k_src_items,
-// k_rec_slot) are gone from the step.  (Adding the block sums into the buckets from the counting
-// kernels instead -- no middle launch -- cost more than it saved: 23 k u64 atomics on 367
-// addresses took k_trans_count from 62 to 82 us and k_sum_u64 from 6.9 to 13.)
+// ---- the apply passes of the two layout scans (Matcher::Stages::layout_trans / layout_records).
+// Every run lays out its pools by one rule: a block loads its slots' counts, finds its base (the
+// pair of sums of the partials before it), scans inside the block and stores base + exclusive sum.
+// Where the base comes from is all the three run paths differ in:
+//   BaseScanned (ordinary runs): k_scan_parts, one block, has already turned part[] into block
+//     offsets and written the totals, which the host reads back to size the pools; k_src_items /
+//     k_rec_slot fill them afterwards.
+//   BaseFolded (small runs): a small batch has at most 256 partials, so each block folds those
+//     before its own: no middle launch, ~5 us.
+//   BaseBuckets (steady runs): a block cannot fold 23 k partials, so k_scan_buckets first sums every
+//     kScanGroup partials into one coarse bucket (one wave per bucket, every bucket written: ~3 us
+//     on C2's 367 buckets) and a block's base is the buckets before its group plus the partials
+//     before it inside the group (rm_common.hpp scan_base_lane; C2: at most 366 + 63 pairs,
+//     L2-resident).  No block waits for another, and the one-block k_scan_parts between the passes
+//     (24 us of a C2 step, twice) is gone from the step.  (Adding the block sums into the buckets
+//     from the counting kernels instead -- no middle launch -- cost more than it saved: 23 k u64
+//     atomics on 367 addresses took k_trans_count from 62 to 82 us and k_sum_u64 from 6.9 to 13.)
+// The two bases that do not leave totals behind (kTotals) take them from the apply pass itself:
+// the last thread of the last block writes base + exclusive + own (lanes past P counted 0).  Those
+// two runs read nothing back before their end, so the same pass also fills the pool (FILL), each
+// write bounded by the pool's capacity: the totals come out of this launch, so the fill cannot be
+// gated by steady_abort / small_abort, which gate the run off right after it.
 __global__ void __launch_bounds__(256) k_scan_buckets(const unsigned long long* part, uint32_t nb, unsigned long long* bkt) {
   const uint32_t g = blockIdx.x * 4u + (threadIdx.x >> 6);   // one wave per bucket
   if (g >= scan_buckets(nb)) return;
@@ -1358,74 +1269,84 @@ __global__ void __launch_bounds__(256) k_scan_buckets(const unsigned long long* 
   if ((threadIdx.x & 63u) == 0) { bkt[2 * (uint64_t)g] = a; bkt[2 * (uint64_t)g + 1] = c; }
 }
 
-__device__ __forceinline__ void block_base_parts(const unsigned long long* part, const unsigned long long* bkt,
-                                                 unsigned long long* pre) {
-  __shared__ unsigned long long s[4][2];
-  unsigned long long a, c;
-  scan_base_lane(part, bkt, blockIdx.x, threadIdx.x, blockDim.x, a, c);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    a += __shfl_down(a, d, 64); c += __shfl_down(c, d, 64);
+struct BaseScanned {
+  static constexpr bool kTotals = false;
+  const unsigned long long* part;
+  __device__ __forceinline__ ulonglong2 operator()() const { return reinterpret_cast<const ulonglong2*>(part)[blockIdx.x]; }
+};
+struct BaseFolded {
+  static constexpr bool kTotals = true;
+  const unsigned long long* part;
+  __device__ __forceinline__ ulonglong2 operator()() const {
+    unsigned long long a = 0, c = 0;
+    for (uint32_t q = threadIdx.x; q < blockIdx.x; q += 256u) {
+      const ulonglong2 v = reinterpret_cast<const ulonglong2*>(part)[q];
+      a += v.x; c += v.y;
+    }
+    return block_sum_pair(a, c);
   }
-  const int wv = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { s[wv][0] = a; s[wv][1] = c; }
-  __syncthreads();
-  pre[0] = s[0][0] + s[1][0] + s[2][0] + s[3][0];
-  pre[1] = s[0][1] + s[1][1] + s[2][1] + s[3][1];
-}
+};
+struct BaseBuckets {
+  static constexpr bool kTotals = true;
+  const unsigned long long *part, *bkt;
+  __device__ __forceinline__ ulonglong2 operator()() const {
+    unsigned long long a, c;
+    scan_base_lane(part, bkt, blockIdx.x, threadIdx.x, 256u, a, c);
+    return block_sum_pair(a, c);
+  }
+};
 
-// k_scan_apply2 + k_src_items; totals to tot[0..1].  The totals come out of this launch, so the
-// item writes cannot be gated by steady_abort: each is bounded by src_cap instead (the run is
-// then gated off after this kernel, and the host runs the batch again the ordinary way).
-__global__ void __launch_bounds__(256) k_trans_apply_steady(DevBatch b, const unsigned long long* part,
-                                                            const unsigned long long* bkt, unsigned long long* tot) {
+// trans_cnt / src_cnt -> trans_off / src_off (+ src_item), one slot per lane: blocks of 256, as
+// k_trans_count's partials; totals to tot[0..1]
+template <class Base, bool FILL>
+__global__ void __launch_bounds__(256) k_trans_apply(DevBatch b, Base base_of, unsigned long long* tot) {
   // (the counts first: their loads are in flight while the base is formed)
   const uint64_t p = (uint64_t)blockIdx.x * 256u + threadIdx.x;
   const uint32_t v[2] = {p < b.P ? b.trans_cnt[p] : 0u, p < b.P ? b.src_cnt[p] : 0u};
-  unsigned long long pre[2];
-  block_base_parts(part, bkt, pre);
+  const ulonglong2 base = base_of();
   uint32_t e[2];
   block256_excl_scan_u32(v, e);
   if (p < b.P) {
-    const unsigned long long at = pre[1] + e[1];
-    b.trans_off[p] = (uint32_t)(pre[0] + e[0]);
+    const unsigned long long at = base.y + e[1];
+    b.trans_off[p] = (uint32_t)(base.x + e[0]);
     b.src_off[p] = (uint32_t)at;
-    for (uint32_t i = 0; i < v[1]; ++i)
-      if (at + i < b.src_cap) b.src_item[at + i] = (uint32_t)p;
+    if constexpr (FILL)
+      for (uint32_t i = 0; i < v[1]; ++i)
+        if (at + i < b.src_cap) b.src_item[at + i] = (uint32_t)p;
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {   // (lanes past P counted 0)
-    tot[0] = pre[0] + e[0] + v[0];
-    tot[1] = pre[1] + e[1] + v[1];
+  if (Base::kTotals && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) {
+    tot[0] = base.x + e[0] + v[0];
+    tot[1] = base.y + e[1] + v[1];
   }
 }
 
-// k_scan_apply4 + k_rec_slot; total to tot[2].  Records past seg_cap are not written (the run is
-// then gated off: small_abort).
-__global__ void __launch_bounds__(256) k_path_apply_steady(DevBatch b, const unsigned long long* part,
-                                                           const unsigned long long* bkt, unsigned long long* tot,
-                                                           uint32_t* rec_slot) {
+// path_cnt -> trav_off (+ rec_slot), four slots per lane: blocks of 1024, as k_sum_u64's
+// partials; total to tot[2].  (A block's path counts may sum past 2^32: this scan runs on u64.)
+template <class Base, bool FILL>
+__global__ void __launch_bounds__(256) k_path_apply(DevBatch b, Base base_of, unsigned long long* tot, uint32_t* rec_slot) {
   __shared__ unsigned long long sa[4], sc[4];
   const uint64_t n = b.P;
   const uint64_t i = ((uint64_t)blockIdx.x * 256u + threadIdx.x) * 4u;
   // (the counts first: their loads are in flight while the base is formed)
   uint32_t v[4];
   load_counts4(b.path_cnt, i, n, v);
-  unsigned long long pre[2];
-  block_base_parts(part, bkt, pre);
+  const ulonglong2 pre = base_of();
   const unsigned long long mine = (unsigned long long)v[0] + v[1] + v[2] + v[3];
   unsigned long long ea, ec;
   block_excl_scan2(mine, 0ull, ea, ec, sa, sc, 4);
-  const unsigned long long base = pre[0] + ea;
+  const unsigned long long base = pre.x + ea;
   store_offsets4(b.trav_off, i, n, (uint32_t)base, v);
-  unsigned long long o = base;
+  if constexpr (FILL) {
+    unsigned long long o = base;
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t c = v[j];   // (0 past n)
-    for (uint32_t q = 0; q < c; ++q)
-      if (o + q < b.seg_cap) rec_slot[o + q] = (uint32_t)(i + j);
-    o += c;
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t c = v[j];   // (0 past n)
+      for (uint32_t q = 0; q < c; ++q)
+        if (o + q < b.seg_cap) rec_slot[o + q] = (uint32_t)(i + j);
+      o += c;
+    }
   }
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) tot[2] = base + mine;
+  if (Base::kTotals && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) tot[2] = base + mine;
 }
 
 // Compaction for the downloads: trace k's records [base[k], base[k] + cnt[k]) of a per-trace
@@ -5873,8 +5794,14 @@ void Matcher::zero_hist(const RunParams& rp) {
 }
 
 // The three ways to run a batch -- run_small, run_steady and the ordinary rest of run_device --
-// launch the same stages through Matcher::Stages (k1, routes, paths, k4) and differ in
-// this plan (and in their scans and read-backs, which stay with them: DESIGN.md §5).
+// launch the same stages through Matcher::Stages (k1, layout_trans, routes, paths,
+// layout_records, k4) and differ in this plan (and in their read-backs: DESIGN.md §5).
+// How a run's two layout scans find a block's base (the apply passes above):
+enum ScanScheme : int {
+  kScanReadBack,   // k_scan_parts, then the host reads the totals back and the fills run later
+  kScanFolded,     // small runs: each apply block folds the partials before it
+  kScanBuckets,    // steady runs: k_scan_buckets, then the buckets and the partials inside the group
+};
 // A stage's hand-over tiers (kTierLane: the lane tier over the ball tier's hand-overs): each one's
 // full grid, the link it reads and the items a block takes per pass of its grid-stride loop
 enum Tier : int { kTierLane = 0, kTierReg2, kTierGrp, kTierWave512, kTierWave4096, kTiers };
@@ -5887,7 +5814,8 @@ struct TierGrids {
   uint32_t grid[kTiers];   // (kTierLane: at most the stage's lane grid)
 };
 struct LaunchPlan {
-  bool k1_wave_all;        // K1 takes every state a wave each: no lane tier
+  ScanScheme scan;
+  bool k1_wave_all;        // K1 takes every state a wave each: no lane tier (small runs up to kSmallWaveK1 points)
   uint32_t k1_wave_grid;
   // K2's item count when the host has read it back (k_src_items then runs first); kNone: the
   // kernels read tot[1] on the device, and the scan's fused apply pass has written the items
@@ -5921,10 +5849,14 @@ struct Matcher::Stages {
   LaunchPlan pl;
   void attach_pools(DevBatch& v) const;
   void k1(const DevBatch& v) const;
+  void scan_middle(uint32_t nb, unsigned long long* tot) const;
+  void layout_trans(const DevBatch& v) const;
   void routes(const DevBatch& v) const;
   void paths(const DevBatch& v) const;
   template <class St> void search_tiers(const DevBatch& v, const TierGrids& tg) const;
+  void layout_records(const DevBatch& v) const;
   void k4(const RunParams& rp, const DevBatch& v, uint32_t total) const;
+  void run_to_end(const RunParams& rp, const DevBatch& v) const;
 };
 
 // the pools a run (re)allocates, attached to its view: the ordinary path calls this again after
@@ -5951,6 +5883,43 @@ void Matcher::Stages::k1(const DevBatch& v) const {
     hipLaunchKernelGGL(k_candidates_wave, dim3(pl.k1_wave_grid), dim3(64), 0, st, gk, v, 0);
   }
   m.toc(kKCandidates);
+}
+
+// the middle pass of a layout scan over nb block partials: the one-block scan that also writes the
+// totals, or the coarse buckets; none where the apply blocks fold the partials themselves
+void Matcher::Stages::scan_middle(uint32_t nb, unsigned long long* tot) const {
+  const Workspace& w = m.ws_;
+  if (pl.scan == kScanReadBack)
+    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, m.stream_, w.tot_part, nb, tot);
+  else if (pl.scan == kScanBuckets)
+    hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(nb) + 3) / 4), dim3(256), 0, m.stream_,
+                       (const unsigned long long*)w.tot_part, nb, w.scan_bkt);
+}
+
+// the transitions' layout: trans_off / src_off from the counts (totals: tot[0..1]) and, unless the
+// host reads the totals back first, K2's item list
+void Matcher::Stages::layout_trans(const DevBatch& v) const {
+  const Workspace& w = m.ws_;
+  hipStream_t st = m.stream_;
+  const dim3 grid((uint32_t)((v.P + 255) / 256)), block(256);
+  const unsigned long long* part = w.tot_part;
+  m.tic(kKScan);
+  hipLaunchKernelGGL(k_trans_count, grid, block, 0, st, v, w.tot_part);
+  scan_middle(grid.x, w.tot64);
+  switch (pl.scan) {
+    case kScanReadBack: hipLaunchKernelGGL((k_trans_apply<BaseScanned, false>), grid, block, 0, st, v, BaseScanned{part}, w.tot64); break;
+    case kScanFolded: hipLaunchKernelGGL((k_trans_apply<BaseFolded, true>), grid, block, 0, st, v, BaseFolded{part}, w.tot64); break;
+    case kScanBuckets:
+      hipLaunchKernelGGL((k_trans_apply<BaseBuckets, true>), grid, block, 0, st, v, BaseBuckets{part, w.scan_bkt}, w.tot64);
+      break;
+  }
+  if (v.perm) {   // K2 items in locality order: src_off from a scan of the counts in perm order (ordinary runs only)
+    hipLaunchKernelGGL(k_perm_src_count, grid, block, 0, st, v, w.pcnt, w.tot_part);
+    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, grid.x, w.tot64 + 2);
+    hipLaunchKernelGGL(k_scan_apply_perm, grid, block, 0, st, (const uint32_t*)w.pcnt, v.P, part, (const uint32_t*)w.perm,
+                       w.src_off);
+  }
+  m.toc(kKScan);
 }
 
 // the routes stage (K2).  The ball tiers run when some mode of the batch has route balls; items
@@ -6019,6 +5988,28 @@ void Matcher::Stages::paths(const DevBatch& v) const {
   m.toc(kKPaths);
 }
 
+// the records' layout, part of the segments stage: trav_off from a scan of path_cnt (0 for slots
+// without a chosen transition; total: tot[2]) and, unless the host reads the total back first, rec_slot
+void Matcher::Stages::layout_records(const DevBatch& v) const {
+  const Workspace& w = m.ws_;
+  hipStream_t st = m.stream_;
+  const dim3 grid((uint32_t)((v.P + 1023) / 1024)), block(256);   // k_sum_u64: four counts per lane
+  const unsigned long long* part = w.tot_part;
+  hipLaunchKernelGGL(k_sum_u64, grid, block, 0, st, w.path_cnt, v.P, w.tot_part);
+  scan_middle(grid.x, w.tot64 + 2);
+  switch (pl.scan) {
+    case kScanReadBack:
+      hipLaunchKernelGGL((k_path_apply<BaseScanned, false>), grid, block, 0, st, v, BaseScanned{part}, w.tot64, w.rec_slot);
+      break;
+    case kScanFolded:
+      hipLaunchKernelGGL((k_path_apply<BaseFolded, true>), grid, block, 0, st, v, BaseFolded{part}, w.tot64, w.rec_slot);
+      break;
+    case kScanBuckets:
+      hipLaunchKernelGGL((k_path_apply<BaseBuckets, true>), grid, block, 0, st, v, BaseBuckets{part, w.scan_bkt}, w.tot64, w.rec_slot);
+      break;
+  }
+}
+
 // K4 and the report.  total: the traversal records when the host has read them back (k_rec_slot
 // then runs first); kNone: K4 reads tot[2], and the scan's fused apply pass has filled rec_slot
 void Matcher::Stages::k4(const RunParams& rp, const DevBatch& v, uint32_t total) const {
@@ -6027,6 +6018,25 @@ void Matcher::Stages::k4(const RunParams& rp, const DevBatch& v, uint32_t total)
   if (total != kNone)
     hipLaunchKernelGGL(k_rec_slot, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, v, m.ws_.rec_slot);
   hipLaunchKernelGGL(k_seg_wave, dim3(v.T), dim3(64), 0, st, g, v, (const uint32_t*)m.ws_.rec_slot, total, report_args(rp));
+}
+
+// A run that reads nothing back before its end (run_small, run_steady), launch for launch
+void Matcher::Stages::run_to_end(const RunParams& rp, const DevBatch& v) const {
+  hipStream_t st = m.stream_;
+  m.tic(kKStates);
+  hipLaunchKernelGGL(k_states, dim3(v.T), dim3(64), 0, st, v);
+  m.toc(kKStates);
+  k1(v);
+  layout_trans(v);
+  routes(v);
+  m.tic(kKViterbi);
+  launch_viterbi(v.T, st, v);
+  m.toc(kKViterbi);
+  paths(v);
+  m.tic(kKSegments);
+  layout_records(v);
+  k4(rp, v, kNone);
+  m.toc(kKSegments);
 }
 
 // The end of every run: the control words come down (with the totals, for a run that has not read
@@ -6064,9 +6074,8 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
   s.attach_pools(v);
   v.gate = kGateRecords | (w.gsearch ? 0u : kGateGlobal);
   locality_used_ = false;   // a few thousand points: nothing to gain from the region order
-  const uint32_t count_grid = (uint32_t)((P + 255) / 256);
-  const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);
   LaunchPlan& pl = s.pl;
+  pl.scan = kScanFolded;
   pl.k1_wave_all = P <= kSmallWaveK1;   // one wave per state
   pl.k1_wave_grid = pl.k1_wave_all ? (uint32_t)P : tier_grid(P, 2048);
   pl.n_src = kNone;
@@ -6075,27 +6084,7 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
   const char* sc_env = std::getenv("RM_SMALL_SHORT_CHAIN");   // (read per run: tests switch it)
   pl.short_chain = route_balls(g) && !(sc_env && *sc_env == '0');
   pl.routes = pl.paths = tier_grids(P);
-
-  tic(kKStates);
-  hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
-  toc(kKStates);
-  s.k1(v);
-  tic(kKScan);
-  hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
-  hipLaunchKernelGGL(k_trans_apply_small, dim3(count_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
-                     count_grid, w.tot64);
-  toc(kKScan);
-  s.routes(v);
-  tic(kKViterbi);
-  launch_viterbi(T, st, v);
-  toc(kKViterbi);
-  s.paths(v);
-  tic(kKSegments);
-  hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
-  hipLaunchKernelGGL(k_path_apply_small, dim3(sum_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
-                     sum_grid, w.tot64, w.rec_slot);
-  s.k4(rp, v, kNone);
-  toc(kKSegments);
+  s.run_to_end(rp, v);
   // the reply's segments, compacted per trace on the device (get_segments then copies them down)
   constexpr uint32_t kSegWords = sizeof(SegmentRec) / 8;
   const size_t offb = ((T + 1) * 4ull + 7) & ~(size_t)7;
@@ -6117,9 +6106,7 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
     RM_HIP(hipMemcpyAsync(hoff_, d_off, (T + 1) * 4ull, hipMemcpyDeviceToHost, st));
   }
   read_back(true);
-  if ((hctl_[kCtlErr] & kErrPathOverflow) || (!w.gsearch && (hctl_[kCtlWaveToGlobal] | hctl_[kCtlPathsWaveToGlobal])) ||
-      htot()[2] > v.seg_cap)
-    return false;
+  if (small_aborted(v, hctl_, htot())) return false;
   seg_prefetched_ = prefetch;
   finish_run(rp);
   return true;
@@ -6138,7 +6125,6 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   const uint32_t T = n_traces_;
   const uint64_t P = n_points_;
   Workspace& w = ws_;
-  hipStream_t st = stream_;
   if (turn_mask_) ensure_turns();
   Stages s{*this, g, {}};
   DevBatch v = make_view(w, in_, T, P);
@@ -6148,8 +6134,6 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   v.src_cap = src_cover;
   v.gate = kGateRecords | (w.gsearch ? 0u : kGateGlobal) | kGateSteady;
   locality_used_ = false;
-  const uint32_t count_grid = (uint32_t)((P + 255) / 256);
-  const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);
   // A stage's five hand-over tiers are empty launches (~4.7 us each on the in-order stream) when
   // its ball tier hands nothing over, so they are not launched once the matcher's last two runs
   // ended with that stage's lists empty.  The prediction is checked on the device every run: items
@@ -6168,13 +6152,12 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   // the hand-over tiers' grids from the previous run's list lengths (each is a grid-stride loop:
   // any grid is correct, and a list that grew runs on fewer blocks than it could): mostly empty
   // launches of 64 blocks instead of up to 4,096
-  static const bool prev_grids = [] { const char* e = std::getenv("RM_STEADY_GRIDS"); return !(e && *e == '0'); }();   // A/B
   const auto sgrid = [&](uint32_t full, CtlWord word, uint32_t per_block) {
-    if (!prev_grids) return (uint32_t)(full == 2048u ? 2048u : tier_grid(P, full));
     const uint64_t want = 4ull * (((uint64_t)steady_ctl_[word] + per_block - 1) / per_block);
     return (uint32_t)std::min<uint64_t>(tier_grid(P, full), std::max<uint64_t>(64u, want));
   };
   LaunchPlan& pl = s.pl;
+  pl.scan = kScanBuckets;
   pl.k1_wave_all = false;
   pl.k1_wave_grid = sgrid(2048, kCtlK1LaneToWave, 1);
   pl.n_src = kNone;
@@ -6187,35 +6170,10 @@ bool Matcher::run_steady(const RunParams& rp, const DevGraph& g) {
   };
   pl.routes = stage_grids(!skip_routes, RoutesStage{});
   pl.paths = stage_grids(!skip_paths, PathsStage{});
-
-  tic(kKStates);
-  hipLaunchKernelGGL(k_states, dim3(T), dim3(64), 0, st, v);
-  toc(kKStates);
-  s.k1(v);
-  tic(kKScan);
-  hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
-  hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(count_grid) + 3) / 4), dim3(256), 0, st,
-                     (const unsigned long long*)w.tot_part, count_grid, w.scan_bkt);
-  hipLaunchKernelGGL(k_trans_apply_steady, dim3(count_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
-                     (const unsigned long long*)w.scan_bkt, w.tot64);
-  toc(kKScan);
-  s.routes(v);
-  tic(kKViterbi);
-  launch_viterbi(T, st, v);
-  toc(kKViterbi);
-  s.paths(v);
-  tic(kKSegments);
-  hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
-  hipLaunchKernelGGL(k_scan_buckets, dim3((scan_buckets(sum_grid) + 3) / 4), dim3(256), 0, st,
-                     (const unsigned long long*)w.tot_part, sum_grid, w.scan_bkt);
-  hipLaunchKernelGGL(k_path_apply_steady, dim3(sum_grid), dim3(256), 0, st, v, (const unsigned long long*)w.tot_part,
-                     (const unsigned long long*)w.scan_bkt, w.tot64, w.rec_slot);
-  s.k4(rp, v, kNone);
-  toc(kKSegments);
+  s.run_to_end(rp, v);
   read_back(true);
   const unsigned long long* tot = htot();
-  if (tot[0] > w.cap_trans || tot[1] > src_cover || (hctl_[kCtlErr] & kErrPathOverflow) ||
-      (!w.gsearch && (hctl_[kCtlWaveToGlobal] | hctl_[kCtlPathsWaveToGlobal])) || tot[2] > v.seg_cap ||
+  if (small_aborted(v, hctl_, tot) || tot[0] > w.cap_trans || tot[1] > src_cover ||
       (skip_routes && hctl_[kCtlBallToSearch]) || (skip_paths && hctl_[kCtlPathsBallToSearch])) {
     ++run_stats_[1];
     return false;
@@ -6255,13 +6213,11 @@ void Matcher::run_device(const RunParams& rp) {
   }
   // (k_states zeroes the control words and the per-trace error bits)
   DevBatch v = make_view(w, in_, T, P);
-  const uint32_t count_grid = (uint32_t)((P + 255) / 256);
-  const uint32_t sum_grid = (uint32_t)((P + 1023) / 1024);   // k_sum_u64: four counts per lane
-  static const bool k1_wave_all = [] { const char* e = std::getenv("RM_K1_WAVE_ALL"); return e && *e == '1'; }();
   Stages s{*this, g, {}};
   LaunchPlan& pl = s.pl;
-  pl.k1_wave_all = k1_wave_all;   // A/B: every state in the wave tier
-  pl.k1_wave_grid = k1_wave_all ? (uint32_t)std::min<uint64_t>(P, 1u << 20) : 2048u;
+  pl.scan = kScanReadBack;
+  pl.k1_wave_all = false;
+  pl.k1_wave_grid = 2048u;
   pl.short_chain = false;
   // the search tiers' grids (grid-stride over lists the host does not read) shrink with the batch:
   // a coalesced service batch of ~15 k points launches them mostly empty
@@ -6285,18 +6241,7 @@ void Matcher::run_device(const RunParams& rp) {
     toc(kKLocality);
   }
   s.k1(v);
-  tic(kKScan);
-  hipLaunchKernelGGL(k_trans_count, dim3(count_grid), dim3(256), 0, st, v, w.tot_part);
-  hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, count_grid, w.tot64);
-  hipLaunchKernelGGL(k_scan_apply2, dim3(count_grid), dim3(256), 0, st, (const uint32_t*)w.trans_cnt,
-                     (const uint32_t*)w.src_cnt, P, (const unsigned long long*)w.tot_part, w.trans_off, w.src_off);
-  if (v.perm) {   // K2 items in locality order: src_off from a scan of the counts in perm order
-    hipLaunchKernelGGL(k_perm_src_count, dim3(count_grid), dim3(256), 0, st, v, w.pcnt, w.tot_part);
-    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, count_grid, w.tot64 + 2);
-    hipLaunchKernelGGL(k_scan_apply_perm, dim3(count_grid), dim3(256), 0, st, (const uint32_t*)w.pcnt, P,
-                       (const unsigned long long*)w.tot_part, (const uint32_t*)w.perm, w.src_off);
-  }
-  toc(kKScan);
+  s.layout_trans(v);
   unsigned long long* tot = htot();
   RM_HIP(hipMemcpyAsync(tot, w.tot64, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   RM_HIP(hipStreamSynchronize(st));
@@ -6324,13 +6269,6 @@ void Matcher::run_device(const RunParams& rp) {
     RM_HIP(hipMemcpyAsync(w.ctl + kCtlErr, &flags, sizeof(uint32_t), hipMemcpyHostToDevice, st));
     RM_HIP(hipStreamSynchronize(st));
   };
-  // traversal records are laid out by a scan of path_cnt (0 for slots without a chosen transition)
-  const auto scan_records = [&] {
-    hipLaunchKernelGGL(k_sum_u64, dim3(sum_grid), dim3(256), 0, st, w.path_cnt, P, w.tot_part);
-    hipLaunchKernelGGL(k_scan_parts, dim3(1), dim3(1024), 0, st, w.tot_part, sum_grid, w.tot64 + 2);
-    hipLaunchKernelGGL(k_scan_apply4, dim3(sum_grid), dim3(256), 0, st, (const uint32_t*)w.path_cnt, P,
-                       (const unsigned long long*)w.tot_part, w.trav_off);
-  };
   const auto read_records = [&] {
     RM_HIP(hipMemcpyAsync(tot + 2, w.tot64 + 2, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     read_ctl();
@@ -6340,7 +6278,7 @@ void Matcher::run_device(const RunParams& rp) {
       zero_ctl({pw(kLinkBallToSearch), pw(kLinkWaveToGlobal), pw(kLinkGroupToWave512), pw(kLinkWave512ToWave4096)});
     s.paths(v);
     tic(kKSegments);
-    scan_records();
+    s.layout_records(v);
     toc(kKSegments);
     read_records();
     if (!routes_global_done && hctl_[kCtlWaveToGlobal]) {
@@ -6358,7 +6296,7 @@ void Matcher::run_device(const RunParams& rp) {
       // chosen transitions whose path search outgrew the LDS wave tier
       ensure_global_search();
       hipLaunchKernelGGL(k_tier_global<PathsStage>, dim3(kGlobalGrid), dim3(64), 0, st, g, v, (GlobalPathSmem*)w.gsearch.get());
-      scan_records();
+      s.layout_records(v);
       read_records();
     }
     if (!(hctl_[kCtlErr] & kErrPathOverflow)) break;

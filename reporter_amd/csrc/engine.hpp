@@ -190,7 +190,7 @@ struct WsPoints {   // sized by the batch's points, traces and option sets (Matc
   DevBuf<uint32_t> rl_paths_c;      // global-memory search tier: the path stage's hand-over list (kCtlPathsWaveToGlobal)
   DevBuf<uint32_t> trace_err;               // per trace: error bits (kErr*) of that trace alone
   DevBuf<unsigned long long> tot64;         // u64 totals: [0] transitions [1] sources [2] path edges
-  DevBuf<unsigned long long> scan_bkt;      // a steady run's coarse scan buckets (rm_common.hpp scan_base_lane)
+  DevBuf<unsigned long long> scan_bkt;      // a steady run's coarse scan buckets (engine.hip BaseBuckets, rm_common.hpp scan_base_lane)
   DevBuf<unsigned long long> tot_part;      // per-block partial pairs of those totals (the scans fold them)
 };
 struct WsTrans {    // the transition pool
@@ -214,7 +214,7 @@ struct WsSegs {     // the record pools
   uint64_t cap_segs = 0;
   DevBuf<SegmentRec> segs;
   DevBuf<ReportRec> reps;
-  DevBuf<uint32_t> rec_slot;   // K4: transition slot of each traversal record (k_rec_slot)
+  DevBuf<uint32_t> rec_slot;   // K4: transition slot of each traversal record (k_rec_slot, or k_path_apply's fill)
 };
 // locality order (engine.hip k_loc_count / k_loc_scatter): the sorted state slots, each slot's
 // region bucket, the bucket cursors and the item counts in sorted order; allocated on the first

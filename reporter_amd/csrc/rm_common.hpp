@@ -484,7 +484,7 @@ constexpr uint32_t kEdgeInternal = 1u, kEdgeHasSegment = 2u, kEdgeChainFirst = 4
 
 constexpr int kHistBins = 16;          // 10 km/h bins, 0..160 (reporter_service.py:133)
 
-// ---- block bases of the steady step's scans (engine.hip k_trans_apply_steady / k_path_apply_steady) ----
+// ---- block bases of the steady step's scans (engine.hip BaseBuckets, the base of k_trans_apply / k_path_apply on a steady run) ----
 // A counting kernel leaves one pair of u64 partials per block (part[2 * block]); every kScanGroup
 // of them are summed into one coarse bucket (bkt[2 * (block / kScanGroup)]).  Block blk's
 // base is the buckets of the groups before its own plus the partials before it inside its group:

@@ -2,8 +2,8 @@
 folded into the apply passes, and hand-over tiers left out after clean runs.
 
 A steady run's two scans (transitions / K2 sources, traversal records) take their block bases from
-coarse buckets of 64 blocks plus the partials inside the group (rm_common.hpp scan_base_lane), the
-apply passes also write src_item and rec_slot under local bounds, and a stage's five hand-over
+coarse buckets of 64 blocks plus the partials inside the group (rm_common.hpp scan_base_lane; engine.hip
+BaseBuckets), the apply passes (k_trans_apply, k_path_apply) also write src_item and rec_slot under local bounds, and a stage's five hand-over
 tiers are not launched once two runs in a row handed nothing over -- a prediction checked on the
 device every run.  Every run must equal the oracle bit for bit.  RM_SMALL_BATCH_POINTS=0 keeps the
 batches off the small-batch path.

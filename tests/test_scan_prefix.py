@@ -1,8 +1,9 @@
 """The steady scans' block bases (rm_common.hpp scan_base_lane), CPU.
 
 A counting kernel leaves one pair of u64 partials per block, every 64 of them are summed into
-one coarse bucket, and an apply block forms its base from the buckets before its group and the partials
-before it inside the group.  rm_scan_block_bases does exactly that on the host with the kernels'
+one coarse bucket, and an apply block of a steady run (engine.hip k_trans_apply / k_path_apply with
+BaseBuckets) forms its base from the buckets before its group and the partials before it inside
+the group.  rm_scan_block_bases does exactly that on the host with the kernels'
 helper, lane by lane; the bases must be the exclusive cumulative sums of the partials.  Block
 counts: one block, either side of a group boundary, the GPU test's 141 and C2's 23,438.
 """

@@ -1400,9 +1400,6 @@ int rm_runner_route_tiers(rm_runner* r, uint64_t out[10]) {
     out[3] = c[kCtlPathsBallToSearch]; out[4] = c[kCtlWaveToGlobal]; out[5] = c[kCtlPathsWaveToGlobal];
     out[6] = c[kCtlGroupToWave512]; out[7] = c[kCtlPathsGroupToWave512];
     out[8] = c[kCtlWave512ToWave4096]; out[9] = c[kCtlPathsWave512ToWave4096];
-#ifdef RM_K2_STATS
-    out[9] = c[kCtlWalkOverflow];   // diagnostic build: K2's walked turn weights
-#endif
   });
 }
 int rm_runner_run_stats(rm_runner* r, uint64_t out[4]) { return guarded([&] { r->m->run_stats(out); }); }

@@ -533,21 +533,6 @@ __device__ __forceinline__ void project(float alon, float alat, uint32_t acum, f
                                         float lon, float lat, float mlon, float mlat, float& sq, uint32_t& s) {
   project_rel((alon - lon) * mlon, (alat - lat) * mlat, acum, (blon - lon) * mlon, (blat - lat) * mlat, bcum, sq, s);
 }
-// An item whose two endpoints lie beyond the padded radius on the same side in x or in y
-//  cannot come within the radius: the projection lies between them, and the
-// fp32 rounding of the projected point is far below pad - r >= 0.5 m (a few ulps of coordinates
-// under 1000 km), so its sq exceeds r^2 with room to spare; rejecting it before the division is
-// bit-exact.  Off by default: measured slower on C2 and CITY30 (the test diverges the lanes of
-// a cell, and the division it saves is not what K1 waits on -- DESIGN.md §6 dead ends);
-// -DRM_K1_REJECT=1 builds it.
-#ifndef RM_K1_REJECT
-#define RM_K1_REJECT 0
-#endif
-__device__ __forceinline__ bool outside_pad(float ax, float ay, float bx, float by, float pad) {
-  if (!RM_K1_REJECT) return false;
-  return (ax > pad && bx > pad) || (ax < -pad && bx < -pad) || (ay > pad && by > pad) || (ay < -pad && by < -pad);
-}
-
 // time_ms on the device: below 2^32 cm*360 the IEEE double quotient truncates to the exact
 // floor (a non-integer quotient lies >= 1/dkph >= 2^-16 below the next integer, far above half
 // an ulp, 2^-21); about half the instructions of the integer division
@@ -557,28 +542,16 @@ __device__ __forceinline__ uint32_t time_ms_dev(uint32_t d_cm, uint32_t dkph) {
   return (uint32_t)((double)(d_cm * 360u) / (double)D);
 }
 
-// How the lane tier writes its descriptors.  1: the wave's candidates are staged in LDS and
-// built a lane per candidate by one rolled body.  0: a lane per state, slots unrolled in groups
-// of four (the form before; kept for A/Bs).  2: diagnostic only, writes cand_n and no
-// descriptors (wrong results: it sizes the epilogue's share of the kernel).
-#ifndef RM_K1_EPILOGUE
-#define RM_K1_EPILOGUE 1
-#endif
-
 // time_ms_dev for a whole wave: the u64 division a road beyond 119 km needs is out of line
 // behind a wave-uniform test, so the body that calls this carries no 64-bit division.  Same bits.
 __device__ __noinline__ uint32_t time_ms_far(uint32_t d_cm, uint32_t dkph) { return time_ms(d_cm, dkph); }
 __device__ __forceinline__ uint32_t time_ms_wave(uint32_t d_cm, uint32_t dkph) {
-#if RM_K1_EPILOGUE == 1
   const uint32_t D = dkph ? dkph : 1u;
   uint32_t t = (uint32_t)((double)(d_cm * 360u) / (double)D);
   if (__ballot(d_cm > 11930464u) != 0ull) {
     if (d_cm > 11930464u) t = time_ms_far(d_cm, dkph);
   }
   return t;
-#else
-  return time_ms_dev(d_cm, dkph);
-#endif
 }
 
 // candidate descriptor of (road, s) for a travel mode: everything the route and path
@@ -650,16 +623,6 @@ static_assert(kK1Slots % 4 == 0 && kK1Slots <= kMaxCand, "K1 slots");
 #endif
 constexpr int kK1Stage = RM_K1_STAGE;
 static_assert(kK1Stage >= 1, "K1 stage");
-// 1: the cooperative epilogue streams its descriptors out with nontemporal stores (0: plain, for A/Bs)
-#ifndef RM_K1_NT
-#define RM_K1_NT 1
-#endif
-// 1: one walk over the slots per hit item (update or insert) instead of a find walk and an insert
-// walk.  Off: it takes 148 VGPRs, three waves per SIMD, and measured slower
-#ifndef RM_K1_ONESCAN
-#define RM_K1_ONESCAN 0
-#endif
-
 // the state slot of the thread (b.P and above: none)
 __device__ __forceinline__ uint64_t k1_slot(const DevBatch& b) {
   if (!b.perm) return (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -735,32 +698,12 @@ __device__ __forceinline__ void k1_gather(const DevGraph& g, const DevBatch& b, 
           if (!((r1[y].z >> 29) & acc)) continue;
           const float ax = (as_f(r0[y].x) - lon) * mlon, ay = (as_f(r0[y].y) - lat) * mlat;
           const float bx = (as_f(r0[y].z) - lon) * mlon, by = (as_f(r0[y].w) - lat) * mlat;
-          if (outside_pad(ax, ay, bx, by, pad)) continue;
           float sq; uint32_t sc;
           project_rel(ax, ay, r1[y].x, bx, by, r1[y].y, sq, sc);
           if (!(sq <= r2)) continue;
           const uint32_t road = r1[y].z & 0x1fffffffu;
           const unsigned long long key = ((unsigned long long)__float_as_uint(sq) << 32) | r1[y].w;
           bool found = false;
-#if RM_K1_ONESCAN
-          // slots fill in order, so one walk does both: update the road's slot where it is found
-          // among the first n, else take slot n (every earlier slot has been compared by then)
-#pragma unroll
-          for (int x = 0; x < kK1Slots; ++x) {
-            if (K1_UNIFORM_STOP(x <= (int)n)) break;
-            if (x < (int)n) {
-              if (rroad[x] == road) {
-                found = true;
-                if (key < rbest[x]) { rbest[x] = key; rs[x] = sc; }
-              }
-            } else if (x == (int)n && !found) {
-              rroad[x] = road; rbest[x] = key; rs[x] = sc;
-            }
-          }
-          if (found) continue;
-          if (n >= (uint32_t)kK1Slots) { ovf = true; break; }
-          ++n;
-#else
 #pragma unroll
           for (int x = 0; x < kK1Slots; ++x) {
             if (K1_UNIFORM_STOP(x < (int)n)) break;   // no active lane holds slot x yet
@@ -777,7 +720,6 @@ __device__ __forceinline__ void k1_gather(const DevGraph& g, const DevBatch& b, 
             if (x == (int)n) { rroad[x] = road; rbest[x] = key; rs[x] = sc; }
           }
           ++n;
-#endif
         }
       }
     }
@@ -809,7 +751,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
     b.rl_cand[q] = (uint32_t)p;
     n = 0;
   }
-#if RM_K1_EPILOGUE == 1
   // rank by (sq, road): both fit one u64 key (sq >= 0, so its bits order as the value).  Roads
   // differ between slots, so of a pair exactly one is below the other: one compare ranks both
   uint32_t rank[kK1Slots];
@@ -860,62 +801,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_K1_
       uint4 d0, d1;
       desc_from_rec(ra, rc, c.x, c.y, cm, mode_access(cm), d0, d1);
       const uint64_t at = sm.p[wv][c.w & 63u] * kMaxCand + ((c.w >> 8) & 15u);
-#if RM_K1_NT
+      // nontemporal: the descriptors are read next by K2, after the rest of K1 has passed through the caches
       typedef uint32_t K1V4 __attribute__((ext_vector_type(4)));
       __builtin_nontemporal_store((K1V4){d0.x, d0.y, d0.z, d0.w}, (K1V4*)&b.cand_desc[2 * at]);
       __builtin_nontemporal_store((K1V4){d1.x, d1.y, d1.z, d1.w}, (K1V4*)&b.cand_desc[2 * at + 1]);
       __builtin_nontemporal_store(c.z, (uint32_t*)&b.cand_sq[at]);
-#else
-      b.cand_desc[2 * at] = d0;
-      b.cand_desc[2 * at + 1] = d1;
-      b.cand_sq[at] = __uint_as_float(c.z);
-#endif
     }
     wave_sync();   // the next pass overwrites the stage
   }
   if (live && !ovf) b.cand_n[p] = (uint8_t)n;
-#elif RM_K1_EPILOGUE == 2
-  if (live && !ovf) b.cand_n[p] = (uint8_t)n;
-#else
-  if (!live || ovf) return;
-  // rank by (sq, road); descriptors are written four at a time after their road records
-  // have all arrived (a store between two loads would serialise them: shared vmcnt)
-  const uint32_t cacc = mode_access(mode);
-#pragma unroll
-  for (int x0 = 0; x0 < kK1Slots; x0 += 4) {
-    if (K1_UNIFORM_STOP(x0 < (int)n)) break;
-    if (x0 >= (int)n) break;
-    uint4 ra[4], rc[4];
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      const uint64_t road = rroad[min(x0 + y, (int)n - 1)];
-      ra[y] = g.road_rec[2 * road];
-      rc[y] = g.road_rec[2 * road + 1];
-    }
-#pragma unroll
-    for (int y = 0; y < 4; ++y) {
-      const int x = x0 + y;
-      if (x >= (int)n) break;
-      const uint32_t sqb = (uint32_t)(rbest[x] >> 32);
-      // rank by (sq, road): both fit one u64 key (sq >= 0, so its bits order as the value)
-      const unsigned long long kx = ((unsigned long long)sqb << 32) | rroad[x];
-      uint32_t rank = 0;
-#pragma unroll
-      for (int z = 0; z < kK1Slots; ++z) {
-        if (K1_UNIFORM_STOP(z < (int)n)) break;
-        if (z >= (int)n) continue;
-        rank += ((((rbest[z] >> 32) << 32) | rroad[z]) < kx) ? 1u : 0u;
-      }
-      uint4 d0, d1;
-      desc_from_rec(ra[y], rc[y], rroad[x], rs[x], mode, cacc, d0, d1);
-      const uint64_t at = p * kMaxCand + rank;
-      b.cand_desc[2 * at] = d0;
-      b.cand_desc[2 * at + 1] = d1;
-      b.cand_sq[at] = __uint_as_float(sqb);
-    }
-  }
-  b.cand_n[p] = (uint8_t)n;
-#endif
 }
 
 // wave tier of K1: states whose radius holds more roads than the lane tier keeps
@@ -980,7 +874,6 @@ __device__ void cand_wave_one(const DevGraph& g, const DevBatch& b, CandSmem& sm
           if (!((r1.z >> 29) & acc)) continue;
           const float ax = (as_f(r0.x) - lon) * mlon, ay = (as_f(r0.y) - lat) * mlat;
           const float bx = (as_f(r0.z) - lon) * mlon, by = (as_f(r0.w) - lat) * mlat;
-          if (outside_pad(ax, ay, bx, by, pad)) continue;
           float sq; uint32_t sc;
           project_rel(ax, ay, r1.x, bx, by, r1.y, sq, sc);
           if (!(sq <= r2)) continue;
@@ -1973,41 +1866,47 @@ __device__ __forceinline__ void route_targets(const DevGraph& g, const DevBatch&
 // A table is keyed by road, so one probe per exit gives the labels of both entry nodes.
 constexpr uint32_t kBallMaxKeys = kBallMaxKeysHost;
 
-// row of `road` in a node's table (balls.hpp), continuing the probe from first-probe row e
-// (rmask: the road-id bits of the row's first word, rm_common.hpp ball_road_mask)
-__device__ __forceinline__ uint4 ball_resolve(const uint4* ent, const uint2& h, uint32_t road, uint4 e, uint32_t rmask) {
+// global-address-space 16-byte pointer: loads through it are global_load_dwordx4 even when the
+// address went through LDS (a generic pointer there would become a flat load)
+typedef unsigned int k2_v4 __attribute__((ext_vector_type(4)));
+typedef const k2_v4 __attribute__((address_space(1)))* k2_gptr;
+__device__ __forceinline__ uint4 k2_ld(k2_gptr p) {
+  const k2_v4 v = *p;
+  return make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ uint4 k2_ld(const uint4* p) { return *p; }
+
+// row of `road` in a node's table (balls.hpp), continuing the probe from first-probe row e at
+// slot s; s becomes the row's slot (rmask: the road-id bits of the row's first word, rm_common.hpp
+// ball_road_mask).  P: const uint4*, or k2_gptr for global loads.
+template <class P>
+__device__ __forceinline__ uint4 ball_resolve(P ent, const uint2& h, uint32_t road, uint4 e, uint32_t rmask, uint32_t& s) {
   if ((e.x & rmask) == road || e.x == kNone) return e;
   const uint32_t mask = (1u << h.y) - 1u;
-  uint32_t s = ball_slot(road, h.y);
   for (;;) {
     s = (s + 1u) & mask;
-    e = ent[ball_row0(h.x) + s];
+    e = k2_ld(ent + (ball_row0(h.x) + s));
     if ((e.x & rmask) == road || e.x == kNone) return e;
   }
 }
-
-// ball_resolve that also gives the row's slot (s: the first probe's slot on entry)
-__device__ __forceinline__ uint4 ball_resolve_at(const uint4* ent, const uint2& h, uint32_t road, uint4 e, uint32_t rmask,
-                                                 uint32_t& s) {
-  if ((e.x & rmask) == road || e.x == kNone) return e;
-  const uint32_t mask = (1u << h.y) - 1u;
-  for (;;) {
-    s = (s + 1u) & mask;
-    e = ent[ball_row0(h.x) + s];
-    if ((e.x & rmask) == road || e.x == kNone) return e;
-  }
+// the row of `road` in the table with header h
+__device__ __forceinline__ uint4 ball_row(const uint4* ent, const uint2& h, uint32_t road, uint32_t rmask) {
+  uint32_t s = ball_slot(road, h.y);
+  return ball_resolve(ent, h, road, ent[ball_row0(h.x) + s], rmask, s);
 }
 
 // keys from a row (kKeyInf for an endpoint outside the ball or a road not in the table)
 __device__ __forceinline__ unsigned long long row_key0(const uint4& e) { return ball_key0(e.x, e.y, e.w); }
 __device__ __forceinline__ unsigned long long row_key1(const uint4& e) { return ball_key1(e.x, e.z, e.w); }
 
+// label of an entry node through one exit (root key rk, row key d), and through the better of both
+__device__ __forceinline__ unsigned long long exit_label(unsigned long long rk, unsigned long long d) {
+  return d != kKeyInf ? rk + d : kKeyInf;
+}
 __device__ __forceinline__ unsigned long long ball_label(unsigned long long rk1, unsigned long long d1,
                                                          unsigned long long rk0, unsigned long long d0) {
-  unsigned long long k = kKeyInf;
-  if (d1 != kKeyInf) k = rk1 + d1;
-  if (d0 != kKeyInf && rk0 + d0 < k) k = rk0 + d0;
-  return k;
+  const unsigned long long l1 = exit_label(rk1, d1), l0 = exit_label(rk0, d0);
+  return l0 < l1 ? l0 : l1;
 }
 
 #ifndef RM_BALL_WPE
@@ -2020,7 +1919,7 @@ __device__ __forceinline__ unsigned long long ball_label(unsigned long long rk1,
 // (source, target) transition per lane and step: the target's descriptor, both exits' probes of
 // the target road, the label, the key, one coalesced store.  No lane walks a target loop of its
 // own (the round-2 kernel's lanes ran to their wave's largest K_B, each target two dependent
-// round trips after the last), and two transitions per lane are in flight at once.
+// round trips after the last).
 #ifndef RM_K2_ITEMS
 #define RM_K2_ITEMS 256
 #endif
@@ -2031,45 +1930,23 @@ static_assert(kK2Items <= kK2Threads && kK2Items % 64 == 0, "phase 1 runs one it
 // and so do batches sampled this sparsely on average (Matcher::run)
 constexpr uint64_t kLocalityNodes = 150000;
 constexpr double kLocalitySparseS = 10.0;
-// global-address-space 16-byte pointer: loads through it are global_load_dwordx4 even when the
-// address went through LDS (a generic pointer there would become a flat load)
-typedef unsigned int k2_v4 __attribute__((ext_vector_type(4)));
-typedef const k2_v4 __attribute__((address_space(1)))* k2_gptr;
-__device__ __forceinline__ uint4 k2_ld(k2_gptr p) {
-  const k2_v4 v = *p;
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-// A source item in full (k_turn_walks rebuilds it for the walked turn weights, k2_route_turn)
-struct K2Src {
-  unsigned long long ent;        // the item's mode's table rows (a global address: see k2_gptr)
-  uint2 h1, h0;                  // table headers of the exits (bits 0: no table)
-  unsigned long long rk1, rk0;   // exit root keys (kKeyInf: that exit is unusable)
-  uint32_t road, s;              // source road and offset on it (direct combinations)
-  uint32_t bound, tmax;          // pair bounds; bound = kNone: handed to the search tiers
-  uint32_t lim;                  // routes with distance <= lim are exact from the tables (ball_exact_limit)
-};
-// per item of a batch with turn costs (rule 3b): the mode's turn rows, the source road's headings
-// and endpoints, the pair's factor
-struct K2Turn {
-  unsigned long long trn;        // turn rows of the item's mode (a global address)
-  uint32_t hw;                   // heading word of the source road (rm_common.hpp head_back)
-  uint32_t fac;                  // pair_info.w: the factor's float bits; 0: the item has no turn costs
-  uint32_t n0, n1;               // the source road's endpoints (the exits' nodes)
-  uint32_t mode, pad;
-};
-// The item record of the kernel without turn costs, 60 bytes (round 6).  LDS sets this kernel's
-// occupancy: at 80 bytes per item (22.8 -> 24.9 KB per block) C2's K2 went 0.866 -> 0.935 ms with
-// the same loop (6 blocks of 4 waves per CU instead of 7); at 60 bytes a block fits 20 KB and a CU
-// holds 8 of them.  The mode's table base comes from a per-mode LDS table (the road word's top
-// bits), the root keys are split into words (4-byte alignment), and the descriptor and route
-// offsets are folded with the item's first transition (dbase, obase).
+// The item record, 60 bytes (round 6).  LDS sets K2's occupancy: at 80 bytes per item (22.8 ->
+// 24.9 KB per block) C2's K2 went 0.866 -> 0.935 ms with the same loop (6 blocks of 4 waves per CU
+// instead of 7); at 60 bytes a block fits 20 KB and a CU holds 8 of them.  The mode's table base
+// comes from a per-mode LDS table (the road word's top bits), the root keys are split into words
+// (4-byte alignment), and the descriptor and route offsets are folded with the item's first
+// transition (dbase, obase).
 struct K2SrcS {
   uint32_t dbase;                // transition q of the block reads descriptor pair dbase + q
   uint32_t obase;                // ... and writes b.route[obase + q]
-  uint32_t h1x, h1y, h0x, h0y;   // table headers of the exits (uint2 would align to 8)
-  uint32_t rk1l, rk1h, rk0l, rk0h;   // exit root keys, split
+  uint32_t h1x, h1y, h0x, h0y;   // table headers of the exits (uint2 would align to 8; bits 0: no table)
+  uint32_t rk1l, rk1h, rk0l, rk0h;   // exit root keys, split (kKeyInf: that exit is unusable)
   uint32_t roadm;                // source road | mode << 29
-  uint32_t s, bound, tmax, lim;
+  uint32_t s;                    // the source's offset on its road (direct combinations)
+  uint32_t bound, tmax;          // pair bounds; bound = kNone: handed to the search tiers
+  uint32_t lim;                  // routes with distance <= lim are exact from the tables (ball_exact_limit)
+  __device__ __forceinline__ unsigned long long rk1() const { return (unsigned long long)rk1h << 32 | rk1l; }
+  __device__ __forceinline__ unsigned long long rk0() const { return (unsigned long long)rk0h << 32 | rk0l; }
 };
 static_assert(sizeof(K2SrcS) == 60, "K2SrcS is 60 bytes");
 // walked turn weights (ties between the exits) a K2 block lists for k_turn_walks: each goes to the
@@ -2112,6 +1989,65 @@ __device__ __forceinline__ uint32_t ball_exact_limit(uint32_t bound, uint32_t ra
   return lim >= bound ? kNone : lim;
 }
 
+// The exits of a source (descriptor rows a0, a1) under a pair's bound, as the route tables see
+// them: root keys, the exit nodes' table headers and the exactness limit
+struct BallExits {
+  unsigned long long rk1, rk0;   // exit root keys (kKeyInf: that exit is unusable)
+  uint2 h1, h0;                  // table headers of the exits (bits 0: the node has no table)
+  uint32_t lim;                  // ball_exact_limit
+  bool fits;                     // the mode has tables
+  // false: the search tiers take the source
+  __device__ __forceinline__ bool tables() const { return fits && h1.y != 0u && h0.y != 0u; }
+};
+__device__ __forceinline__ BallExits ball_exits(const DevGraph& g, const uint4& a0, const uint4& a1, uint32_t bound, int mode) {
+  BallExits x;
+  exit_keys(a0, bound, x.rk1, x.rk0);
+  // the mode's tables answer any bound: beyond their radius, the routes they decide
+  x.fits = (g.ball_mask >> mode) & 1u;
+  x.lim = ball_exact_limit(bound, g.ball_radius[mode], x.rk1, x.rk0);
+  x.h1 = x.h0 = make_uint2(0u, 1u);
+  if (x.fits) {   // both headers loaded together, then kept where the exit is usable
+    const uint2* hp = g.ball_hdr[mode];
+    const uint2 x1 = hp[a1.y], x0 = hp[a1.x];
+    if (x.rk1 != kKeyInf) x.h1 = x1;
+    if (x.rk0 != kKeyInf) x.h0 = x0;
+  }
+  return x;
+}
+
+// a row or the empty row, selected per word (a select of the aggregate went through scratch)
+__device__ __forceinline__ uint4 k2_row_or_none(bool use, const uint4& e) {
+  return make_uint4(use ? e.x : kNone, use ? e.y : kBallNoDist, use ? e.z : kBallNoDist, use ? e.w : 0u);
+}
+typedef unsigned int k2_v2 __attribute__((ext_vector_type(2)));
+typedef const k2_v2 __attribute__((address_space(1)))* k2_trow;
+// Both exits' rows of a target road (r1, r0, at slots s1, s0): the first probes are issued
+// together, an unused exit (u1 / u0 false) reading the valid row `dummy` that the empty row then
+// replaces, and collisions are resolved after both.  With TROWS (and `trn`) both exits' turn rows
+// at the first-probe slots are read with the probes (v1, v0).
+struct BallRows {
+  uint4 r1, r0;
+  uint32_t s1, s0;
+  k2_v2 v1, v0;
+};
+template <bool TROWS, class P>
+__device__ __forceinline__ BallRows ball_rows(P ent, P dummy, const uint2& h1, const uint2& h0, bool u1, bool u0,
+                                              uint32_t road, uint32_t rm, k2_trow tra = nullptr, bool trn = false) {
+  BallRows R;
+  R.s1 = ball_slot(road, h1.y);
+  R.s0 = ball_slot(road, h0.y);
+  const uint64_t i1 = ball_row0(h1.x) + R.s1, i0 = ball_row0(h0.x) + R.s0;
+  const uint4 l1 = k2_ld(u1 ? ent + i1 : dummy), l0 = k2_ld(u0 ? ent + i0 : dummy);
+  if constexpr (TROWS) {
+    const k2_trow tdummy = (k2_trow)dummy;
+    R.v1 = *(u1 && trn ? tra + i1 : tdummy);
+    R.v0 = *(u0 && trn ? tra + i0 : tdummy);
+  }
+  R.r1 = ball_resolve(ent, h1, road, k2_row_or_none(u1, l1), rm, R.s1);
+  R.r0 = ball_resolve(ent, h0, road, k2_row_or_none(u0, l0), rm, R.s0);
+  return R;
+}
+
 // route of item S to the target described by (t0, t1), from the target road's rows (r1, r0)
 // in the tables of S's two exits (kRouteInvalid when there is none within the bounds); `exact`
 // false when the tables cannot decide it (ball_exact_limit)
@@ -2125,10 +2061,6 @@ __device__ __forceinline__ uint32_t k2_route_v(unsigned long long rk1, unsigned 
   exact = lim == kNone || (key != kKeyInf && key_dist(key) <= lim);
   return (key != kKeyInf && key_dist(key) <= bound && key_time(key) <= tmax) ? key_dist(key) : kRouteInvalid;
 }
-__device__ __forceinline__ uint32_t k2_route(const K2Src& S, const uint4& t0, const uint4& t1, const uint4& r1,
-                                             const uint4& r0, bool& exact) {
-  return k2_route_v(S.rk1, S.rk0, S.road, S.s, S.lim, S.bound, S.tmax, t0, t1, r1, r0, exact);
-}
 
 // labels from the route balls of the two exits (see k_routes_ball2)
 struct BallPathLabels {
@@ -2136,17 +2068,11 @@ struct BallPathLabels {
   uint2 h1, h0;
   unsigned long long rk1, rk0;
   uint32_t rm;   // road-id bits of a row's first word
-  // both exits' rows of `road` (a dummy row for an unusable exit), first probes issued together
+  // both exits' rows of `road`; an unusable exit reads row 0 (valid: the mode has tables)
   __device__ void rows(uint32_t road, uint4& r1, uint4& r0) const {
-    // both first probes issued together: an unusable exit reads row 0 (valid: the mode has
-    // tables) and its row is replaced by the empty row afterwards
-    const bool u1 = rk1 != kKeyInf, u0 = rk0 != kKeyInf;
-    const uint64_t i1 = u1 ? ball_row0(h1.x) + ball_slot(road, h1.y) : 0u;
-    const uint64_t i0 = u0 ? ball_row0(h0.x) + ball_slot(road, h0.y) : 0u;
-    const uint4 l1 = ent[i1], l0 = ent[i0];
-    const uint4 none = make_uint4(kNone, kBallNoDist, kBallNoDist, 0u);
-    r1 = ball_resolve(ent, h1, road, u1 ? l1 : none, rm);
-    r0 = ball_resolve(ent, h0, road, u0 ? l0 : none, rm);
+    const BallRows R = ball_rows<false>(ent, ent, h1, h0, rk1 != kKeyInf, rk0 != kKeyInf, road, rm);
+    r1 = R.r1;
+    r0 = R.r0;
   }
   __device__ unsigned long long operator()(uint32_t, uint32_t road, uint32_t side) const {
     uint4 r1, r0;
@@ -2204,221 +2130,87 @@ struct TableCursor {
 // at a node whose route runs along its own road ties there), or a row without its sum
 constexpr uint32_t kTableTurnSteps = 2u * kBallMaxKeysHost + 3u;
 
-// A route the tables answer in a batch with turn costs (rule 3b, TURN), and its distance term
-// d = turn_m + |route_m - gc| (route_term).  The turn weight: when one exit gives the entry node
-// its label strictly, that exit's turn row holds the weight of the path from the exit node on and
-// the heading it leaves the exit node with, and the turn at the exit node is from the source road;
-// otherwise (a tie, or a row without its sum) canonical_turns through the tables.
-// pt1 / pt0: both exits' turn rows at the first-probe slots h1s / h0s, loaded with the probes (a
-// route resolved past a collision reloads its row); tw: the turn weights in LDS
-__device__ __forceinline__ uint32_t k2_route_turn(const DevGraph& g, const K2Src& S, const K2Turn& T, const uint4& t0,
-                                                  const uint4& t1, const uint4& r1, const uint4& r0, uint32_t s1,
-                                                  uint32_t s0, uint32_t h1s, uint32_t h0s, const uint2& pt1,
-                                                  const uint2& pt0, const uint32_t* tw, double gc, bool& exact, double& d) {
-  const unsigned long long k10 = row_key0(r1), k00 = row_key0(r0), k11 = row_key1(r1), k01 = row_key1(r0);
-  const unsigned long long l10 = k10 != kKeyInf ? S.rk1 + k10 : kKeyInf, l00 = k00 != kKeyInf ? S.rk0 + k00 : kKeyInf;
-  const unsigned long long l11 = k11 != kKeyInf ? S.rk1 + k11 : kKeyInf, l01 = k01 != kKeyInf ? S.rk0 + k01 : kKeyInf;
-  const unsigned long long lab0 = l00 < l10 ? l00 : l10, lab1 = l01 < l11 ? l01 : l11;
-  const uint4 a0 = make_uint4(S.road, S.s, 0u, 0u);
-  int combo = -1;
-  const unsigned long long key = route_key_vals(a0, t0, t1, lab0, lab1, &combo);
-  exact = S.lim == kNone || (key != kKeyInf && key_dist(key) <= S.lim);
-  const bool valid = key != kKeyInf && key_dist(key) <= S.bound && key_time(key) <= S.tmax;
-  uint32_t U = 0u;
-  if (T.fac && valid && combo >= 2 && exact) {
-    const uint32_t side = (uint32_t)combo - 2u;
-    const unsigned long long la = side ? l11 : l10, lb = side ? l01 : l00;
-    uint32_t w = kTurnNone;
-    const bool e1 = la < lb;
-    if (la != lb) {
-      uint2 trow = e1 ? pt1 : pt0;
-      if ((e1 ? s1 != h1s : s0 != h0s)) {   // resolved past a collision: the row of the final slot
-        const uint64_t row = e1 ? ball_row0(S.h1.x) + s1 : ball_row0(S.h0.x) + s0;
-        trow = reinterpret_cast<const uint2*>(T.trn)[row];
-      }
-      w = side ? trow.y : trow.x;
-    }
-    if ((w & kTurnTMask) != kTurnNone) {
-      U = tw[turn_degree(head_back(T.hw, e1 ? 0u : 1u), w >> kTurnHeadShift)] + (w & kTurnTMask);
-    } else {
-      const BallPathLabels lab{(const uint4*)S.ent, S.h1, S.h0, S.rk1, S.rk0, g.ball_road_mask};
-      TableCursor c{lab, r1, r0};
-      bool ok = true;
-      U = canonical_turns(g, c, (int)T.mode, T.hw, T.n1, T.n0, S.rk1, S.rk0, t0.x, side ? t1.y : t1.x, side,
-                          kTableTurnSteps, ok);
-      if (!ok) exact = false;
-    }
-  }
-  const uint32_t r = valid ? key_dist(key) : kRouteInvalid;
-  d = route_term(r, U, T.fac, gc);
-  return r;
+// K2 item t decoded: pair slot, source rank, the pair's first route, pair_info, its fields, the source's cand_desc row
+struct K2Item { uint32_t p, i, base; uint4 pi; uint32_t bound, tmax, KB; int mode; uint64_t arow; };
+__device__ __forceinline__ K2Item k2_item(const DevBatch& b, uint32_t t) {
+  const uint32_t p = b.src_item[t], i = t - b.src_off[p];
+  const uint4 pi = b.pair_info[p];
+  return {p, i, b.trans_off[p], pi, pi.x, pi.y, (pi.z >> 8) & 0xffu, (int)(pi.z >> 16), ((uint64_t)(p - 1) * kMaxCand + i) * 2};
 }
-
-// ---- k_routes_ball2 phase 2 (round 6, VERDICT r05 item 2: "take control of the waits").  A
-// software-pipelined loop was built and measured: the probe addresses formed branch-free (every
-// exit's header valid, ball_slot_bf), 24-byte descriptor reads, two register sets so a step issued
-// its probes, then the next step's descriptors, then waited for its own probes only (the ISA
-// checked: vmcnt(7)/(6) waits, no waits between the issue groups).  C2's K2 did not move (0.951 vs
-// 0.931 ms for the unpipelined loop on the same build, bench-style timing): the kernel is not bound
-// by where its waits sit but by occupancy and VALU (valu_frac 0.65).  What moved it was LDS: the
-// item records at 80 bytes gave 6 blocks per CU, at 72 bytes 7 (0.935 -> 0.866 ms), at 60 (K2SrcS)
-// 8.  The turn-cost kernel keeps the pipelined loop (k2_phase2_pipe_t).
+// the item's record but for dbase and obase, which depend on the block (k_routes_ball2's phase 1)
+__device__ __forceinline__ K2SrcS k2_src(const K2Item& it, const BallExits& x, const uint4& a0) {
+  K2SrcS z;
+  z.dbase = z.obase = 0u;
+  z.h1x = x.h1.x; z.h1y = x.h1.y;
+  z.h0x = x.h0.x; z.h0y = x.h0.y;
+  z.rk1l = (uint32_t)x.rk1; z.rk1h = (uint32_t)(x.rk1 >> 32);
+  z.rk0l = (uint32_t)x.rk0; z.rk0h = (uint32_t)(x.rk0 >> 32);
+  z.roadm = a0.x | (uint32_t)it.mode << 29;
+  z.s = a0.y;
+  z.bound = it.bound;
+  z.tmax = it.tmax;
+  z.lim = x.lim;
+  return z;
+}
+// descriptor of transition q of a block, owned by item A: the first row, and of the second only
+// the entry times
 typedef unsigned int k2_u2 __attribute__((ext_vector_type(2)));
 typedef const k2_u2 __attribute__((address_space(1)))* k2_gptr2;
-__device__ __forceinline__ uint2 k2_ld2(k2_gptr2 p) {
-  const k2_u2 v = *p;
-  return make_uint2(v.x, v.y);
-}
-// a row or the empty row, selected per word (a select of the aggregate went through scratch)
-__device__ __forceinline__ uint4 k2_row_or_none(bool use, const uint4& e) {
-  return make_uint4(use ? e.x : kNone, use ? e.y : kBallNoDist, use ? e.z : kBallNoDist, use ? e.w : 0u);
-}
-// ball_resolve through a global-address-space pointer
-__device__ __forceinline__ uint4 ball_resolve_g(k2_gptr ent, const uint2& h, uint32_t road, uint4 e, uint32_t rmask) {
-  if ((e.x & rmask) == road || e.x == kNone) return e;
-  const uint32_t mask = (1u << h.y) - 1u;
-  uint32_t s = ball_slot(road, h.y);
-  for (;;) {
-    s = (s + 1u) & mask;
-    e = k2_ld(ent + (ball_row0(h.x) + s));
-    if ((e.x & rmask) == road || e.x == kNone) return e;
-  }
-}
-// phase 2 without turn costs: two transitions per lane and step, every load of a step issued before
-// any is used (the descriptors unconditionally -- a handed-over item's descriptor is as valid an
-// address --, the four first probes branch-free with an unused probe reading a valid dummy row)
-__device__ __forceinline__ uint4 ball_resolve_at_g(k2_gptr ent, const uint2& h, uint32_t road, uint4 e, uint32_t rmask,
-                                                   uint32_t& s) {
-  if ((e.x & rmask) == road || e.x == kNone) return e;
-  const uint32_t mask = (1u << h.y) - 1u;
-  for (;;) {
-    s = (s + 1u) & mask;
-    e = k2_ld(ent + (ball_row0(h.x) + s));
-    if ((e.x & rmask) == road || e.x == kNone) return e;
-  }
-}
-// phase 2 without turn costs: 3 (default, round 6) one transition per lane and step with the next
-// step's descriptor loaded ahead; 1 the same without the prefetch; 2 two transitions per step
-#ifndef RM_K2_PLAIN_STEP
-#define RM_K2_PLAIN_STEP 3
-#endif
-template <class SM>
-__device__ __forceinline__ void k2_phase2_slim(SM& sm, const DevBatch& b, uint32_t n, uint32_t rm, k2_gptr dummy) {
-  const uint4 none = make_uint4(kNone, kBallNoDist, kBallNoDist, 0u);
-  if (RM_K2_PLAIN_STEP == 3) {   // one transition per step, the next step's descriptor loaded ahead
-    // (its loads are in flight with this step's probes: one memory round trip per step instead of
-    // two; 54 VGPRs, 8 waves per SIMD; C2 routes 0.782 -> 0.766 ms)
-    uint32_t q = threadIdx.x;
-    uint4 ta0 = make_uint4(0u, 0u, 0u, 0u);
-    uint2 ta1 = make_uint2(0u, 0u);
-    if (q < n) {
-      const K2SrcS& A0 = sm.src[sm.owner[q]];
-      const uint4* pd = b.cand_desc + 2 * (uint64_t)(A0.dbase + q);
-      ta0 = k2_ld((k2_gptr)(const void*)pd);
-      ta1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pd + 1) + 1));
-    }
-    for (; q < n; q += kK2Threads) {
-      const K2SrcS& A = sm.src[sm.owner[q]];
-      const uint32_t qn = q + kK2Threads < n ? q + kK2Threads : q;   // clamped: a valid address
-      const K2SrcS& An = sm.src[sm.owner[qn]];
-      const uint4* pdn = b.cand_desc + 2 * (uint64_t)(An.dbase + qn);
-      const uint4 nt0 = k2_ld((k2_gptr)(const void*)pdn);
-      const uint2 nt1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pdn + 1) + 1));
-      const bool la = A.bound != kNone;
-      const unsigned long long ak1 = (unsigned long long)A.rk1h << 32 | A.rk1l, ak0 = (unsigned long long)A.rk0h << 32 | A.rk0l;
-      const bool ua = la && ta0.w != 0u;
-      const bool ua1 = ua && ak1 != kKeyInf, ua0 = ua && ak0 != kKeyInf;
-      const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[A.roadm >> 29];
-      const k2_gptr pa1 = ua1 ? ea + (ball_row0(A.h1x) + ball_slot(ta0.x, A.h1y)) : dummy;
-      const k2_gptr pa0 = ua0 ? ea + (ball_row0(A.h0x) + ball_slot(ta0.x, A.h0y)) : dummy;
-      const uint4 la1 = k2_ld(pa1), la0 = k2_ld(pa0);
-      bool xa = true;
-      const uint32_t r = k2_route_v(ak1, ak0, A.roadm & 0x1fffffffu, A.s, A.lim, A.bound, A.tmax, ta0,
-                                    make_uint4(0u, 0u, ta1.x, ta1.y),
-                                    ball_resolve_g(ea, make_uint2(A.h1x, A.h1y), ta0.x, k2_row_or_none(ua1, la1), rm),
-                                    ball_resolve_g(ea, make_uint2(A.h0x, A.h0y), ta0.x, k2_row_or_none(ua0, la0), rm), xa);
-      if (la) {
-        b.route[A.obase + q] = r;
-        if (!xa) k2_redo(sm, sm.owner[q]);
-      }
-      ta0 = nt0;
-      ta1 = nt1;
-    }
-    return;
-  }
-  if (RM_K2_PLAIN_STEP == 1) {   // (A/B: one transition per lane and step, fewer registers)
-    for (uint32_t q = threadIdx.x; q < n; q += kK2Threads) {
-      const K2SrcS& A = sm.src[sm.owner[q]];
-      const bool la = A.bound != kNone;
-      const uint4* pda = b.cand_desc + 2 * (uint64_t)(A.dbase + q);
-      const uint4 ta0 = k2_ld((k2_gptr)(const void*)pda);
-      const uint2 ta1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pda + 1) + 1));
-      const unsigned long long ak1 = (unsigned long long)A.rk1h << 32 | A.rk1l, ak0 = (unsigned long long)A.rk0h << 32 | A.rk0l;
-      const bool ua = la && ta0.w != 0u;
-      const bool ua1 = ua && ak1 != kKeyInf, ua0 = ua && ak0 != kKeyInf;
-      const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[A.roadm >> 29];
-      const k2_gptr pa1 = ua1 ? ea + (ball_row0(A.h1x) + ball_slot(ta0.x, A.h1y)) : dummy;
-      const k2_gptr pa0 = ua0 ? ea + (ball_row0(A.h0x) + ball_slot(ta0.x, A.h0y)) : dummy;
-      const uint4 la1 = k2_ld(pa1), la0 = k2_ld(pa0);
-      bool xa = true;
-      const uint32_t r = k2_route_v(ak1, ak0, A.roadm & 0x1fffffffu, A.s, A.lim, A.bound, A.tmax, ta0,
-                                    make_uint4(0u, 0u, ta1.x, ta1.y),
-                                    ball_resolve_g(ea, make_uint2(A.h1x, A.h1y), ta0.x, k2_row_or_none(ua1, la1), rm),
-                                    ball_resolve_g(ea, make_uint2(A.h0x, A.h0y), ta0.x, k2_row_or_none(ua0, la0), rm), xa);
-      if (la) {
-        b.route[A.obase + q] = r;
-        if (!xa) k2_redo(sm, sm.owner[q]);
-      }
-    }
-    return;
-  }
-  for (uint32_t q = threadIdx.x; q < n; q += 2 * kK2Threads) {
-    const uint32_t qb = q + kK2Threads;
-    const bool hb = qb < n;
-    const uint32_t qB = hb ? qb : q;
-    const K2SrcS& A = sm.src[sm.owner[q]];
-    const K2SrcS& B = sm.src[sm.owner[qB]];
-    const bool la = A.bound != kNone, lb = hb && B.bound != kNone;
-    const uint4* pda = b.cand_desc + 2 * (uint64_t)(A.dbase + q);
-    const uint4* pdb = b.cand_desc + 2 * (uint64_t)(B.dbase + qB);
-    const uint4 ta0 = k2_ld((k2_gptr)(const void*)pda), tb0 = k2_ld((k2_gptr)(const void*)pdb);
-    // of the second half only the entry times
-    const uint2 ta1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pda + 1) + 1));
-    const uint2 tb1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pdb + 1) + 1));
-    const unsigned long long ak1 = (unsigned long long)A.rk1h << 32 | A.rk1l, ak0 = (unsigned long long)A.rk0h << 32 | A.rk0l;
-    const unsigned long long bk1 = (unsigned long long)B.rk1h << 32 | B.rk1l, bk0 = (unsigned long long)B.rk0h << 32 | B.rk0l;
-    const bool ua = la && ta0.w != 0u, ub = lb && tb0.w != 0u;   // some direction of the target road is usable
-    const bool ua1 = ua && ak1 != kKeyInf, ua0 = ua && ak0 != kKeyInf;
-    const bool ub1 = ub && bk1 != kKeyInf, ub0 = ub && bk0 != kKeyInf;
-    const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[A.roadm >> 29];
-    const k2_gptr eb = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[B.roadm >> 29];
-    const k2_gptr pa1 = ua1 ? ea + (ball_row0(A.h1x) + ball_slot(ta0.x, A.h1y)) : dummy;
-    const k2_gptr pa0 = ua0 ? ea + (ball_row0(A.h0x) + ball_slot(ta0.x, A.h0y)) : dummy;
-    const k2_gptr pb1 = ub1 ? eb + (ball_row0(B.h1x) + ball_slot(tb0.x, B.h1y)) : dummy;
-    const k2_gptr pb0 = ub0 ? eb + (ball_row0(B.h0x) + ball_slot(tb0.x, B.h0y)) : dummy;
-    const uint4 la1 = k2_ld(pa1), la0 = k2_ld(pa0), lb1 = k2_ld(pb1), lb0 = k2_ld(pb0);
-    bool xa = true, xb = true;
-    if (la)
-      b.route[A.obase + q] = k2_route_v(ak1, ak0, A.roadm & 0x1fffffffu, A.s, A.lim, A.bound, A.tmax, ta0,
-                                        make_uint4(0u, 0u, ta1.x, ta1.y),
-                                        ball_resolve_g(ea, make_uint2(A.h1x, A.h1y), ta0.x, k2_row_or_none(ua1, la1), rm),
-                                        ball_resolve_g(ea, make_uint2(A.h0x, A.h0y), ta0.x, k2_row_or_none(ua0, la0), rm), xa);
-    if (lb)
-      b.route[B.obase + qb] = k2_route_v(bk1, bk0, B.roadm & 0x1fffffffu, B.s, B.lim, B.bound, B.tmax, tb0,
-                                         make_uint4(0u, 0u, tb1.x, tb1.y),
-                                         ball_resolve_g(eb, make_uint2(B.h1x, B.h1y), tb0.x, k2_row_or_none(ub1, lb1), rm),
-                                         ball_resolve_g(eb, make_uint2(B.h0x, B.h0y), tb0.x, k2_row_or_none(ub0, lb0), rm), xb);
-    if (!xa) k2_redo(sm, sm.owner[q]);
-    if (!xb) k2_redo(sm, sm.owner[qB]);
-  }
-  (void)none;
+__device__ __forceinline__ void k2_target(const DevBatch& b, const K2SrcS& A, uint32_t q, uint4& t0, uint4& t1) {
+  const uint4* pd = b.cand_desc + 2 * (uint64_t)(A.dbase + q);
+  t0 = k2_ld((k2_gptr)(const void*)pd);
+  const k2_u2 v = *(k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pd + 1) + 1);
+  t1 = make_uint4(0u, 0u, v.x, v.y);
 }
 
-// k_routes_ball2<true>'s two-per-step loop (round 6): the route of a transition from the tables,
-// and what its turn weight needs -- nothing (U = 0: no turn costs, an invalid or direct route, a
-// route the tables cannot decide), the turn row of the exit that strictly gives the entry node its
-// label (`row`, read after the probes), or the walk (a tie between the exits).  The same decisions
-// as k2_route_turn.
+// ---- k_routes_ball2 phase 2 (round 6).  A software-pipelined loop was built and measured: the
+// probe addresses formed branch-free (every exit's header valid), 24-byte descriptor reads, two
+// register sets so a step issued its probes, then the next step's descriptors, then waited for its
+// own probes only (the ISA checked: vmcnt(7)/(6) waits, no waits between the issue groups).  C2's
+// K2 did not move (0.951 vs 0.931 ms for the unpipelined loop on the same build, bench-style
+// timing): the kernel is not bound by where its waits sit but by occupancy and VALU (valu_frac
+// 0.65).  What moved it was LDS: the item records at 80 bytes gave 6 blocks per CU, at 72 bytes 7
+// (0.935 -> 0.866 ms), at 60 (K2SrcS) 8.
+//
+// Without turn costs: one transition per lane and step, with the next step's descriptor loaded
+// ahead (its loads are in flight with this step's probes: one memory round trip per step instead
+// of two; 54 VGPRs, 8 waves per SIMD; C2 routes 0.782 -> 0.766 ms).  The descriptors are loaded
+// unconditionally -- a handed-over item's descriptor is as valid an address.
+template <class SM>
+__device__ __forceinline__ void k2_phase2_slim(SM& sm, const DevBatch& b, uint32_t n, uint32_t rm, k2_gptr dummy) {
+  uint32_t q = threadIdx.x;
+  uint4 ta0 = make_uint4(0u, 0u, 0u, 0u), ta1 = ta0;
+  if (q < n) k2_target(b, sm.src[sm.owner[q]], q, ta0, ta1);
+  for (; q < n; q += kK2Threads) {
+    const K2SrcS& A = sm.src[sm.owner[q]];
+    const uint32_t qn = q + kK2Threads < n ? q + kK2Threads : q;   // clamped: a valid address
+    uint4 nt0, nt1;
+    k2_target(b, sm.src[sm.owner[qn]], qn, nt0, nt1);
+    const bool la = A.bound != kNone;
+    const unsigned long long ak1 = A.rk1(), ak0 = A.rk0();
+    const bool ua = la && ta0.w != 0u;   // some direction of the target road is usable
+    const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[A.roadm >> 29];
+    // (the probes written out, not ball_rows: through it this kernel takes 56 VGPRs instead of 54)
+    const bool ua1 = ua && ak1 != kKeyInf, ua0 = ua && ak0 != kKeyInf;
+    uint32_t s1 = ball_slot(ta0.x, A.h1y), s0 = ball_slot(ta0.x, A.h0y);
+    const uint4 la1 = k2_ld(ua1 ? ea + (ball_row0(A.h1x) + s1) : dummy), la0 = k2_ld(ua0 ? ea + (ball_row0(A.h0x) + s0) : dummy);
+    const uint4 r1 = ball_resolve(ea, make_uint2(A.h1x, A.h1y), ta0.x, k2_row_or_none(ua1, la1), rm, s1);
+    const uint4 r0 = ball_resolve(ea, make_uint2(A.h0x, A.h0y), ta0.x, k2_row_or_none(ua0, la0), rm, s0);
+    bool xa = true;
+    const uint32_t r = k2_route_v(ak1, ak0, A.roadm & 0x1fffffffu, A.s, A.lim, A.bound, A.tmax, ta0, ta1, r1, r0, xa);
+    if (la) {
+      b.route[A.obase + q] = r;
+      if (!xa) k2_redo(sm, sm.owner[q]);
+    }
+    ta0 = nt0;
+    ta1 = nt1;
+  }
+}
+
+// With turn costs: the route of a transition from the tables, and what its turn weight needs --
+// nothing (U = 0: no turn costs, an invalid or direct route, a route the tables cannot decide), the
+// turn row of the exit that strictly gives the entry node its label (`row`, read after the
+// probes), or the walk (a tie between the exits).
 struct K2TurnKey {
   uint64_t row;      // need 1: the turn row's index (the winning exit's final slot)
   uint32_t r;        // route cm or kRouteInvalid
@@ -2431,9 +2223,9 @@ __device__ __forceinline__ K2TurnKey k2_turn_key(const K2SrcS& S, unsigned long 
                                                  uint32_t fac, const uint4& t0, const uint4& t1, const uint4& r1,
                                                  const uint4& r0, uint32_t s1, uint32_t s0) {
   const unsigned long long k10 = row_key0(r1), k00 = row_key0(r0), k11 = row_key1(r1), k01 = row_key1(r0);
-  const unsigned long long l10 = k10 != kKeyInf ? rk1 + k10 : kKeyInf, l00 = k00 != kKeyInf ? rk0 + k00 : kKeyInf;
-  const unsigned long long l11 = k11 != kKeyInf ? rk1 + k11 : kKeyInf, l01 = k01 != kKeyInf ? rk0 + k01 : kKeyInf;
-  const unsigned long long lab0 = l00 < l10 ? l00 : l10, lab1 = l01 < l11 ? l01 : l11;
+  const unsigned long long l10 = exit_label(rk1, k10), l00 = exit_label(rk0, k00);
+  const unsigned long long l11 = exit_label(rk1, k11), l01 = exit_label(rk0, k01);
+  const unsigned long long lab0 = l00 < l10 ? l00 : l10, lab1 = l01 < l11 ? l01 : l11;   // (ball_label)
   const uint4 a0 = make_uint4(S.roadm & 0x1fffffffu, S.s, 0u, 0u);
   int combo = -1;
   const unsigned long long key = route_key_vals(a0, t0, t1, lab0, lab1, &combo);
@@ -2469,41 +2261,32 @@ __device__ __forceinline__ uint32_t k2_turn_weight(const K2TurnKey& k, uint32_t 
 // the exits, a row without its sum: 1.3 % of C2's transitions) goes to a list that k_turn_walks
 // walks right after this kernel, one lane each: the walk's registers (86 VGPRs with it in this
 // loop, 60 without) stay out of this kernel.
-typedef unsigned int k2_v2 __attribute__((ext_vector_type(2)));
-typedef const k2_v2 __attribute__((address_space(1)))* k2_trow;
 template <class SM>
 __device__ __forceinline__ void k2_phase2_turn1(const DevGraph& g, SM& sm, const DevBatch& b, uint32_t n, uint32_t rm,
                                                 k2_gptr dummy, uint32_t t0i) {
-  const k2_trow tdummy = (k2_trow)(const void*)b.cand_desc;
   for (uint32_t q = threadIdx.x; q < n; q += kK2Threads) {
     const uint32_t o = sm.owner[q];
     const K2SrcS& A = sm.src[o];
     const bool la = A.bound != kNone;
     const uint32_t di = A.dbase + q;   // = pair * 16 + target
     const uint32_t p = di >> 4;
-    const uint4* pda = b.cand_desc + 2 * (uint64_t)di;
-    const uint4 ta0 = k2_ld((k2_gptr)(const void*)pda);
-    const uint2 ta1 = k2_ld2((k2_gptr2)(const void*)(reinterpret_cast<const uint2*>(pda + 1) + 1));
+    uint4 ta0, ta1;
+    k2_target(b, A, q, ta0, ta1);
     const uint32_t road = A.roadm & 0x1fffffffu;
     const uint32_t fac = b.pair_info[p].w, hw = g.road_head[road];
     const double gc = b.gc[p];
-    const unsigned long long ak1 = (unsigned long long)A.rk1h << 32 | A.rk1l, ak0 = (unsigned long long)A.rk0h << 32 | A.rk0l;
+    const unsigned long long ak1 = A.rk1(), ak0 = A.rk0();
     const bool ua = la && ta0.w != 0u;
-    const bool ua1 = ua && ak1 != kKeyInf, ua0 = ua && ak0 != kKeyInf;
     const uint32_t mode = A.roadm >> 29;
     const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)sm.ent_mode[mode];
     const k2_trow tra = (k2_trow)(const void*)(uintptr_t)sm.trn_mode[mode];
-    const uint32_t h1s = ball_slot(ta0.x, A.h1y), h0s = ball_slot(ta0.x, A.h0y);
-    const uint64_t i1 = ball_row0(A.h1x) + h1s, i0 = ball_row0(A.h0x) + h0s;
-    const uint4 la1 = k2_ld(ua1 ? ea + i1 : dummy), la0 = k2_ld(ua0 ? ea + i0 : dummy);
     // (a pair without turn costs may be of a mode without turn rows: no row read)
-    const k2_v2 v1 = *(ua1 && fac ? tra + i1 : tdummy), v0 = *(ua0 && fac ? tra + i0 : tdummy);
-    uint32_t s1 = h1s, s0 = h0s;
-    const uint4 r1 = ball_resolve_at_g(ea, make_uint2(A.h1x, A.h1y), ta0.x, k2_row_or_none(ua1, la1), rm, s1);
-    const uint4 r0 = ball_resolve_at_g(ea, make_uint2(A.h0x, A.h0y), ta0.x, k2_row_or_none(ua0, la0), rm, s0);
-    const K2TurnKey k = k2_turn_key(A, ak1, ak0, fac, ta0, make_uint4(0u, 0u, ta1.x, ta1.y), r1, r0, s1, s0);
-    k2_v2 w = k.e1 ? v1 : v0;
-    if (k.need == 1u && (k.e1 ? s1 != h1s : s0 != h0s)) w = tra[k.row];   // resolved past a collision
+    const BallRows R = ball_rows<true>(ea, dummy, make_uint2(A.h1x, A.h1y), make_uint2(A.h0x, A.h0y),
+                                       ua && ak1 != kKeyInf, ua && ak0 != kKeyInf, ta0.x, rm, tra, fac != 0u);
+    const K2TurnKey k = k2_turn_key(A, ak1, ak0, fac, ta0, ta1, R.r1, R.r0, R.s1, R.s0);
+    k2_v2 w = k.e1 ? R.v1 : R.v0;
+    if (k.need == 1u && (k.e1 ? R.s1 != ball_slot(ta0.x, A.h1y) : R.s0 != ball_slot(ta0.x, A.h0y)))
+      w = tra[k.row];   // resolved past a collision
     const uint32_t U = k2_turn_weight(k, hw, w.x, w.y, sm.tw16);
     if (!la) continue;
     if (U != kNone) {
@@ -2524,63 +2307,36 @@ __device__ __forceinline__ void k2_phase2_turn1(const DevGraph& g, SM& sm, const
   }
 }
 
-// The turn weights K2 left to walk (each K2 block's region of b.walk), one lane each: the item again as
-// k_routes_ball2's phase 1 forms it, the route with both exits' turn rows at their first-probe
-// slots, and the walk through the tables (k2_route_turn / canonical_turns).  A route the tables
-// cannot decide hands its item to the search tiers, which run next.
-// one walked turn weight: item t's route to its pair's target j (ro: its route index, known to the
-// marker scan; kNone: from the item)
+// One turn weight that K2 left to walk: item t's route to its pair's target j.  The item's record
+// is formed as k_routes_ball2's phase 1 forms it and the route decided by the same k2_turn_key.
+// K2 lists a route only when k2_turn_weight gave kNone, that is with need != 0 and either a tie
+// between the exits or a turn row without its sum: its weight is never the row's, so the walk
+// (canonical_turns through the tables) is the only way here and no turn row is read.  A route the
+// tables cannot decide hands its item to the search tiers, which run next.
 __device__ void k2_walk_one(const DevGraph& g, const DevBatch& b, uint32_t t, uint32_t j) {
   const uint32_t rm = g.ball_road_mask;
-  const k2_gptr dummy = (k2_gptr)(const void*)b.cand_desc;
-  const k2_trow tdummy = (k2_trow)(const void*)b.cand_desc;
-  const uint32_t p = b.src_item[t];
-  const uint4 pi = b.pair_info[p];
-  const uint32_t i = t - b.src_off[p];
-  const uint32_t KB = (pi.z >> 8) & 0xffu;
-  const uint64_t ro = (uint64_t)b.trans_off[p] + i * KB + j;
-  const uint64_t arow = ((uint64_t)(p - 1) * kMaxCand + i) * 2;
-  const uint4 a0 = b.cand_desc[arow], a1 = b.cand_desc[arow + 1];
-  const int mode = (int)(pi.z >> 16);
-  K2Src A;
-  exit_keys(a0, pi.x, A.rk1, A.rk0);
-  A.lim = ball_exact_limit(pi.x, g.ball_radius[mode], A.rk1, A.rk0);
-  const uint2* hp = g.ball_hdr[mode];
-  A.h1 = A.rk1 != kKeyInf ? hp[a1.y] : make_uint2(0u, 1u);
-  A.h0 = A.rk0 != kKeyInf ? hp[a1.x] : make_uint2(0u, 1u);
-  A.ent = (unsigned long long)(uintptr_t)g.ball_ent[mode];
-  A.road = a0.x;
-  A.s = a0.y;
-  A.bound = pi.x;
-  A.tmax = pi.y;
-  K2Turn T;
-  T.fac = pi.w;
-  T.trn = (unsigned long long)(uintptr_t)g.ball_turn[mode];
-  T.hw = g.road_head[a0.x];
-  T.n0 = a1.x;
-  T.n1 = a1.y;
-  T.mode = (uint32_t)mode;
-  T.pad = 0u;
-  const k2_gptr da = (k2_gptr)(const void*)(b.cand_desc + 2 * ((uint64_t)p * kMaxCand + j));
+  const K2Item it = k2_item(b, t);
+  const uint64_t ro = (uint64_t)it.base + it.i * it.KB + j;
+  const uint4 a0 = b.cand_desc[it.arow], a1 = b.cand_desc[it.arow + 1];
+  const BallExits x = ball_exits(g, a0, a1, it.bound, it.mode);
+  const K2SrcS A = k2_src(it, x, a0);
+  const k2_gptr da = (k2_gptr)(const void*)(b.cand_desc + 2 * ((uint64_t)it.p * kMaxCand + j));
   const uint4 ta0 = k2_ld(da), ta1 = k2_ld(da + 1);
-  const double gc = b.gc[p];
   const bool ua = ta0.w != 0u;
-  const bool ua1 = ua && A.rk1 != kKeyInf, ua0 = ua && A.rk0 != kKeyInf;
-  const uint32_t h1s = ball_slot(ta0.x, A.h1.y), h0s = ball_slot(ta0.x, A.h0.y);
-  const uint64_t i1 = ball_row0(A.h1.x) + h1s, i0 = ball_row0(A.h0.x) + h0s;
-  const k2_gptr ea = (k2_gptr)(const void*)(uintptr_t)A.ent;
-  const k2_trow tra = (k2_trow)(const void*)(uintptr_t)T.trn;
-  const uint4 la1 = k2_ld(ua1 ? ea + i1 : dummy), la0 = k2_ld(ua0 ? ea + i0 : dummy);
-  const k2_v2 v1 = *(ua1 && T.fac ? tra + i1 : tdummy), v0 = *(ua0 && T.fac ? tra + i0 : tdummy);
-  uint32_t s1 = h1s, s0 = h0s;
-  const uint4 r1 = ball_resolve_at_g(ea, A.h1, ta0.x, k2_row_or_none(ua1, la1), rm, s1);
-  const uint4 r0 = ball_resolve_at_g(ea, A.h0, ta0.x, k2_row_or_none(ua0, la0), rm, s0);
+  const BallRows R = ball_rows<false>((k2_gptr)(const void*)g.ball_ent[it.mode], (k2_gptr)(const void*)b.cand_desc, x.h1,
+                                      x.h0, ua && x.rk1 != kKeyInf, ua && x.rk0 != kKeyInf, ta0.x, rm);
+  const K2TurnKey k = k2_turn_key(A, x.rk1, x.rk0, it.pi.w, ta0, ta1, R.r1, R.r0, R.s1, R.s0);
+  uint32_t U = 0u;
   bool ok = true;
-  double d = 0.0;
-  b.route[ro] = k2_route_turn(g, A, T, ta0, ta1, r1, r0, s1, s0, h1s, h0s, make_uint2(v1.x, v1.y),
-                              make_uint2(v0.x, v0.y), g.turn_w, gc, ok, d);
-  b.route_d[ro] = d;
-  if (!ok) link_append<RoutesStage>(b, kLinkBallToSearch, t);
+  if (k.need != 0u) {
+    const BallPathLabels lab{g.ball_ent[it.mode], x.h1, x.h0, x.rk1, x.rk0, rm};
+    TableCursor c{lab, R.r1, R.r0};
+    U = canonical_turns(g, c, it.mode, g.road_head[a0.x], a1.y, a1.x, x.rk1, x.rk0, ta0.x, k.side ? ta1.y : ta1.x, k.side,
+                        kTableTurnSteps, ok);
+  }
+  b.route[ro] = k.r;
+  b.route_d[ro] = route_term(k.r, U, it.pi.w, b.gc[it.p]);
+  if (!k.exact || !ok) link_append<RoutesStage>(b, kLinkBallToSearch, t);
 }
 // (launched with K2's grid and n_arg, one block per K2 block: the block's region of b.walk)
 #ifndef RM_WALK_THREADS
@@ -2634,8 +2390,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
   const uint32_t tl = min(n_items, t0i + kK2Items) - 1u;              // last item of the block
   const bool live = threadIdx.x < (uint32_t)kK2Items && t <= tl;   // (items <= threads per block)
   // ---- phase 1: one lane per item
-  uint32_t KB = 0, ob = 0, pq = 0, md = 0;
-  K2Src S;
+  uint32_t KB = 0, ob = 0, pq = 0;
+  K2SrcS z;
   if (threadIdx.x == 0) {   // each mode's table rows and turn rows (a mode without: a valid dummy array)
 #pragma unroll
     for (int m = 0; m < 5; ++m) {
@@ -2645,35 +2401,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
     }
   }
   if (live) {
-    const uint32_t p = b.src_item[t];
-    pq = p;
-    const uint4 pi = b.pair_info[p];
-    const uint32_t i = t - b.src_off[p];
-    KB = (pi.z >> 8) & 0xffu;
-    ob = b.trans_off[p] + i * KB;
-    const uint64_t arow = ((uint64_t)(p - 1) * kMaxCand + i) * 2;
-    const uint4 a0 = b.cand_desc[arow], a1 = b.cand_desc[arow + 1];
-    const int mode = (int)(pi.z >> 16);
-    md = (uint32_t)mode;
-    exit_keys(a0, pi.x, S.rk1, S.rk0);
-    // the mode's tables answer any bound: beyond their radius, the routes they decide
-    const bool fits = (g.ball_mask >> mode) & 1u;
-    S.lim = ball_exact_limit(pi.x, g.ball_radius[mode], S.rk1, S.rk0);
-    S.h1 = S.h0 = make_uint2(0u, 1u);
-    if (fits) {   // both headers loaded together, then kept where the exit is usable
-      const uint2* hp = g.ball_hdr[mode];
-      const uint2 x1 = hp[a1.y], x0 = hp[a1.x];
-      if (S.rk1 != kKeyInf) S.h1 = x1;
-      if (S.rk0 != kKeyInf) S.h0 = x0;
-    }
-    S.road = a0.x;
-    S.s = a0.y;
-    S.bound = pi.x;
-    S.tmax = pi.y;
+    const K2Item it = k2_item(b, t);
+    pq = it.p;
+    KB = it.KB;
+    ob = it.base + it.i * KB;
+    const uint4 a0 = b.cand_desc[it.arow], a1 = b.cand_desc[it.arow + 1];
+    const BallExits x = ball_exits(g, a0, a1, it.bound, it.mode);
+    z = k2_src(it, x, a0);
     bool turn_ok = true;
-    if constexpr (TURN) turn_ok = !pi.w || ((g.ball_turn_mask >> mode) & 1u);   // no turn rows: the search tiers weigh the turns
-    if (!fits || S.h1.y == 0u || S.h0.y == 0u || !turn_ok) {   // the search tiers take it (they run later)
-      S.bound = kNone;
+    if constexpr (TURN) turn_ok = !it.pi.w || ((g.ball_turn_mask >> it.mode) & 1u);   // no turn rows: the search tiers weigh the turns
+    if (!x.tables() || !turn_ok) {   // the search tiers take it (they run later)
+      z.bound = kNone;
       link_append<RoutesStage>(b, kLinkBallToSearch, t);
     }
   }
@@ -2697,18 +2435,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
   }
   if (live) {
     const uint32_t rel = wbase + incl - KB;
-    K2SrcS z;
     z.dbase = pq * kMaxCand - rel;
     z.obase = ob - rel;
-    z.h1x = S.h1.x; z.h1y = S.h1.y;
-    z.h0x = S.h0.x; z.h0y = S.h0.y;
-    z.rk1l = (uint32_t)S.rk1; z.rk1h = (uint32_t)(S.rk1 >> 32);
-    z.rk0l = (uint32_t)S.rk0; z.rk0h = (uint32_t)(S.rk0 >> 32);
-    z.roadm = S.road | md << 29;
-    z.s = S.s;
-    z.bound = S.bound;
-    z.tmax = S.tmax;
-    z.lim = S.lim;
     sm.src[threadIdx.x] = z;
     for (uint32_t j = 0; j < KB; ++j) sm.owner[rel + j] = (uint8_t)threadIdx.x;
   }
@@ -2739,14 +2467,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(TURN ?
 // that outgrows the registers is queued (as its item) for the LDS lane tier.
 // With `listed`, thread q takes the q-th item the ball tier handed over (kLinkBallToSearch).
 constexpr uint64_t kListedGrid = 4096;   // blocks of a grid-stride launch over hand-over lists
-
-// K2 item t decoded: pair slot, source rank, the pair's first route, pair_info, its fields, the source's cand_desc row
-struct K2Item { uint32_t p, i, base; uint4 pi; uint32_t bound, tmax, KB; int mode; uint64_t arow; };
-__device__ __forceinline__ K2Item k2_item(const DevBatch& b, uint32_t t) {
-  const uint32_t p = b.src_item[t], i = t - b.src_off[p];
-  const uint4 pi = b.pair_info[p];
-  return {p, i, b.trans_off[p], pi, pi.x, pi.y, (pi.z >> 8) & 0xffu, (int)(pi.z >> 16), ((uint64_t)(p - 1) * kMaxCand + i) * 2};
-}
 
 // TURN: compiled with the turn-weight walks (rule 3b) only for batches with turn costs (they
 // cost the plain tier registers: scratch 12 -> 64 bytes per lane)
@@ -2923,21 +2643,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
   const uint32_t i = (uint32_t)ci, j = (uint32_t)cj;
   const uint4 a0 = b.cand_desc[((p - 1) * kMaxCand + i) * 2], a1 = b.cand_desc[((p - 1) * kMaxCand + i) * 2 + 1];
   const uint4 b0 = b.cand_desc[(p * kMaxCand + j) * 2], b1 = b.cand_desc[(p * kMaxCand + j) * 2 + 1];
-  unsigned long long rk1, rk0;
-  exit_keys(a0, bound, rk1, rk0);
-  const bool fits = (g.ball_mask >> mode) & 1u;   // beyond the radius: when the route is exact (ball_exact_limit)
-  uint2 h1 = make_uint2(0u, 1u), h0 = h1;
-  if (fits) {   // both headers loaded together
-    const uint2* hp = g.ball_hdr[mode];
-    const uint2 x1 = hp[a1.y], x0 = hp[a1.x];
-    if (rk1 != kKeyInf) h1 = x1;
-    if (rk0 != kKeyInf) h0 = x0;
-  }
-  if (!fits || h1.y == 0u || h0.y == 0u) {
+  const BallExits x = ball_exits(g, a0, a1, bound, mode);
+  if (!x.tables()) {
     link_append<PathsStage>(b, kLinkBallToSearch, (uint32_t)p);
     return;
   }
-  const BallPathLabels lab{g.ball_ent[mode], h1, h0, rk1, rk0, g.ball_road_mask};
+  const unsigned long long rk1 = x.rk1, rk0 = x.rk0;
+  const BallPathLabels lab{g.ball_ent[mode], x.h1, x.h0, rk1, rk0, g.ball_road_mask};
   // the target road's rows once for both entry labels (and the walk's first node)
   uint4 r1 = make_uint4(kNone, kBallNoDist, kBallNoDist, 0u), r0 = r1;
   if (d_spf(b0) || d_spr(b0)) lab.rows(b0.x, r1, r0);
@@ -2945,8 +2657,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RM_PAT
   const unsigned long long lab1 = d_spr(b0) ? ball_label(rk1, row_key1(r1), rk0, row_key1(r0)) : kKeyInf;
   int combo = -1;
   const unsigned long long key = route_key_vals(a0, b0, b1, lab0, lab1, &combo);
-  const uint32_t lim = ball_exact_limit(bound, g.ball_radius[mode], rk1, rk0);
-  if (lim != kNone && (key == kKeyInf || key_dist(key) > lim)) {   // not decided by the tables
+  if (x.lim != kNone && (key == kKeyInf || key_dist(key) > x.lim)) {   // not decided by the tables (ball_exact_limit)
     link_append<PathsStage>(b, kLinkBallToSearch, (uint32_t)p);
     return;
   }
@@ -4633,7 +4344,7 @@ __global__ void k_ball_lookup(DevGraph g, int mode, uint64_t n, const uint32_t* 
   if (h.y) {
     const uint4* ent = g.ball_ent[mode];
     const uint32_t rm = g.ball_road_mask;
-    const uint4 e = ball_resolve(ent, h, road[i], ent[ball_row0(h.x) + ball_slot(road[i], h.y)], rm);
+    const uint4 e = ball_row(ent, h, road[i], rm);
     if (e.x != kNone && (e.x & rm) == road[i]) {
       k0 = row_key0(e);
       k1 = row_key1(e);
@@ -4673,7 +4384,7 @@ __device__ uint32_t ball_turn_word(const DevGraph& g, int mode, uint32_t x, cons
         const uint32_t inf = g.in_info[q];
         if (!edge_ok(inf, acc)) continue;
         const uint32_t r2 = rr.z >> 1;
-        const uint4 eu = ball_resolve(ent, h, r2, ent[ball_row0(h.x) + ball_slot(r2, h.y)], rm);
+        const uint4 eu = ball_row(ent, h, r2, rm);
         const unsigned long long ku = (rr.z & 1u) ? row_key1(eu) : row_key0(eu);
         if (ku != kKeyInf && ku + make_key(rr.w, time_ms_dev(rr.w, mode_speed_dkph(mode, inf & 0xffffu))) == kv) {
           rec = rr;
@@ -4690,7 +4401,7 @@ __device__ uint32_t ball_turn_word(const DevGraph& g, int mode, uint32_t x, cons
     v = rec.y;
     if (v == x) return T | hs << kTurnHeadShift;
     side = rev;   // the edge's source: node0 of its road when it runs forward
-    e = ball_resolve(ent, h, r2, ent[ball_row0(h.x) + ball_slot(r2, h.y)], rm);
+    e = ball_row(ent, h, r2, rm);
     kv = side ? row_key1(e) : row_key0(e);
     if (e.x == kNone || kv == kKeyInf) return kTurnNone;
   }

@@ -137,8 +137,7 @@ enum CtlWord : int {
   kCtlPathsGroupToWave512 = 12, // paths: the same
   kCtlWave512ToWave4096 = 13,   // routes: 512-slot tier -> 4096-slot tier
   kCtlPathsWave512ToWave4096 = 14,   // paths: the same
-  kCtlWalkOverflow = 15,        // a K2 block's walk list overflowed (k_turn_walks_marked reads them
-                                // all); K2's walked turn weights under RM_K2_STATS
+  kCtlWalkOverflow = 15,        // a K2 block's walk list overflowed (k_turn_walks_marked reads them all)
 };
 static_assert(kCtlWalkOverflow + 1 == kCtlWords, "one name per control word");
 // Gate bits of DevBatch::gate: what a run without read-backs checks on the device instead (the host

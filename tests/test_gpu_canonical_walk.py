@@ -20,8 +20,14 @@ and on a one-way chain the search labels only the nodes between source and targe
 Two-way chain: traces of eleven points, 40 s apart, exactly on nodes n, n + 3, ... (n = 1, 2, 3).
 Every candidate sits at an end of its road (s = 0 or s = 6856).  Such a source ties its two exits at
 the target's entry node (the route from the far exit runs back along the source road), a tie has no
-turn row to read (k2_route_turn), so with 500 m tables K2 lists these routes for k_turn_walks, which
+turn row to read (k2_turn_key: need 2), so with 500 m tables K2 lists these routes for k_turn_walks, which
 walks them through the tables.  No counter shows that walk; the listing follows from the tie.
+
+Dense two-way chain: the same chain at half the spacing (node i at lon i * 0.00027, lat 0.00015 *
+(i & 1), roads of 3,433 cm) under a 200 m search radius, six traces of ten points on nodes n, n + 3,
+...  Up to 14 candidates a point, all at road ends, give so many tied routes that some K2 block lists
+more than kWalkPerBlock = 512 of them whatever the item order: the rest are marked in place and
+walked by k_turn_walks_marked.
 """
 import numpy as np
 import pytest
@@ -39,14 +45,19 @@ ROAD_CM = 6856
 _cache = {}
 
 
-def _node(i):
-    return i * DLON, DLAT * (i & 1)
+DENSE = (0.00027, 0.00015)   # the dense chain's node spacing
+DENSE_ROAD_CM = 3433
+WALK_PER_BLOCK, K2_ITEMS = 512, 256   # engine.hip kWalkPerBlock, kK2Items
 
 
-def _chain_osm(oneway):
+def _node(i, d=(DLON, DLAT)):
+    return i * d[0], d[1] * (i & 1)
+
+
+def _chain_osm(oneway, d=(DLON, DLAT)):
     rows = ["<?xml version='1.0' encoding='UTF-8'?>", '<osm version="0.6" generator="hand">']
     for i in range(N_WAYS + 1):
-        lon, lat = _node(i)
+        lon, lat = _node(i, d)
         rows.append(' <node id="%d" lat="%.7f" lon="%.7f"/>' % (i + 1, lat, lon))
     for k in range(N_WAYS):
         rows.append(' <way id="%d">' % (100 + k))
@@ -169,5 +180,68 @@ def test_twoway_tied_exits_walk_the_tables(built_lib, tmpdir_session, radius):
     if radius:
         assert tiers["ball_to_search"] == 0, tiers
     assert c["chained"] >= 10 and _turned(ref) > 0, c
+    bm.close()
+    eng.close()
+
+
+def _dense_case(built_lib, tmpdir_session):
+    if "dense" not in _cache:
+        osm = tmpdir_session / "walk_dense.osm"
+        osm.write_text(_chain_osm(False, DENSE))
+        path = world.import_osm(str(osm), str(tmpdir_session / "walk_dense.rmg"), cell_m=50.0)
+        g = graphfile.load(path)
+        assert len(g["road_len_cm"]) == N_WAYS and (np.asarray(g["road_len_cm"]) == DENSE_ROAD_CM).all()
+        # road ids ascend along the chain (what "further along" below means)
+        west = np.minimum(g["node_lon"][g["road_node0"]], g["node_lon"][g["road_node1"]])
+        assert (np.diff(west) > 0).all()
+        tr = _traces([[_node(n + 3 * q, DENSE) for q in range(10)] for n in (2, 1, 3, 2, 1, 3)], 40.0)
+        opts = engine.default_options(1, turn_penalty_factor=200.0, search_radius=200.0)
+        T = len(tr["trace_off"]) - 1
+        ref = mo.match(g, mo.Batch(tr["trace_off"], tr["lon"], tr["lat"], tr["time"], tr["accuracy"], opts,
+                                   np.zeros(T, np.uint32)))
+        _cache["dense"] = (path, tr, opts, ref)
+    return _cache["dense"]
+
+
+def _tied_routes(tr, ref):
+    """(items, tied) from the reference alone: the (pair, source) items K2 takes, and the valid routes
+    from a source at s == 0 to a road further along the chain or from one at s == length to a road
+    further back -- the far exit's route runs back along the source road, so both exits give the
+    entry node the same label."""
+    items = tied = 0
+    for k in range(len(tr["trace_off"]) - 1):
+        o = int(tr["trace_off"][k])
+        for p in range(o + 1, o + int(ref["n_states"][k])):
+            ka, kb = int(ref["cand_n"][p - 1]), int(ref["cand_n"][p])
+            items += ka
+            route = ref["route"][int(ref["trans_off"][p]):][:ka * kb].reshape(ka, kb)
+            src_road, src_s = ref["cand_road"][p - 1, :ka, None], ref["cand_s"][p - 1, :ka, None]
+            dst_road = ref["cand_road"][p, None, :kb]
+            tie = ((src_s == 0) & (dst_road > src_road)) | ((src_s == DENSE_ROAD_CM) & (dst_road < src_road))
+            tied += int((tie & (route != 0xffffffff)).sum())
+    return items, tied
+
+
+@pytest.mark.parametrize("small", [False, True], ids=["ordinary", "small"])
+def test_dense_twoway_overflows_a_block_walk_list(built_lib, tmpdir_session, monkeypatch, small):
+    """More tied routes than all K2 blocks can list (512 each): some block's list overflows, its
+    further walks are marked in place and k_turn_walks_marked walks them.  Every route is the
+    tables' and every distance term the oracle's, on the ordinary run path and on the small one."""
+    if small:
+        monkeypatch.delenv("RM_SMALL_BATCH_POINTS", raising=False)
+    else:
+        monkeypatch.setenv("RM_SMALL_BATCH_POINTS", "0")
+    path, tr, opts, ref = _dense_case(built_lib, tmpdir_session)
+    items, tied = _tied_routes(tr, ref)
+    blocks = -(-items // K2_ITEMS)
+    print("dense two-way, small %s: points %d items %d blocks %d tied %d cand_n max %d" %
+          (small, int(tr["trace_off"][-1]), items, blocks, tied, int(ref["cand_n"].max())))
+    assert tied > WALK_PER_BLOCK * blocks, (items, tied)
+    eng, bm = _run(path, tr, opts, 1000.0)
+    tiers = bm.route_tiers()
+    print(tiers)
+    c = compare_all(bm, ref, tr["trace_off"])
+    assert tiers["ball_to_search"] == 0, tiers
+    assert c["chained"] == int(tr["trace_off"][-1]) - (len(tr["trace_off"]) - 1), c   # every transition chained
     bm.close()
     eng.close()

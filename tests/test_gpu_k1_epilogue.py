@@ -1,5 +1,5 @@
 """K1's cooperative epilogue: the lane tier stages a wave's candidates in LDS and builds their
-descriptors a lane per candidate (engine.hip k_candidates_lane, RM_K1_EPILOGUE).
+descriptors a lane per candidate (engine.hip k_candidates_lane).
 
 Every case runs the C1 world with a batch above 4,096 points, so the lane tier runs (below that
 K1 is one wave per state), and compares with the oracle: candidates bit for bit and, through

@@ -678,6 +678,47 @@ rm_comm* rm_comm_init_host(int nranks, int rank, rm_host_allgather_fn fn, void* 
  * rm_runner_tiles runs with an nranks communicator (the device filter uses the same function). */
 int rm_tile_file_owner(uint64_t bucket, uint32_t tile, int nranks);
 
+/* ---------------- the stream on several GPUs (DESIGN.md §3 rule 16) ----------------
+ * A stream of nranks ranks gives, file for file and byte for byte, the output of the one-rank stream
+ * over the same polls, and each file is written by exactly one rank.  Every rank makes the same
+ * calls on the same text (reading and keying are replicated, so the directories agree index for
+ * index); the sessions are sharded by vehicle, rm_vehicle_owner(directory index, nranks): a
+ * multiplicative hash, so first-seen order does not stripe the load; and just before a flush the
+ * tile rows go to the rank rm_tile_file_owner names for their file.
+ *
+ * rm_session_push_messages_sharded reads, keys and drops exactly as rm_session_push_messages (info,
+ * the dropped list and rm_session_messages_span are the same on every rank), then appends, triggers
+ * and matches only the points of the vehicles `rank` owns.  A window's arrival stays the index among
+ * all kept points of the call.  shard: [0] own points [1] foreign points.  rm_session_punctuate
+ * needs no change.
+ *
+ * A tile store numbers its add calls from 0 and keeps, beside every row, key = call << 32 | a: the
+ * triggering arrival of the row's report (rm_tilestore_add_session), the segment's index in the
+ * array (rm_tilestore_add).  Keys are kept from the store's first call below, or its first
+ * rm_tilestore_add_session of a session that was pushed sharded; a store that sees neither
+ * allocates and launches nothing for them.  (Rows added before that from a session never pushed
+ * sharded get their report's index for a: rows of one rank in that rank's order.)
+ *   rm_tilestore_export_rows   the rows held and their keys as a library-allocated blob (rm_free);
+ *                              the store keeps them
+ *   rm_tilestore_import_owned  clears the store and loads, of the n blobs (in rank order), the rows
+ *                              whose file `rank` owns, merged by one stable sort on the key -- the
+ *                              one-rank store's order exactly, so rm_tilestore_flush runs unchanged
+ *   rm_tilestore_exchange      export -> all-gather -> import on the device through `comm` (RCCL or
+ *                              the host transport; every rank calls it, padded to the largest count)
+ *   out: [0] rows before [1] rows sent away [2] rows received [3] rows held
+ *   rm_tilestore_exchange_time ms (HIP events) of the last import / exchange: partition, transport, merge
+ * Not supported: rm_snapshot_save of a store that keeps keys, and rm_snapshot_load into one, fail
+ * with a message (rows restored from a snapshot cannot be exported either); and ranks reading
+ * disjoint parts of the input, which would need order keys taken from the messages themselves. */
+int rm_vehicle_owner(uint32_t index, int nranks);
+int rm_session_push_messages_sharded(rm_session* s, rm_directory* dir, const rm_messages_desc* d, int nranks, int rank,
+                                     uint64_t out[8], uint64_t info[8], uint64_t shard[2]);
+int rm_tilestore_export_rows(rm_tilestore* t, char** blob, size_t* len);
+int rm_tilestore_import_owned(rm_tilestore* t, const char* const* blobs, const size_t* lens, uint32_t n, int nranks, int rank,
+                              uint64_t out[4]);
+int rm_tilestore_exchange(rm_tilestore* t, rm_comm* comm, uint64_t out[4]);
+int rm_tilestore_exchange_time(rm_tilestore* t, double ms[3]);
+
 /* ---------------- device memory helpers (histograms without a framework) ---------------- */
 int rm_device_alloc(size_t bytes, void** dev_ptr);
 int rm_device_free(void* dev_ptr);

@@ -252,6 +252,13 @@ PROTOTYPES = [
     ("rm_comm_barrier", C.c_int, [P]),
     ("rm_comm_init_host", P, [C.c_int, C.c_int, P, P, C.c_int]),
     ("rm_tile_file_owner", C.c_int, [C.c_uint64, C.c_uint32, C.c_int]),
+    ("rm_vehicle_owner", C.c_int, [C.c_uint32, C.c_int]),
+    ("rm_session_push_messages_sharded", C.c_int, [P, P, C.POINTER(RmMessagesDesc), C.c_int, C.c_int, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_export_rows", C.c_int, [P, C.POINTER(P), C.POINTER(C.c_size_t)]),
+    ("rm_tilestore_import_owned", C.c_int, [P, P, P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_exchange", C.c_int, [P, P, C.POINTER(C.c_uint64)]),
+    ("rm_tilestore_exchange_time", C.c_int, [P, C.POINTER(C.c_double)]),
     ("rm_device_alloc", C.c_int, [C.c_size_t, C.POINTER(P)]),
     ("rm_device_free", C.c_int, [P]),
     ("rm_device_memset", C.c_int, [P, C.c_int, C.c_size_t]),

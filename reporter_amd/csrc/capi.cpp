@@ -1679,7 +1679,9 @@ struct RcclTileComm final : TileComm {
     auto x = std::make_shared<uint64_t>(v);
     ncclComm_t n = nc;
     void* sc = scratch;
+    const int dev = c->device;
     comm_bounded(c, rank, nranks, "tile all-reduce", [=] {
+      RM_HIP(hipSetDevice(dev));   // (library mode runs this on a helper thread)
       RM_HIP(hipMemcpyAsync(sc, x.get(), 8, hipMemcpyHostToDevice, st));
       nccl_done(n, ncclAllReduce(sc, sc, 1, ncclUint64, ncclMax, n, st), "ncclAllReduce");
       RM_HIP(hipMemcpyAsync(x.get(), sc, 8, hipMemcpyDeviceToHost, st));
@@ -1689,7 +1691,9 @@ struct RcclTileComm final : TileComm {
   }
   void allgather(const void* send, void* recv, size_t bytes, hipStream_t st) override {
     ncclComm_t n = nc;
+    const int dev = c->device;
     comm_bounded(c, rank, nranks, "tile all-gather", [=] {
+      RM_HIP(hipSetDevice(dev));
       nccl_done(n, ncclAllGather(send, recv, bytes, ncclUint8, n, st), "ncclAllGather");
       RM_HIP(hipStreamSynchronize(st));
     });
@@ -1715,6 +1719,13 @@ struct HostTileComm final : TileComm {
     RM_HIP(hipStreamSynchronize(st));
   }
 };
+
+// the tile collectives over a communicator that has a GPU
+std::unique_ptr<TileComm> make_tile_comm(rm_comm* comm) {
+  if (comm->device < 0) throw std::runtime_error("the communicator has no GPU");
+  if (comm->host_fn) return std::make_unique<HostTileComm>(comm);
+  return std::make_unique<RcclTileComm>(comm);
+}
 }  // namespace
 
 extern "C" {
@@ -1801,11 +1812,7 @@ int rm_runner_tiles(rm_runner* r, const rm_tile_params* p, rm_comm* comm, char**
     for (char& ch : mode) ch = (char)std::toupper((unsigned char)ch);   // mode.upper() (:194)
     tp.mode = mode;
     std::unique_ptr<TileComm> tc;
-    if (comm) {
-      if (comm->device < 0) throw std::runtime_error("the communicator has no GPU");
-      if (comm->host_fn) tc = std::make_unique<HostTileComm>(comm);
-      else tc = std::make_unique<RcclTileComm>(comm);
-    }
+    if (comm) tc = make_tile_comm(comm);
     const std::string out = r->m->tiles(tp, tc.get());
     char* b = (char*)std::malloc(out.size() + 1);
     if (!b) throw std::bad_alloc();
@@ -1969,9 +1976,12 @@ int rm_directory_names(rm_directory* d, uint32_t first, uint32_t n, uint64_t* of
   });
 }
 
-int rm_session_push_messages(rm_session* s, rm_directory* dir, const rm_messages_desc* d, uint64_t out[8], uint64_t info[8]) {
+// nranks 0: the unsharded push
+static int push_messages(rm_session* s, rm_directory* dir, const rm_messages_desc* d, int nranks, int rank, uint64_t out[8],
+                         uint64_t info[8], uint64_t shard[2]) {
   return guarded([&] {
     if (!s || !dir) throw std::runtime_error("session or directory is NULL");
+    if (nranks && (nranks < 1 || rank < 0 || rank >= nranks)) throw std::runtime_error("session shard needs 0 <= rank < nranks");
     if (dir->d->device() != s->s->device()) throw std::runtime_error("the directory is on another device than the session");
     if (dir->d->max_vehicles() > s->s->n_vehicles())
       throw std::runtime_error("the directory's max_vehicles exceeds the session's n_vehicles");
@@ -1982,13 +1992,27 @@ int rm_session_push_messages(rm_session* s, rm_directory* dir, const rm_messages
     dir->d->assign(m);
     s->dir_ms = dir->d->last_ms();
     const LineGroups g = m.line_groups();
-    s->s->push_device(g.n_points, g.p_uuid, g.p_time, g.p_lon, g.p_lat, g.p_acc, nullptr, md.has_stamp != 0, md.stamp_ms, out);
+    if (nranks)
+      s->s->push_device_sharded(g.n_points, g.p_uuid, g.p_time, g.p_lon, g.p_lat, g.p_acc, nullptr, md.has_stamp != 0, md.stamp_ms,
+                                nranks, rank, out, shard);
+    else
+      s->s->push_device(g.n_points, g.p_uuid, g.p_time, g.p_lon, g.p_lat, g.p_acc, nullptr, md.has_stamp != 0, md.stamp_ms, out);
     if (info) {
       m.lines_info(info);
       info[7] = m.dropped_messages(nullptr);
     }
   });
 }
+
+int rm_session_push_messages(rm_session* s, rm_directory* dir, const rm_messages_desc* d, uint64_t out[8], uint64_t info[8]) {
+  return push_messages(s, dir, d, 0, 0, out, info, nullptr);
+}
+int rm_session_push_messages_sharded(rm_session* s, rm_directory* dir, const rm_messages_desc* d, int nranks, int rank,
+                                     uint64_t out[8], uint64_t info[8], uint64_t shard[2]) {
+  if (nranks < 1) return fail("session shard needs 0 <= rank < nranks");
+  return push_messages(s, dir, d, nranks, rank, out, info, shard);
+}
+int rm_vehicle_owner(uint32_t index, int nranks) { return vehicle_owner(index, nranks); }
 
 int rm_session_dropped_messages(rm_session* s, uint32_t* n, uint32_t chunk[64], uint64_t line[64], char* reasons, size_t reasons_len) {
   return guarded([&] {
@@ -2089,6 +2113,39 @@ int rm_tilestore_time(rm_tilestore* t, double ms[6]) {
   return guarded([&] {
     if (!t || !ms) throw std::runtime_error("tile store or ms is NULL");
     t->t->times(ms);
+  });
+}
+
+// the sharded stream's exchange (DESIGN.md §3 rule 16)
+int rm_tilestore_export_rows(rm_tilestore* t, char** blob, size_t* len) {
+  if (!blob || !len) return fail("blob/len is NULL");
+  *blob = nullptr;
+  *len = 0;
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    t->t->export_rows(blob, len);
+  });
+}
+int rm_tilestore_import_owned(rm_tilestore* t, const char* const* blobs, const size_t* lens, uint32_t n, int nranks, int rank,
+                              uint64_t out[4]) {
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    t->t->import_owned(blobs, lens, n, nranks, rank, out);
+  });
+}
+int rm_tilestore_exchange(rm_tilestore* t, rm_comm* comm, uint64_t out[4]) {
+  return guarded([&] {
+    if (!t) throw std::runtime_error("tile store is NULL");
+    if (!comm) throw std::runtime_error("communicator is NULL");
+    if (comm->device != t->t->device()) throw std::runtime_error("the communicator is on another device than the tile store");
+    const std::unique_ptr<TileComm> tc = make_tile_comm(comm);
+    t->t->exchange(*tc, out);
+  });
+}
+int rm_tilestore_exchange_time(rm_tilestore* t, double ms[3]) {
+  return guarded([&] {
+    if (!t || !ms) throw std::runtime_error("tile store or ms is NULL");
+    t->t->exchange_times(ms);
   });
 }
 

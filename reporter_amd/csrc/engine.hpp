@@ -402,6 +402,12 @@ class Session {
   // stage buffers.
   void push_device(uint64_t n, const uint32_t* d_vehicle, const double* d_time, const float* d_lon, const float* d_lat,
                    const float* d_acc, const long long* d_stamp, bool has_stamp, int64_t stamp, uint64_t out[8]);
+  // The masked push of a sharded stream (DESIGN.md §3 rule 16): of the n arrivals only those whose
+  // vehicle_owner(vehicle, nranks) is `rank` are appended, triggered and matched; a window's arrival
+  // stays the index among all n.  shard: the own points, the foreign points
+  void push_device_sharded(uint64_t n, const uint32_t* d_vehicle, const double* d_time, const float* d_lon, const float* d_lat,
+                           const float* d_acc, const long long* d_stamp, bool has_stamp, int64_t stamp, int nranks, int rank,
+                           uint64_t out[8], uint64_t shard[2]);
   void punctuate(int64_t timestamp_ms, uint64_t out[8]);
   // throws what a push of n arrivals would throw for lack of room, before anything is changed
   void check_room(uint64_t n) const;
@@ -418,6 +424,10 @@ class Session {
   // reports in HBM (n_reports() of them, complete when the call has returned)
   int device() const;
   const SessionReport* reports_device() const;
+  // ... the last call's windows in HBM (n_windows(), ordered as get_windows gives them), and whether
+  // a sharded push was ever made: the tile store then keys the rows it takes from here (rule 16)
+  const SessionWindow* windows_device() const;
+  bool sharded() const;
   // the stream snapshot (rule 15).  snapshot_pack: the store packed as get_store packs it (no
   // output of the stream changes), the non-empty vehicles ranked.  snapshot_room: the current
   // buffer with room for n points, for a session that holds none.  snapshot_loaded: n points and
@@ -497,6 +507,20 @@ class TileStore {
   // in, rows kept, tiles held, files written, blob bytes.  The store is empty afterwards.
   void flush(char** blob, size_t* len, uint64_t out[5]);
   void times(double ms[6]) const;   // upload, expand, sort, cull, text, download of the last call
+  // The sharded stream's exchange (DESIGN.md §3 rule 16).  Every row has a key beside it, add call
+  // << 32 | a (a session's report: its triggering arrival; host segments: the index in the array),
+  // kept from the first of these calls or the first add_session of a sharded session on; a store
+  // that sees neither allocates and launches nothing for keys.
+  // export_rows: *blob is malloc'd, the rows held and their keys; the store keeps them.
+  // import_owned: the store's contents are replaced by the rows of the n blobs (in rank order)
+  // whose file tile_file_owner gives to `rank`, merged by one stable sort on the key.
+  // exchange: the same with the rows all-gathered on the device through `comm`.
+  // out: rows before, rows sent away, rows received, rows held.
+  void export_rows(char** blob, size_t* len);
+  void import_owned(const char* const* blobs, const size_t* lens, uint32_t n, int nranks, int rank, uint64_t out[4]);
+  void exchange(struct TileComm& comm, uint64_t out[4]);
+  void exchange_times(double ms[3]) const;   // partition, transport, merge of the last import / exchange
+  bool keyed() const;
   int device() const;
   uint64_t rows_held() const;
   uint64_t capacity() const;

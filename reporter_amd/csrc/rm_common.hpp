@@ -344,6 +344,16 @@ RM_HD int tile_file_owner(uint64_t bucket, uint32_t tile, int nranks) {
   return (int)((h >> 33) % (unsigned long long)(nranks > 0 ? nranks : 1));
 }
 
+// Rank that holds a vehicle's session in the multi-rank stream (DESIGN.md §3 rule 16): every rank
+// numbers every vehicle through its directory, so the dense indices agree, and the owner is a
+// multiplicative (Fibonacci) hash of the index scaled to the rank count -- not index % nranks,
+// which would stripe the load in first-seen order.  Shared by the session's owned-point mask
+// (sessions.hip k_sess_own) and the host export rm_vehicle_owner.
+RM_HD int vehicle_owner(uint32_t index, int nranks) {
+  const uint32_t h = index * 0x9e3779b1u;
+  return (int)(((unsigned long long)h * (unsigned long long)(nranks > 0 ? nranks : 1)) >> 32);
+}
+
 #endif
 
 // A node's table starts at row 2 * hdr.x of its mode's entry array (hdr = {first row / 2,

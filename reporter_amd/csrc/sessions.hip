@@ -51,6 +51,7 @@ enum SessCtr : int {
   kSErr,           // bit 0 vehicle index out of range, 1 NaN time, 2 output overflow
   kSTotal,         // points in the store after the append
   kSActive,        // vehicles with new arrivals
+  kSOwn,           // a sharded push: the points of the call whose vehicle this rank owns
   kSNumCtr = 16
 };
 
@@ -83,6 +84,21 @@ __global__ void k_sess_keys(uint64_t n, const uint32_t* veh, const double* time,
   key[j] = ((unsigned long long)v << 32) | (unsigned long long)j;
 }
 
+// The masked push of a sharded stream (DESIGN.md §3 rule 16): the call's points whose vehicle this
+// rank owns, then their keys packed in arrival order.  A key keeps the point's index among all the
+// points of the call, so the copy reads the unmasked arrays and a window's arrival is the global one.
+__global__ void k_sess_own(uint64_t n, const uint32_t* veh, int nranks, int rank, uint32_t* flag) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) flag[j] = vehicle_owner(veh[j], nranks) == rank ? 1u : 0u;
+}
+__global__ void k_sess_own_pack(uint64_t n, const unsigned long long* key, const uint32_t* flag, const uint32_t* ofs,
+                                unsigned long long* out, uint32_t* ctr) {
+  const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  if (flag[j]) out[ofs[j]] = key[j];
+  if (j + 1 == n) ctr[kSOwn] = ofs[j] + flag[j];
+}
+
 // the new points of a vehicle are sorted[nstart[v] .. nend[v]) (both zeroed before: none)
 __global__ void k_sess_runs(uint64_t n, const unsigned long long* key, uint32_t nV, uint32_t* nstart, uint32_t* nend) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -100,7 +116,7 @@ __global__ void k_sess_tot(uint32_t nV, const uint32_t* cnt, const uint32_t* nst
 }
 
 // one thread per point: the kept old points [0, extent) of `src`, then the n new ones in sorted order
-__global__ void k_sess_copy(uint64_t extent, uint64_t n, uint32_t nV, PtBuf src, PtBuf dst, const uint32_t* off,
+__global__ void k_sess_copy(uint64_t extent, uint64_t n, uint64_t n_src, uint32_t nV, PtBuf src, PtBuf dst, const uint32_t* off,
                             const uint32_t* cnt, const uint32_t* noff, const uint32_t* nstart,
                             const unsigned long long* key, const float* b_lon, const float* b_lat, const double* b_time,
                             const float* b_acc) {
@@ -120,7 +136,7 @@ __global__ void k_sess_copy(uint64_t extent, uint64_t n, uint32_t nV, PtBuf src,
   if (j >= n) return;
   const unsigned long long k = key[j];
   const uint32_t v = (uint32_t)(k >> 32), a = (uint32_t)k;
-  if (v >= nV || a >= n) return;
+  if (v >= nV || a >= n_src) return;
   const uint64_t d = (uint64_t)noff[v] + cnt[v] + (j - nstart[v]);
   if (d >= dst.cap) return;
   dst.lon[d] = b_lon[a]; dst.lat[d] = b_lat[a]; dst.acc[d] = b_acc ? b_acc[a] : -1.0f; dst.time[d] = b_time[a];
@@ -363,6 +379,8 @@ struct Session::Impl {
   ScanScratch scr{kFull};
   uint64_t rep_bound = 0;     // host bound on the reports written so far in the call
   uint64_t n_win = 0, n_rep = 0, rounds = 0, triggers = 0, arrivals = 0;
+  int sh_nranks = 1, sh_rank = 0;   // the shard of the call under way (1, 0: every point is this rank's)
+  bool sharded = false;             // a sharded push has been made: a tile store fed from here keys its rows
   // HIP-event pairs of the call, by part (0 upload, 1 append, 2 trigger, 3 match, 4 trim)
   PartTimer timer;
   double ms[5] = {0, 0, 0, 0, 0};
@@ -451,9 +469,10 @@ struct Session::Impl {
     timer.harvest(ms);
     if (hctr[kSErr] & 4u) throw std::runtime_error("session output buffers overflowed");
   }
-  // lay the store out anew in the other buffer with the n sorted new points (key1) behind each
-  // vehicle's kept ones; the vehicles' state is untouched until commit()
-  void layout_and_copy(uint64_t n, const float* b_lon, const float* b_lat, const double* b_time, const float* b_acc,
+  // lay the store out anew in the other buffer with the n sorted new points (key1; their arrival
+  // indices run below n_src, the length of the b_ arrays) behind each vehicle's kept ones; the
+  // vehicles' state is untouched until commit()
+  void layout_and_copy(uint64_t n, uint64_t n_src, const float* b_lon, const float* b_lat, const double* b_time, const float* b_acc,
                        hipStream_t st) {
     RM_HIP(hipMemsetAsync(nstart, 0, nV * sizeof(uint32_t), st));
     RM_HIP(hipMemsetAsync(nend, 0, nV * sizeof(uint32_t), st));
@@ -463,7 +482,7 @@ struct Session::Impl {
     RM_HIP(hipMemcpyAsync(ctr + kSTotal, noff + nV, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
     ensure_buf(buf[1 - cur], extent + n);
     if (extent + n)
-      hipLaunchKernelGGL(k_sess_copy, dim3(grid(extent + n)), dim3(256), 0, st, extent, n, nV, buf[cur].view(),
+      hipLaunchKernelGGL(k_sess_copy, dim3(grid(extent + n)), dim3(256), 0, st, extent, n, n_src, nV, buf[cur].view(),
                          buf[1 - cur].view(), off, cnt, noff, nstart, key1, b_lon, b_lat, b_time, b_acc);
   }
   void commit(const long long* stamp, hipStream_t st) {
@@ -515,6 +534,8 @@ Session::~Session() {
 uint32_t Session::n_vehicles() const { return p_->nV; }
 int Session::device() const { return p_->m->eng_->device(); }
 const SessionReport* Session::reports_device() const { return p_->rep_s; }
+const SessionWindow* Session::windows_device() const { return p_->win_s; }
+bool Session::sharded() const { return p_->sharded; }
 uint64_t Session::n_reports() const { return p_->n_rep; }
 uint64_t Session::n_windows() const { return p_->n_win; }
 void Session::times(double ms[5]) const { for (int i = 0; i < 5; ++i) ms[i] = p_->ms[i]; }
@@ -704,26 +725,71 @@ void Session::push_device(uint64_t n, const uint32_t* d_vehicle, const double* d
   append(n, d_vehicle, d_time, d_lon, d_lat, d_acc, d_stamp, out);
 }
 
+void Session::push_device_sharded(uint64_t n, const uint32_t* d_vehicle, const double* d_time, const float* d_lon,
+                                  const float* d_lat, const float* d_acc, const long long* d_stamp, bool has_stamp, int64_t stamp,
+                                  int nranks, int rank, uint64_t out[8], uint64_t shard[2]) {
+  Impl& s = *p_;
+  if (nranks < 1 || rank < 0 || rank >= nranks) throw std::runtime_error("session shard needs 0 <= rank < nranks");
+  s.sh_nranks = nranks; s.sh_rank = rank;
+  try {
+    push_device(n, d_vehicle, d_time, d_lon, d_lat, d_acc, d_stamp, has_stamp, stamp, out);
+  } catch (...) {
+    s.sh_nranks = 1; s.sh_rank = 0;
+    throw;
+  }
+  s.sh_nranks = 1; s.sh_rank = 0;
+  s.sharded = true;
+  if (shard) { shard[0] = s.arrivals; shard[1] = n - s.arrivals; }
+}
+
 // push() behind its staging: the n arrivals lie in HBM.  They are copied into the store before the
 // first match round, which reuses the runner's workspace.
 void Session::append(uint64_t n, const uint32_t* d_veh, const double* d_time, const float* d_lon, const float* d_lat,
                      const float* d_acc, const long long* d_stamp, uint64_t out[8]) {
   Impl& s = *p_;
   hipStream_t st = s.m->stream_;
+  const auto check_input = [&s] {
+    if (s.hctr[kSErr] & 1u) throw std::runtime_error("session vehicle index out of range");
+    if (s.hctr[kSErr] & 2u) throw std::runtime_error("session point time is NaN");
+  };
   s.timer.tic(1, st);
   hipLaunchKernelGGL(k_sess_keys, dim3(grid(n)), dim3(256), 0, st, n, d_veh, d_time, s.nV, s.key0, s.ctr);
-  s.scr.sort_keys(s.key0.get(), s.key1.get(), n, st);
-  s.layout_and_copy(n, d_lon, d_lat, d_time, d_acc, st);
+  uint64_t m = n;   // the points this rank appends
+  if (s.sh_nranks > 1) {
+    // the owned points' keys packed in arrival order (the sort buffers of finish_call hold the
+    // flags and offsets: ensure_win(n) has sized them), one read of their count
+    if (s.sort_cap < n) s.ensure_sort(n);   // (push_device's ensure_win(n) has done it: held here against a reorder)
+    uint32_t* flag = s.sidx0;
+    uint32_t* ofs = s.sidx1;
+    hipLaunchKernelGGL(k_sess_own, dim3(grid(n)), dim3(256), 0, st, n, d_veh, s.sh_nranks, s.sh_rank, flag);
+    s.scr.scan<uint32_t>(flag, ofs, n, st);
+    hipLaunchKernelGGL(k_sess_own_pack, dim3(grid(n)), dim3(256), 0, st, n, (const unsigned long long*)s.key0,
+                       (const uint32_t*)flag, (const uint32_t*)ofs, s.key1, s.ctr);
+    s.timer.toc(st);
+    RM_HIP(hipGetLastError());
+    s.read_ctr(st);
+    check_input();   // (over every point of the call, owned or not: the ranks fail together)
+    m = s.hctr[kSOwn];
+    if (m > n) throw std::runtime_error("session owned-point count out of range");
+    std::swap(s.key0, s.key1);
+    if (m == 0) {   // nothing of this call is this rank's
+      s.hctr[kSActive] = 0;
+      rounds(false, out);
+      return;
+    }
+    s.timer.tic(1, st);
+  }
+  s.scr.sort_keys(s.key0.get(), s.key1.get(), m, st);
+  s.layout_and_copy(m, n, d_lon, d_lat, d_time, d_acc, st);
   s.timer.toc(st);
   RM_HIP(hipGetLastError());
   s.read_ctr(st);   // nothing of the session has changed yet: a bad input leaves it as it was
-  if (s.hctr[kSErr] & 1u) throw std::runtime_error("session vehicle index out of range");
-  if (s.hctr[kSErr] & 2u) throw std::runtime_error("session point time is NaN");
+  check_input();
   s.timer.tic(1, st);
   s.commit(d_stamp, st);
   s.timer.toc(st);
   s.extent = s.hctr[kSTotal];
-  s.arrivals = n;
+  s.arrivals = m;
   s.read_ctr(st);   // round 0's work list
   rounds(false, out);
 }
@@ -764,7 +830,7 @@ uint64_t Session::get_store(uint32_t* cnt, float* max_sep, int64_t* last_update,
   hipStream_t st = m.stream_;
   m.sync();
   // an append of nothing packs the store (holes of trimmed prefixes and dropped lists go)
-  s.layout_and_copy(0, nullptr, nullptr, nullptr, nullptr, st);
+  s.layout_and_copy(0, 0, nullptr, nullptr, nullptr, nullptr, st);
   RM_HIP(hipMemsetAsync(s.ctr + kSActive, 0, sizeof(uint32_t), st));
   s.commit(nullptr, st);
   s.read_ctr(st);
@@ -800,7 +866,7 @@ SessionSnap Session::snapshot_pack() {
   // get_store's pack, then the rank of every non-empty vehicle among them.  The error word is
   // the last call's (an overflow there has been thrown already): the pack sets no bit of it
   RM_HIP(hipMemsetAsync(s.ctr + kSErr, 0, sizeof(uint32_t), st));
-  s.layout_and_copy(0, nullptr, nullptr, nullptr, nullptr, st);
+  s.layout_and_copy(0, 0, nullptr, nullptr, nullptr, nullptr, st);
   RM_HIP(hipMemsetAsync(s.ctr + kSActive, 0, sizeof(uint32_t), st));
   s.commit(nullptr, st);
   hipLaunchKernelGGL(k_sess_live, dim3(grid(s.nV + 1ull)), dim3(256), 0, st, s.nV, (const uint32_t*)s.cnt, s.tot);

@@ -189,6 +189,8 @@ int common_device(Session* s, Directory* d, TileStore* t) {
 void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, size_t user_len, char** blob_out, size_t* len_out,
                    uint64_t out[6], double ms[6]) {
   if (user_len && !user) throw std::runtime_error("snapshot: user bytes are NULL");
+  // (rule 16: the format has no section for row keys, and a restored store could not rejoin its ranks)
+  if (t && t->keyed()) throw std::runtime_error("snapshot: a tile store that keeps row keys (a sharded stream's) cannot be saved");
   RM_HIP(hipSetDevice(common_device(s, d, t)));
   if (t) RM_HIP(hipStreamSynchronize(t->stream()));
   SessionSnap v;

@@ -14,6 +14,11 @@
 //           a wave builds the contiguous span of its 64 rows in LDS and streams it to the blob in
 //           aligned 16-byte stores (the unaligned head and tail byte-wise);
 //           one download of the blob.
+//   exchange  (rule 16, a stream on several ranks) a key per row beside the rows, call << 32 | a,
+//           written by k_ts_emit once the store keeps keys; every rank's rows and keys gathered
+//           (export / import through host blobs, or all-gathered through a TileComm), k_ts_own ->
+//           scan -> k_ts_own_pack -> one stable radix sort on the key -> k_ts_take: the store then
+//           holds the rows of the files it owns in the one-rank order, and flush runs unchanged.
 //
 // One stream, no graph, HIP events per stage.  Nothing loops over segments or rows on the host.
 #include <hip/hip_runtime.h>
@@ -23,6 +28,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "engine.hpp"
 #include "tile_cull.hpp"
@@ -38,12 +44,24 @@ constexpr uint64_t kTsMaxRows = 0x7fffffffull;   // (hipcub takes the item count
 constexpr double kTwo53 = 9007199254740992.0;
 
 // device counters (u64), mirrored in pinned memory
-enum TsCtr : int { kTKept = 0, kTSkipped, kTErr, kTTotal, kTTiles, kTFiles, kTRuns, kTKeptRows, kTBytes, kTNumCtr = 16 };
+enum TsCtr : int {
+  kTKept = 0, kTSkipped, kTErr, kTTotal, kTTiles, kTFiles, kTRuns, kTKeptRows, kTBytes,
+  kTOwnLo, kTOwnHi, kTOwned,   // the exchange: owned rows before and behind this rank's own rows, and of all
+  kTNumCtr = 16
+};
 
 struct SegSrc {   // segment j: {u64 id, u64 next_id, f64 min, f64 max, i32 length, i32 queue} at base + j * stride
   const char* base;
   uint32_t stride;
+  // a session's reports: the call's windows, for the triggering arrival of segment j's report (its
+  // window index lies at base + j * stride + kRepWindow); null: host segments
+  const SessionWindow* win;
+  uint32_t n_win;
 };
+constexpr uint32_t kRepWindow = (uint32_t)offsetof(SessionReport, window);
+constexpr unsigned long long kTsPadKey = ~0ull;   // the key of a padding row of the exchange (no row has it: calls < 2^32 - 1)
+constexpr uint64_t kTsBlobMagic = 0x31574f5253544d52ull;   // "RMTSROW1"
+constexpr uint64_t kTsBlobHead = 32;   // magic, rows, quantisation, 0; then the rows; then their keys
 struct SegIn {
   uint64_t id, next_id;
   double mn, mx;
@@ -96,8 +114,9 @@ __global__ void k_ts_count(SegSrc s, uint64_t n, uint64_t q, unsigned long long*
   block_count(ctr + kTSkipped, skipped);
 }
 
+// keys null: a store that keeps no keys.  key_hi: the add call's number << 32 (rule 16's row key)
 __global__ void k_ts_emit(SegSrc s, uint64_t n, uint64_t q, const unsigned long long* ofs, TileStoreRow* rows, uint64_t at0,
-                          uint64_t cap, uint64_t arrival0) {
+                          uint64_t cap, uint64_t arrival0, unsigned long long* keys, unsigned long long key_hi) {
   const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j >= n) return;
   const uint64_t o = ofs[j], c = ofs[j + 1] - o;
@@ -110,12 +129,52 @@ __global__ void k_ts_emit(SegSrc s, uint64_t n, uint64_t q, const unsigned long 
   t.tile = (uint32_t)(g.id & 0x1FFFFFFull);                       // Segment.java:34-36
   t.arrival = arrival0 + j;
   const uint64_t b0 = (uint64_t)g.mn / q;
+  unsigned long long key = key_hi | (j & 0xffffffffull);
+  if (keys && s.win) {
+    const uint32_t w = *(const uint32_t*)(s.base + j * (uint64_t)s.stride + kRepWindow);
+    key = key_hi | (w < s.n_win ? s.win[w].arrival : 0xffffffffu);
+  }
   for (uint64_t i = 0; i < c; ++i) {
     const uint64_t at = at0 + o + i;
     if (at >= cap) return;
     t.bucket = b0 + i;
     rows[at] = t;
+    if (keys) keys[at] = key;
   }
+}
+
+// rows [b, e) of a store that kept no keys so far, all of add call `key_hi >> 32` whose first
+// segment had the running number arrival0: the key the call would have written (host segments: the
+// index in the array; a session that was never sharded: the report's index, which orders one
+// rank's rows as well as its arrival does)
+__global__ void k_ts_backfill(uint64_t b, uint64_t e, const TileStoreRow* rows, uint64_t arrival0, unsigned long long key_hi,
+                              unsigned long long* keys) {
+  const uint64_t k = b + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < e) keys[k] = key_hi | ((rows[k].arrival - arrival0) & 0xffffffffull);
+}
+
+// the exchange (rule 16): the gathered rows whose file this rank writes (padding rows carry kTsPadKey)
+__global__ void k_ts_own(uint64_t n, const TileStoreRow* rows, const unsigned long long* keys, int rank, int nranks,
+                         unsigned long long* flag) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) flag[k] = (keys[k] != kTsPadKey && tile_file_owner(rows[k].bucket, rows[k].tile, nranks) == rank) ? 1ull : 0ull;
+  else if (k == n) flag[n] = 0ull;   // the scan's last entry is the total
+}
+// ... their keys and gathered indices packed in gathered order (ranks in rank order, store order inside)
+__global__ void k_ts_own_pack(uint64_t n, const unsigned long long* keys, const unsigned long long* flag,
+                              const unsigned long long* ofs, unsigned long long* okey, uint32_t* oidx) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n || !flag[k]) return;
+  okey[ofs[k]] = keys[k];
+  oidx[ofs[k]] = (uint32_t)k;
+}
+// ... and, sorted stably by key, into the store
+__global__ void k_ts_take(uint64_t n, const uint32_t* idx, const unsigned long long* skey, const TileStoreRow* src,
+                          TileStoreRow* rows, unsigned long long* keys, uint64_t cap) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n || k >= cap) return;
+  rows[k] = src[idx[k]];
+  keys[k] = skey[k];
 }
 
 // sort key of a pass: 0 next_id, 1 id (Segment.compareTo, least significant first), 2 tile, 3 bucket
@@ -214,6 +273,19 @@ struct TileStore::Impl {
   // the store
   DevBuf<TileStoreRow> rows;
   uint64_t n_rows = 0, cap = 0, arrivals = 0;
+  // rule 16: the rows' keys beside them (cap of them once `keyed`, none before), the add calls
+  // numbered from 0, and the calls whose rows are held without keys: {first row, first segment's
+  // running number, call}
+  DevBuf<unsigned long long> keys;
+  bool keyed = false;
+  uint64_t calls = 0;
+  struct CallRec { uint64_t row0, arrival0, call; };
+  std::vector<CallRec> unkeyed;
+  uint64_t restored = 0;   // rows a snapshot put here: their calls are not known, so they cannot be keyed
+  // the exchange: every rank's rows and keys as gathered, and its three parts' times
+  DevBuf<TileStoreRow> grows; DevBuf<unsigned long long> gkeys; uint64_t g_cap = 0;
+  PartTimer xtimer;
+  double xms[3] = {0, 0, 0};
   // counters
   DevBuf<unsigned long long> ctr;
   PinBuf<unsigned long long> hctr;   // pinned mirror
@@ -248,8 +320,79 @@ struct TileStore::Impl {
     if (need <= cap) return;
     uint64_t c = std::max<uint64_t>(cap, 1);
     while (c < need) c *= 2;
+    if (keyed) keys.reserve(c, kFull, n_rows, st);   // (first: a full HBM here leaves rows and cap as they were)
     rows.reserve(c, kFull, n_rows, st);
     cap = c;
+  }
+  // From here on the store keeps a key per row; the rows it holds get theirs call by call.
+  void make_keyed() {
+    if (keyed) return;
+    if (restored) throw std::runtime_error("tile store holds rows restored from a snapshot: they cannot take part in an exchange");
+    keys.reserve(cap, kFull);
+    keyed = true;
+    for (size_t i = 0; i < unkeyed.size(); ++i) {
+      const uint64_t b = unkeyed[i].row0, e = i + 1 < unkeyed.size() ? unkeyed[i + 1].row0 : n_rows;
+      if (e > b)
+        hipLaunchKernelGGL(k_ts_backfill, dim3(grid(e - b)), dim3(256), 0, st, b, e, (const TileStoreRow*)rows,
+                           unkeyed[i].arrival0, (unsigned long long)(unkeyed[i].call << 32), keys);
+    }
+    RM_HIP(hipGetLastError());
+    unkeyed.clear();
+  }
+  void ensure_gather(uint64_t n) {
+    if (n <= g_cap) return;
+    g_cap = 0;
+    const uint64_t c = std::max<uint64_t>(n + n / 2, 4096);
+    grows.reserve(c, kFull); gkeys.reserve(c, kFull);
+    g_cap = c;
+  }
+  void begin_exchange() {
+    xtimer.harvest(nullptr);
+    for (double& x : xms) x = 0.0;
+  }
+  // The device half of the exchange behind its transport: of the n gathered rows (grows, gkeys;
+  // this rank's own are [own_b, own_e)) those whose file this rank writes replace the store's
+  // contents, merged by one stable sort on the key.  out[1..3]: sent away, received, held
+  void merge_owned(uint64_t n, uint64_t own_b, uint64_t own_e, int nranks, int rank, uint64_t out[4]) {
+    n_rows = 0;
+    restored = 0;
+    unkeyed.clear();
+    uint64_t K = 0, own_kept = 0;
+    if (n) {
+      ensure_counts(n);
+      ensure_flush(n);
+      RM_HIP(hipMemsetAsync(ctr, 0, kTNumCtr * sizeof(unsigned long long), st));
+      xtimer.tic(0, st);
+      hipLaunchKernelGGL(k_ts_own, dim3(grid(n + 1)), dim3(256), 0, st, n, (const TileStoreRow*)grows,
+                         (const unsigned long long*)gkeys, rank, nranks, cnt);
+      scr.scan<unsigned long long>(cnt, ofs, n + 1, st);
+      RM_HIP(hipMemcpyAsync(ctr + kTOwnLo, ofs + own_b, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+      RM_HIP(hipMemcpyAsync(ctr + kTOwnHi, ofs + own_e, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+      RM_HIP(hipMemcpyAsync(ctr + kTOwned, ofs + n, sizeof(unsigned long long), hipMemcpyDeviceToDevice, st));
+      xtimer.toc(st);
+      RM_HIP(hipGetLastError());
+      read_ctr();
+      K = hctr[kTOwned];
+      own_kept = hctr[kTOwnHi] - hctr[kTOwnLo];
+      if (K > n || hctr[kTOwnHi] > K || hctr[kTOwnLo] > hctr[kTOwnHi]) throw std::runtime_error("tile store owned-row count out of range");
+      ensure_rows(K);
+      if (K) {
+        xtimer.tic(0, st);
+        hipLaunchKernelGGL(k_ts_own_pack, dim3(grid(n)), dim3(256), 0, st, n, (const unsigned long long*)gkeys,
+                           (const unsigned long long*)cnt, (const unsigned long long*)ofs, k0, p0);
+        xtimer.toc(st);
+        xtimer.tic(2, st);
+        scr.sort_pairs(k0.get(), k1.get(), p0, p1, K, 64, st);
+        hipLaunchKernelGGL(k_ts_take, dim3(grid(K)), dim3(256), 0, st, K, (const uint32_t*)p1, (const unsigned long long*)k1,
+                           (const TileStoreRow*)grows, rows, keys, cap);
+        xtimer.toc(st);
+        RM_HIP(hipGetLastError());
+      }
+    }
+    RM_HIP(hipStreamSynchronize(st));
+    xtimer.harvest(xms);
+    n_rows = K;
+    if (out) { out[1] = (own_e - own_b) - own_kept; out[2] = K - own_kept; out[3] = K; }
   }
   void ensure_counts(uint64_t n) {
     if (n + 1 <= cnt_cap) return;
@@ -278,6 +421,7 @@ struct TileStore::Impl {
   // count, scan, one read, growth or failure, emit: the n segments at `src` join the store
   void add_device(SegSrc src, uint64_t n, uint64_t out[4]) {
     if (n >= kTsMaxRows) throw BatchTooLarge("tile store call too large (segments >= 2^31 - 1)");
+    if (calls >= 0xfffffffeull) throw std::runtime_error("tile store has numbered 2^32 - 2 add calls");
     ensure_counts(n);
     timer.tic(1, st);
     hipLaunchKernelGGL(k_ts_count, dim3(grid(n + 1)), dim3(256), 0, st, src, n, (uint64_t)tp.quantisation, cnt, ctr);
@@ -296,14 +440,17 @@ struct TileStore::Impl {
     if (total) {
       timer.tic(1, st);
       hipLaunchKernelGGL(k_ts_emit, dim3(grid(n)), dim3(256), 0, st, src, n, (uint64_t)tp.quantisation,
-                         (const unsigned long long*)ofs, rows, n_rows, cap, arrivals);
+                         (const unsigned long long*)ofs, rows, n_rows, cap, arrivals, keyed ? keys.get() : nullptr,
+                         (unsigned long long)(calls << 32));
       timer.toc(st);
       RM_HIP(hipGetLastError());
       RM_HIP(hipStreamSynchronize(st));
       timer.harvest(ms);
     }
+    if (!keyed && total) unkeyed.push_back(CallRec{n_rows, arrivals, calls});
     n_rows += total;
     arrivals += n;
+    calls += 1;
     if (out) { out[0] = hctr[kTKept]; out[1] = hctr[kTSkipped]; out[2] = total; out[3] = n_rows; }
   }
 };
@@ -354,6 +501,7 @@ void* TileStore::snapshot_room(uint64_t n_rows) {
   Impl& s = *p_;
   RM_HIP(hipSetDevice(s.device));
   if (s.n_rows) throw std::runtime_error("snapshot: the tile store is not empty");
+  if (s.keyed) throw std::runtime_error("snapshot: a tile store that keeps row keys (a sharded stream's) cannot be restored into");
   if (n_rows >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
   s.ensure_rows(n_rows);
   return s.rows;
@@ -361,6 +509,8 @@ void* TileStore::snapshot_room(uint64_t n_rows) {
 void TileStore::snapshot_loaded(uint64_t n_rows, uint64_t arrivals) {
   p_->n_rows = n_rows;
   p_->arrivals = arrivals;
+  p_->restored = n_rows;
+  p_->unkeyed.clear();
 }
 
 void TileStore::add(const TileSegment* segs, uint64_t n, uint64_t out[4]) {
@@ -376,7 +526,7 @@ void TileStore::add(const TileSegment* segs, uint64_t n, uint64_t out[4]) {
     RM_HIP(hipMemcpyAsync(s.dstage, s.hstage, n * sizeof(TileSegment), hipMemcpyHostToDevice, s.st));
     s.timer.toc(s.st);
   }
-  s.add_device(SegSrc{s.dstage, (uint32_t)sizeof(TileSegment)}, n, out);
+  s.add_device(SegSrc{s.dstage, (uint32_t)sizeof(TileSegment), nullptr, 0u}, n, out);
 }
 
 void TileStore::add_session(Session& sess, uint64_t out[4]) {
@@ -385,7 +535,107 @@ void TileStore::add_session(Session& sess, uint64_t out[4]) {
   RM_HIP(hipSetDevice(s.device));
   s.begin_call();
   // the session's calls return with their stream synchronised: rep_s is complete
-  s.add_device(SegSrc{(const char*)sess.reports_device(), (uint32_t)sizeof(SessionReport)}, sess.n_reports(), out);
+  if (sess.sharded()) s.make_keyed();   // a sharded stream's rows carry rule 16's keys
+  s.add_device(SegSrc{(const char*)sess.reports_device(), (uint32_t)sizeof(SessionReport), sess.windows_device(),
+                      (uint32_t)sess.n_windows()}, sess.n_reports(), out);
+}
+
+bool TileStore::keyed() const { return p_->keyed; }
+void TileStore::exchange_times(double ms[3]) const { for (int i = 0; i < 3; ++i) ms[i] = p_->xms[i]; }
+
+// rule 16's two device halves.  The blob: kTsBlobHead bytes {magic, rows, quantisation, 0}, the rows
+// in store order, their keys.
+void TileStore::export_rows(char** blob_out, size_t* len_out) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  s.make_keyed();
+  const uint64_t n = s.n_rows;
+  const size_t len = kTsBlobHead + n * (sizeof(TileStoreRow) + 8);
+  char* host = (char*)std::malloc(len);
+  if (!host) throw std::bad_alloc();
+  const uint64_t head[4] = {kTsBlobMagic, n, s.tp.quantisation, 0};
+  std::memcpy(host, head, sizeof head);
+  hipError_t e = hipSuccess;
+  if (n) {
+    e = hipMemcpyAsync(host + kTsBlobHead, s.rows, n * sizeof(TileStoreRow), hipMemcpyDeviceToHost, s.st);
+    if (e == hipSuccess) e = hipMemcpyAsync(host + kTsBlobHead + n * sizeof(TileStoreRow), s.keys, n * 8, hipMemcpyDeviceToHost, s.st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(s.st);
+  if (e != hipSuccess) {
+    std::free(host);
+    RM_HIP(e);
+  }
+  *blob_out = host;
+  *len_out = len;
+}
+
+void TileStore::import_owned(const char* const* blobs, const size_t* lens, uint32_t n, int nranks, int rank, uint64_t out[4]) {
+  Impl& s = *p_;
+  if (nranks < 1 || rank < 0 || rank >= nranks) throw std::runtime_error("tile store import needs 0 <= rank < nranks");
+  if (n && (!blobs || !lens)) throw std::runtime_error("tile store import: blobs or lens is NULL");
+  RM_HIP(hipSetDevice(s.device));
+  // every blob is checked before the store is touched
+  uint64_t total = 0, own_b = 0, own_e = 0;
+  std::vector<uint64_t> cnt(n);
+  for (uint32_t i = 0; i < n; ++i) {
+    uint64_t head[4];
+    if (!blobs[i] || lens[i] < kTsBlobHead) throw std::runtime_error("tile store import: blob " + std::to_string(i) + " is too short");
+    std::memcpy(head, blobs[i], sizeof head);
+    if (head[0] != kTsBlobMagic) throw std::runtime_error("tile store import: blob " + std::to_string(i) + " is no row export");
+    if (head[1] >= kTsMaxRows || lens[i] != kTsBlobHead + head[1] * (sizeof(TileStoreRow) + 8))
+      throw std::runtime_error("tile store import: blob " + std::to_string(i) + " has another length than its row count gives");
+    if (head[2] != s.tp.quantisation) throw std::runtime_error("tile store import: blob " + std::to_string(i) + " has another quantisation");
+    cnt[i] = head[1];
+    if ((int)i == rank) { own_b = total; own_e = total + cnt[i]; }
+    total += cnt[i];
+    if (total >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
+  }
+  if ((int)n <= rank) own_b = own_e = total;
+  s.make_keyed();
+  s.begin_exchange();
+  const uint64_t before = s.n_rows;
+  s.ensure_gather(total);
+  s.xtimer.tic(1, s.st);
+  uint64_t at = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (!cnt[i]) continue;
+    const char* src = blobs[i] + kTsBlobHead;
+    RM_HIP(hipMemcpyAsync(s.grows + at, src, cnt[i] * sizeof(TileStoreRow), hipMemcpyHostToDevice, s.st));
+    RM_HIP(hipMemcpyAsync(s.gkeys + at, src + cnt[i] * sizeof(TileStoreRow), cnt[i] * 8, hipMemcpyHostToDevice, s.st));
+    at += cnt[i];
+  }
+  s.xtimer.toc(s.st);
+  RM_HIP(hipStreamSynchronize(s.st));   // (the blobs are the caller's pageable memory)
+  if (out) out[0] = before;
+  s.merge_owned(total, own_b, own_e, nranks, rank, out);
+}
+
+// export -> all-gather -> import with the rows staying on the device: padded to the largest rank's
+// count (padding keys kTsPadKey), every rank's rows and keys gathered in rank order
+void TileStore::exchange(TileComm& comm, uint64_t out[4]) {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  s.make_keyed();
+  s.begin_exchange();
+  const uint64_t R = s.n_rows, nr = (uint64_t)comm.nranks;
+  const uint64_t Rm = comm.max_u64(R, s.st);
+  if (Rm < R || Rm * nr >= kTsMaxRows) throw BatchTooLarge("tile store exchange too large (rows of all ranks >= 2^31 - 1)");
+  const uint64_t all = Rm * nr;
+  if (out) out[0] = R;
+  if (all) {
+    s.ensure_rows(Rm);
+    s.ensure_gather(all);
+    s.xtimer.tic(1, s.st);
+    if (Rm > R) {
+      RM_HIP(hipMemsetAsync(s.rows + R, 0, (Rm - R) * sizeof(TileStoreRow), s.st));
+      RM_HIP(hipMemsetAsync(s.keys + R, 0xff, (Rm - R) * 8, s.st));
+    }
+    comm.allgather(s.rows, s.grows, Rm * sizeof(TileStoreRow), s.st);
+    comm.allgather(s.keys, s.gkeys, Rm * 8, s.st);
+    s.xtimer.toc(s.st);
+  }
+  const uint64_t b = (uint64_t)comm.rank * Rm;
+  s.merge_owned(all, b, b + R, comm.nranks, comm.rank, out);
 }
 
 void TileStore::flush(char** blob_out, size_t* len_out, uint64_t out[5]) {
@@ -485,6 +735,8 @@ void TileStore::flush(char** blob_out, size_t* len_out, uint64_t out[5]) {
   }
   host[bytes] = 0;
   s.n_rows = 0;   // the store is empty after a flush (AnonymisingProcessor.java:229, 240)
+  s.unkeyed.clear();
+  s.restored = 0;
   *blob_out = host;
   *len_out = bytes;
   if (out) { out[0] = R; out[1] = K; out[2] = tiles; out[3] = files; out[4] = bytes; }

@@ -290,6 +290,94 @@ class Comm:
                     pass
 
 
+class GlooComm(Comm):
+    """A Comm over torch.distributed's gloo backend as the host transport, so several ranks may
+    share one GPU (RCCL refuses that).  The group meets through a file store: rank 0 names a fresh
+    file beside the rendezvous file and hands the name to the others through rendezvous(), the way
+    the RCCL id travels (no TCP port is picked, so none can be taken in between); a process group
+    the caller has already initialised is used as it is."""
+
+    def __init__(self, rank, world_size, device, rdzv_dir=None, token=None, timeout_s=300.0):
+        import torch
+        import torch.distributed as tdist
+        self._own_group = not tdist.is_initialized()
+        if self._own_group:
+            self._gloo_path = rendezvous_path(rdzv_dir, token) + ".gloo"
+
+            def make_id():
+                store = ("%s.%s.store" % (self._gloo_path, os.urandom(8).hex())).encode()
+                if len(store) > 512:
+                    raise ValueError("rendezvous directory path too long")
+                return store.ljust(512, b"\0")
+            self._store = rendezvous(rank, self._gloo_path, make_id, 512, timeout_s).rstrip(b"\0").decode()
+            tdist.init_process_group("gloo", init_method="file://" + self._store, rank=rank, world_size=world_size)
+        self._tdist = tdist
+
+        def allgather(b):
+            t = torch.frombuffer(bytearray(b), dtype=torch.uint8)
+            out = [torch.empty_like(t) for _ in range(world_size)]
+            tdist.all_gather(out, t)
+            return [o.numpy().tobytes() for o in out]
+        Comm.__init__(self, rank, world_size, device, allgather=allgather)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            Comm.close(self)
+            if self._own_group:
+                self._tdist.destroy_process_group()
+                if self.rank == 0:
+                    for path in (self._gloo_path, self._store):
+                        try:
+                            os.remove(path)
+                        except OSError:
+                            pass
+
+
+def stream_comm(rank, world_size, device, transport="rccl"):
+    """The communicator of `python -m reporter_amd.stream --ranks N`: RCCL, or gloo as the host transport."""
+    if transport == "host":
+        return GlooComm(rank, world_size, device)
+    if transport != "rccl":
+        raise ValueError("transport must be rccl or host")
+    return Comm(rank, world_size, device)
+
+
+def self_launch(module, argv, n, timeout_s=None):
+    """Start n fresh child processes of `python -m module argv`, one per rank (RANK, LOCAL_RANK,
+    WORLD_SIZE and a random nonce of this launch, which also names its rendezvous file, in their
+    environment), wait for all and return the first non-zero exit status; when a rank fails, or
+    timeout_s seconds have passed (status 124), the others are ended.  The caller has not opened
+    the GPU: each rank opens it in a process of its own."""
+    import subprocess
+    import sys
+    nonce = os.urandom(12).hex()
+    procs = []
+    for r in range(n):
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), RM_RDZV_TOKEN=nonce, RM_RDZV_NONCE=nonce)
+        procs.append(subprocess.Popen([sys.executable, "-m", module] + list(argv), env=env))
+    rc = 0
+    left = list(procs)
+    t0 = time.time()
+    while left:
+        if timeout_s is not None and time.time() - t0 > timeout_s:
+            for q in left:
+                q.kill()
+            for q in left:
+                q.wait()
+            return rc or 124
+        for p in list(left):
+            try:
+                code = p.wait(timeout=0.2)
+            except subprocess.TimeoutExpired:
+                continue
+            left.remove(p)
+            if code and not rc:
+                rc = code
+                for q in left:
+                    q.terminate()
+    return rc
+
+
 class DeviceBuffer:
     """Plain device allocation (no framework)."""
 

@@ -800,16 +800,29 @@ class VehicleSessions:
         _lib.check(_lib.lib().rm_session_push(self._h, C.byref(d), out))
         return dict(zip(SESSION_COUNTS, (int(x) for x in out)))
 
-    def push_messages(self, chunks, fmt, directory, stamp_ms=None, strict=False):
+    def push_messages(self, chunks, fmt, directory, stamp_ms=None, strict=False, shard=None):
         """Raw messages (one per line, in `chunks`) read, keyed through `directory` and pushed, all
         on the GPU (DESIGN.md §3 rule 14).  stamp_ms: the stream time of the whole call, or None
         for each message's own time.  Returns (push counts, line counts): SESSION_COUNTS and
-        MESSAGES_INFO.  A tolerant call drops malformed messages (dropped_messages() lists them)."""
+        MESSAGES_INFO.  A tolerant call drops malformed messages (dropped_messages() lists them).
+        shard=(rank, nranks): the masked push of a stream on several ranks (rule 16) -- everything is
+        read and keyed, only the points of the vehicles `rank` owns are appended and matched; the
+        line counts then carry "own" and "foreign", the points of either kind."""
         d, keep = _messages_desc(chunks, fmt, strict, stamp_ms)
         out = (C.c_uint64 * 8)()
         info = (C.c_uint64 * 8)()
-        _lib.check(_lib.lib().rm_session_push_messages(self._h, getattr(directory, "_h", None), C.byref(d), out, info))
-        return dict(zip(SESSION_COUNTS, (int(x) for x in out))), dict(zip(MESSAGES_INFO, (int(x) for x in info)))
+        h = getattr(directory, "_h", None)
+        if shard is None:
+            _lib.check(_lib.lib().rm_session_push_messages(self._h, h, C.byref(d), out, info))
+            own = None
+        else:
+            rank, nranks = (int(x) for x in shard)
+            own = (C.c_uint64 * 2)()
+            _lib.check(_lib.lib().rm_session_push_messages_sharded(self._h, h, C.byref(d), nranks, rank, out, info, own))
+        info = dict(zip(MESSAGES_INFO, (int(x) for x in info)))
+        if own is not None:
+            info["own"], info["foreign"] = int(own[0]), int(own[1])
+        return dict(zip(SESSION_COUNTS, (int(x) for x in out))), info
 
     def dropped_messages(self):
         """The first (at most 64) messages the last push_messages dropped: (chunk, line, reason)."""
@@ -886,6 +899,17 @@ TILE_SEGMENT_DTYPE = np.dtype([
 assert TILE_SEGMENT_DTYPE.itemsize == 40
 TILE_ADD_COUNTS = ("kept", "skipped", "rows", "held")
 TILE_FLUSH_COUNTS = ("rows_in", "rows_kept", "tiles", "files", "bytes")
+TILE_EXCHANGE_COUNTS = ("before", "sent", "received", "held")
+
+
+def vehicle_owner(index, nranks):
+    """The rank that holds directory index `index`'s session in a stream of nranks ranks (rule 16)."""
+    return int(_lib.lib().rm_vehicle_owner(int(index), int(nranks)))
+
+
+def tile_file_owner(bucket, tile, nranks):
+    """The rank that culls and writes the file of time bucket `bucket` and tile id `tile`."""
+    return int(_lib.lib().rm_tile_file_owner(int(bucket), int(tile), int(nranks)))
 
 
 class TileStore:
@@ -942,6 +966,41 @@ class TileStore:
         parts = raw.split(b"\0")
         files = {parts[i].decode(): parts[i + 1] for i in range(0, len(parts) - 1, 2)}
         return files, dict(zip(TILE_FLUSH_COUNTS, (int(x) for x in out)))
+
+    def export_rows(self):
+        """The rows held and their keys as bytes (rm_tilestore_export_rows, rule 16); the store keeps them."""
+        blob = C.c_void_p()
+        n = C.c_size_t()
+        _lib.check(_lib.lib().rm_tilestore_export_rows(self._h, C.byref(blob), C.byref(n)))
+        try:
+            return C.string_at(blob.value, n.value)
+        finally:
+            _lib.lib().rm_free(blob)
+
+    def import_owned(self, blobs, rank, nranks):
+        """Replace the store's contents by the rows of `blobs` (every rank's export_rows, in rank
+        order) whose file `rank` owns, merged into the one-rank store's order; returns TILE_EXCHANGE_COUNTS."""
+        blobs = [bytes(b) for b in blobs]
+        n = len(blobs)
+        ptrs = (C.c_char_p * max(n, 1))(*blobs)
+        lens = (C.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rm_tilestore_import_owned(self._h, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
+                                                        int(nranks), int(rank), out))
+        return dict(zip(TILE_EXCHANGE_COUNTS, (int(x) for x in out)))
+
+    def exchange(self, comm):
+        """export -> all-gather -> import on the device through a dist.Comm (rule 16): every rank
+        calls it just before flush(); returns TILE_EXCHANGE_COUNTS."""
+        out = (C.c_uint64 * 4)()
+        _lib.check(_lib.lib().rm_tilestore_exchange(self._h, getattr(comm, "_h", None), out))
+        return dict(zip(TILE_EXCHANGE_COUNTS, (int(x) for x in out)))
+
+    def exchange_ms(self):
+        """Device ms of the last import_owned / exchange: partition, transport, merge."""
+        t = (C.c_double * 3)()
+        _lib.check(_lib.lib().rm_tilestore_exchange_time(self._h, t))
+        return dict(zip(("partition", "transport", "merge"), (float(x) for x in t)))
 
     def ms(self):
         """Device ms of the last call: upload, expand, sort, cull, text, download."""

@@ -16,12 +16,23 @@ its position in the input are written to FILE after every tile flush and at a st
 --stop-after-polls N stops after N polls without the final punctuate and flush (the file-fed
 counterpart of Reporter.java --duration), and --resume continues from FILE, writing what the
 stream that never stopped would have written.
+
+With --ranks N the stream runs on N GPUs (DESIGN.md §3 rule 16) and writes, file for file and byte
+for byte, what one rank writes: N fresh child processes are started, one per rank (or the ranks come
+from torch.distributed.run through RANK / WORLD_SIZE / LOCAL_RANK); every rank reads and keys all
+the text, holds the sessions of the vehicles it owns, and before each flush the tile rows go to the
+rank that owns their file, which alone writes it.  --transport host carries the exchange over gloo,
+so several ranks can share one GPU (rank r takes GPU LOCAL_RANK modulo the device count).  Rank 0
+prints the summed statistics.  --ranks cannot be combined with --checkpoint.
 """
 import argparse
 import json
 import logging
 import os
 import sys
+
+
+MAX_RANKS = 16
 
 
 def polls_from(paths, poll_bytes, first=0, offset=0):
@@ -67,7 +78,10 @@ def write_flush(files, dest, k):
 
 def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transition_levels=(0, 1), privacy=2,
         quantisation=3600, flush_interval=300, source="smpl_rprt", max_vehicles=1 << 16, poll_bytes=1 << 20, device=0,
-        report_dist_m=None, report_count=None, report_time_s=None, checkpoint=None, stop_after_polls=None, resume=False):
+        report_dist_m=None, report_count=None, report_time_s=None, checkpoint=None, stop_after_polls=None, resume=False,
+        comm=None):
+    """comm: a dist.Comm of the stream's ranks (None: one rank).  Every rank calls run() with the
+    same arguments; the statistics returned are summed over the ranks."""
     from . import engine
     from .batch import options_from_config
     opts, graph = options_from_config(conf, mode)
@@ -83,6 +97,10 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
     vdir = engine.VehicleDirectory(max_vehicles, device)
     store = engine.TileStore(device, quantisation, privacy, source, mode)
     stats = dict(polls=0, messages=0, dropped=0, forwarded=0, flushes=0, files=0)
+    rank, nranks = (comm.rank, comm.world_size) if comm is not None else (0, 1)
+    shard = (rank, nranks) if comm is not None else None
+    if comm is not None and (checkpoint or resume):
+        raise ValueError("a stream of several ranks keeps no checkpoint")
     last_flush = now = None
     inputs = [[os.path.abspath(p), os.path.getsize(p)] for p in paths]
     pos = [0, 0]   # file index and byte offset of the next poll
@@ -103,19 +121,21 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
             write_checkpoint(checkpoint, engine.save_stream(sess, vdir, store, json.dumps(user).encode()))
 
         def flush():
+            if comm is not None:
+                store.exchange(comm)   # every tile row to the rank that writes its file
             files, _ = store.flush()
             stats["files"] += write_flush(files, dest, stats["flushes"])
             stats["flushes"] += 1
 
         polled = 0
         for text, pos[0], pos[1] in polls_from(paths, poll_bytes, pos[0], pos[1]):
-            out, info = sess.push_messages([text], fmt, vdir)
+            out, info = sess.push_messages([text], fmt, vdir, shard=shard)
             store.add_session(sess)
             stats["polls"] += 1
             stats["messages"] += info["points"]
             stats["dropped"] += info["dropped"]
             stats["forwarded"] += out["forwarded"]
-            for c, ln, why in sess.dropped_messages():
+            for c, ln, why in sess.dropped_messages() if rank == 0 else ():
                 logging.warning("poll %d line %d dropped: %s", stats["polls"], ln, why)
             span = sess.messages_span()
             if span is not None:
@@ -141,6 +161,9 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
             stats["forwarded"] += out["forwarded"]
         flush()
         stats["vehicles"] = vdir.size
+        if comm is not None:   # what the ranks did apart: summed (counts below 2^53 are exact in a double)
+            for k in ("forwarded", "files"):
+                stats[k] = int(comm.allreduce_host(stats[k]))
         if checkpoint:
             save(done=True)
         return stats
@@ -175,9 +198,25 @@ def main(argv=None):
     ap.add_argument("--stop-after-polls", type=int, help="stop after this many polls, without the final punctuate and "
                     "flush, leaving the checkpoint to --resume from")
     ap.add_argument("--resume", action="store_true", help="continue from --checkpoint")
+    ap.add_argument("--ranks", type=int, default=1, help="run the stream on this many GPUs (at most %d), one process each" % MAX_RANKS)
+    ap.add_argument("--transport", choices=("rccl", "host"), default="rccl", help="the ranks' exchange: RCCL, or gloo over "
+                    "the host, with which several ranks can share one GPU")
     a = ap.parse_args(argv)
     if (a.resume or a.stop_after_polls is not None) and not a.checkpoint:
         ap.error("--resume and --stop-after-polls need --checkpoint")
+    if not 1 <= a.ranks <= MAX_RANKS:
+        ap.error("--ranks must be 1 .. %d" % MAX_RANKS)
+    world = int(os.environ.get("WORLD_SIZE", "1")) if "RANK" in os.environ else 0
+    if world and a.ranks > 1 and a.ranks != world:
+        ap.error("--ranks %d under a launcher that started %d ranks (WORLD_SIZE)" % (a.ranks, world))
+    if (a.ranks > 1 or world > 1) and a.checkpoint:
+        ap.error("--ranks cannot be combined with --checkpoint (a sharded stream's state is not saved)")
+    if world > MAX_RANKS:
+        ap.error("at most %d ranks" % MAX_RANKS)
+    if a.ranks > 1 and not world:
+        # this process has not opened the GPU and never does: each rank is a fresh child
+        from .dist import self_launch
+        return self_launch("reporter_amd.stream", sys.argv[1:] if argv is None else argv, a.ranks)
     paths = []
     for p in a.inputs:
         if os.path.isdir(p):
@@ -186,11 +225,25 @@ def main(argv=None):
         else:
             paths.append(p)
     levels = lambda s: tuple(int(x) for x in s.split(",") if x != "")
+    device = int(os.environ.get("LOCAL_RANK", "0"))
+    comm = None
+    if world > 1:
+        import ctypes
+        from . import _lib, dist
+        cnt = ctypes.c_int(0)
+        _lib.check(_lib.lib().rm_device_count(ctypes.byref(cnt)))
+        if a.transport == "rccl" and world > cnt.value:
+            ap.error("--transport rccl needs a GPU per rank (%d ranks, %d devices): use --transport host" % (world, cnt.value))
+        device %= max(cnt.value, 1)
+        comm = dist.stream_comm(int(os.environ["RANK"]), world, device, a.transport)
     stats = run(paths, a.match_config, a.output_location, a.formatter, a.mode, levels(a.reports), levels(a.transitions),
                 a.privacy, a.quantisation, a.flush_interval, a.source, a.max_vehicles, a.poll_bytes,
-                int(os.environ.get("LOCAL_RANK", "0")), a.report_dist, a.report_count, a.report_time, a.checkpoint,
-                a.stop_after_polls, a.resume)
-    print(json.dumps(stats))
+                device, a.report_dist, a.report_count, a.report_time, a.checkpoint,
+                a.stop_after_polls, a.resume, comm)
+    if comm is not None:
+        comm.close()   # (a rank that failed above leaves without the closing barrier: the launcher ends the others)
+    if comm is None or comm.rank == 0:
+        print(json.dumps(stats))
     return 0
 
 

@@ -30,7 +30,8 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 
 from reporter_amd import engine, world   # noqa: E402
 
@@ -175,6 +176,37 @@ def snapshot_probe(bm, texts, fmt, n_vehicles, at):
                             note="VehicleSessions.store() + VehicleDirectory.names(): read-outs only, no tile rows, nothing loads them"))
 
 
+def sharded_probe(bm, texts, fmt, n_vehicles, comm, flush_every):
+    """The stream of rule 16 on this rank: masked pushes, the tile store fed device to device, and every
+    `flush_every` pushes (and at the end) the exchange and a flush.  Per flush the exchange's three stage
+    times (HIP events) and its row counts; per push the route's parts as route_a gives them."""
+    sess = engine.VehicleSessions(bm, n_vehicles)
+    vdir = engine.VehicleDirectory(n_vehicles)
+    store = engine.TileStore(comm.device)
+    shard = (comm.rank, comm.world_size)
+    pushes, flushes, own = [], [], 0
+    for k, text in enumerate(texts):
+        t0 = time.perf_counter()
+        out, info = sess.push_messages([text], fmt, vdir, shard=shard)
+        wall = (time.perf_counter() - t0) * 1e3
+        ms = sess.messages_ms()
+        store.add_session(sess)
+        pushes.append([round(wall, 3)] + [round(ms[p], 3) for p in PARTS])
+        own += info["own"]
+        if (k + 1) % flush_every == 0 or k + 1 == len(texts):
+            t0 = time.perf_counter()
+            moved = store.exchange(comm)
+            wall = (time.perf_counter() - t0) * 1e3
+            files, counts = store.flush()
+            flushes.append(dict(moved, wall_ms=round(wall, 3), files=counts["files"],
+                                **{k2: round(v, 4) for k2, v in store.exchange_ms().items()}))
+    for x in (store, vdir, sess):
+        x.close()
+    p = np.array(pushes)
+    return dict(rank=comm.rank, ranks=comm.world_size, own_points=own, sum_ms=dict(zip(("wall",) + PARTS, p.sum(axis=0).round(2).tolist())),
+                push_columns=["wall_ms"] + list(PARTS), pushes=pushes, flushes=flushes)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--vehicles", type=int, default=10000)
@@ -183,7 +215,17 @@ def main():
     ap.add_argument("--runs", type=int, default=4)
     ap.add_argument("--snapshot-at", type=int, help="measure the stream snapshot: save after this push, load, finish")
     ap.add_argument("--out")
+    ap.add_argument("--ranks", type=int, default=1, help="the stream of DESIGN.md §3 rule 16 on this many ranks (one fresh "
+                    "process each): per flush the exchange's stage times and rows moved, one JSON file per rank")
+    ap.add_argument("--transport", choices=("rccl", "host"), default="rccl", help="host: gloo, so the ranks can share one GPU")
+    ap.add_argument("--flush-every", type=int, default=2, help="with --ranks: pushes between two flushes")
     a = ap.parse_args()
+    ranked = "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1
+    if a.ranks > 1 and not ranked:
+        from reporter_amd import dist
+        env_path = os.pathsep.join([os.path.join(ROOT, "scripts"), ROOT, os.environ.get("PYTHONPATH", "")])
+        os.environ["PYTHONPATH"] = env_path
+        sys.exit(dist.self_launch("stream_probe", sys.argv[1:], a.ranks))
     a.out = a.out or (os.path.join("profiles", "snapshot", "snapshot_probe.json") if a.snapshot_at is not None
                       else os.path.join("profiles", "stream", "stream_probe.json"))
     cfg = world.CONFIGS["C2"]
@@ -201,8 +243,38 @@ def main():
     cuts = [(s, min(s + per, T * n)) for s in range(0, T * n, per)]
     texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in ((0,) if a.snapshot_at is not None else (0, 1))}
     fmt = {0: engine.MessageFormat(0), 1: engine.MessageFormat(1)}
-    eng = engine.Engine(graph, 0)
+    device = 0
+    if ranked:   # each rank its own GPU, as python -m reporter_amd.stream takes them; only the host transport may share one
+        import ctypes
+        from reporter_amd import _lib
+        cnt = ctypes.c_int(0)
+        _lib.check(_lib.lib().rm_device_count(ctypes.byref(cnt)))
+        if a.transport == "rccl" and int(os.environ["WORLD_SIZE"]) > max(cnt.value, 1):
+            sys.exit("--transport rccl needs a GPU per rank (%d ranks, %d devices): use --transport host" %
+                     (int(os.environ["WORLD_SIZE"]), cnt.value))
+        device = int(os.environ.get("LOCAL_RANK", "0")) % max(cnt.value, 1)
+    eng = engine.Engine(graph, device)
     bm = engine.BatchMatcher(eng)
+    if ranked:
+        from reporter_amd import dist
+        rank, world_size = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+        comm = dist.stream_comm(rank, world_size, device, a.transport)
+        route_a(bm, texts[0][:2], fmt[0], T)   # warm the route
+        out = dict(args=dict(vehicles=a.vehicles, points=a.points, per_push=a.per_push, ranks=world_size, transport=a.transport,
+                             flush_every=a.flush_every), messages_per_push=per,
+                   note="ranks sharing one GPU show the exchange's cost, not scaling",
+                   **sharded_probe(bm, texts[0], fmt[0], T, comm, a.flush_every))
+        comm.close()
+        path = (a.out if a.out.endswith(".json") and "stream_probe.json" not in a.out else
+                os.path.join("profiles", "stream_shard", "stream_probe.json"))[:-5] + ".rank%d.json" % rank
+        os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+        with open(path, "w") as f:
+            f.write(json.dumps(out) + "\n")
+        if rank == 0:
+            print(json.dumps(dict(out, pushes=None)))
+        bm.close()
+        eng.close()
+        return
     if a.snapshot_at is not None:
         print("text written", file=sys.stderr, flush=True)
         route_a(bm, texts[0][:2], fmt[0], T)   # warm the route

@@ -707,9 +707,10 @@ int rm_tile_file_owner(uint64_t bucket, uint32_t tile, int nranks);
  *                              the host transport; every rank calls it, padded to the largest count)
  *   out: [0] rows before [1] rows sent away [2] rows received [3] rows held
  *   rm_tilestore_exchange_time ms (HIP events) of the last import / exchange: partition, transport, merge
- * Not supported: rm_snapshot_save of a store that keeps keys, and rm_snapshot_load into one, fail
- * with a message (rows restored from a snapshot cannot be exported either); and ranks reading
- * disjoint parts of the input, which would need order keys taken from the messages themselves. */
+ * Not supported: ranks reading disjoint parts of the input, which would need order keys taken from
+ * the messages themselves.  A sharded stream is saved and restored by the calls of rule 17 below:
+ * rm_snapshot_save of a store that keeps keys, and rm_snapshot_load into one, still fail with a
+ * message (rows restored by rm_snapshot_load cannot be exported either). */
 int rm_vehicle_owner(uint32_t index, int nranks);
 int rm_session_push_messages_sharded(rm_session* s, rm_directory* dir, const rm_messages_desc* d, int nranks, int rank,
                                      uint64_t out[8], uint64_t info[8], uint64_t shard[2]);
@@ -718,6 +719,37 @@ int rm_tilestore_import_owned(rm_tilestore* t, const char* const* blobs, const s
                               uint64_t out[4]);
 int rm_tilestore_exchange(rm_tilestore* t, rm_comm* comm, uint64_t out[4]);
 int rm_tilestore_exchange_time(rm_tilestore* t, double ms[3]);
+
+/* ---------------- checkpoints of the stream on several GPUs (DESIGN.md §3 rule 17) ----------------
+ * A stream of M ranks stopped behind any poll, saved rank by rank, torn down, rebuilt on N ranks from
+ * the M blobs and continued writes, file for file and byte for byte, what the one-rank stream that
+ * never stopped writes; M and N are each 1 .. 16 and need not be equal (the reference's changelog
+ * restore and rebalance).  A blob of this kind is a snapshot blob (version 1) with two more sections:
+ * kind 11, the u64 key of every tile row, and kind 12, one record {u32 rank, nranks, calls, 0}.
+ *
+ * rm_snapshot_save_shard   rank's blob: its sessions, the directory (replicated), its rows, their keys
+ *                          and the record; the store is needed and keeps keys from here on.  out and
+ *                          ms as for rm_snapshot_save.
+ * rm_snapshot_load_shards  into empty objects, from the n_blobs blobs of one save in any order: the
+ *                          sessions of the vehicles rm_vehicle_owner gives to `rank` of `nranks`, the
+ *                          directory, and the rows of the files rm_tile_file_owner gives it, in the
+ *                          one-rank order.  The blobs must be all M of one save (their nranks is
+ *                          n_blobs, every rank once, equal calls, equal directories) and of the
+ *                          store's quantisation.  One blob without kinds 11 and 12 (rm_snapshot_save's)
+ *                          counts as rank 0 of 1: its rows are keyed by position under call 0.  The
+ *                          session counts as pushed sharded afterwards and the store keeps keys.  A
+ *                          load that fails leaves its targets empty and usable.
+ *   out: [0] bytes of all blobs [1] names [2] vehicles held [3] points held [4] rows held
+ *        [5] user bytes of the first blob [6] calls [7] saved ranks
+ *   ms (HIP events): [0] upload [1] check [2] unpack [3] the rows' partition and merge
+ * rm_snapshot_load refuses a blob with kinds 11 and 12, naming rm_snapshot_load_shards.
+ * rm_snapshot_check_host_shard is rm_snapshot_check_host with three more words:
+ *   info: [9] rank [10] nranks (0: no shard record) [11] calls */
+int rm_snapshot_save_shard(rm_session* s, rm_directory* d, rm_tilestore* t, int rank, int nranks, const char* user,
+                           size_t user_len, char** blob, size_t* len, uint64_t out[6], double ms[6]);
+int rm_snapshot_load_shards(rm_session* s, rm_directory* d, rm_tilestore* t, const char* const* blobs, const size_t* lens,
+                            uint32_t n_blobs, int rank, int nranks, uint64_t out[8], double ms[6]);
+int rm_snapshot_check_host_shard(const char* blob, size_t len, uint64_t info[12], char* err, size_t errlen);
 
 /* ---------------- device memory helpers (histograms without a framework) ---------------- */
 int rm_device_alloc(size_t bytes, void** dev_ptr);

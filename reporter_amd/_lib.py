@@ -243,6 +243,10 @@ PROTOTYPES = [
                                    C.POINTER(C.c_double)]),
     ("rm_snapshot_load", C.c_int, [P, P, P, C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("rm_snapshot_check_host", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
+    ("rm_snapshot_save_shard", C.c_int, [P, P, P, C.c_int, C.c_int, C.c_char_p, C.c_size_t, C.POINTER(P), C.POINTER(C.c_size_t),
+                                         C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rm_snapshot_load_shards", C.c_int, [P, P, P, P, P, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rm_snapshot_check_host_shard", C.c_int, [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]),
     ("rm_comm_unique_id", C.c_int, [P]),
     ("rm_comm_init", P, [C.c_int, C.c_int, P, C.c_int]),
     ("rm_comm_destroy", None, [P]),

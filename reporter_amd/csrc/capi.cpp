@@ -2176,6 +2176,36 @@ int rm_snapshot_check_host(const char* blob, size_t len, uint64_t info[9], char*
   return rc;
 }
 
+// the snapshot of a stream on several ranks (DESIGN.md §3 rule 17)
+int rm_snapshot_save_shard(rm_session* s, rm_directory* d, rm_tilestore* t, int rank, int nranks, const char* user,
+                           size_t user_len, char** blob, size_t* len, uint64_t out[6], double ms[6]) {
+  if (!blob || !len) return fail("blob/len is NULL");
+  *blob = nullptr;
+  *len = 0;
+  return guarded([&] {
+    snapshot_save_shard(s ? s->s.get() : nullptr, d ? d->d.get() : nullptr, t ? t->t.get() : nullptr, rank, nranks, user, user_len,
+                        blob, len, out, ms);
+  });
+}
+int rm_snapshot_load_shards(rm_session* s, rm_directory* d, rm_tilestore* t, const char* const* blobs, const size_t* lens,
+                            uint32_t n_blobs, int rank, int nranks, uint64_t out[8], double ms[6]) {
+  return guarded([&] {
+    snapshot_load_shards(s ? s->s.get() : nullptr, d ? d->d.get() : nullptr, t ? t->t.get() : nullptr, blobs, lens, n_blobs, rank,
+                         nranks, out, ms);
+  });
+}
+int rm_snapshot_check_host_shard(const char* blob, size_t len, uint64_t info[12], char* err, size_t errlen) {
+  const int rc = guarded([&] {
+    const std::string why = snap::check_host(blob, len, info, 0, info ? info + 9 : nullptr);
+    if (!why.empty()) throw std::runtime_error(why);
+  });
+  if (rc && err && errlen) {
+    std::strncpy(err, g_err.c_str(), errlen - 1);
+    err[errlen - 1] = 0;
+  }
+  return rc;
+}
+
 }  // extern "C"
 
 namespace {

@@ -437,6 +437,7 @@ class Session {
   SessionSnap snapshot_room(uint64_t n_points);
   void snapshot_loaded(uint64_t n_points);
   void snapshot_clear();   // every vehicle empty, as created (a load that failed half way)
+  void snapshot_sharded();   // a load of shards (rule 17): the next add_session from here keeps keys
 
  private:
   struct Impl;
@@ -532,6 +533,17 @@ class TileStore {
   hipStream_t stream() const;
   void* snapshot_room(uint64_t n_rows);
   void snapshot_loaded(uint64_t n_rows, uint64_t arrivals);
+  // a sharded stream's snapshot (rule 17).  snapshot_keys: the store keeps keys from here on (the
+  // rows held get theirs) and the keys held, in store order.  calls: the add calls numbered so far.
+  // snapshot_merge, into an empty store: of the n_parts ranges of rows (device memory, in rank order;
+  // keys[i] null: that range's rows are keyed by their position under call 0) those whose file
+  // `rank` owns, through the exchange's own merge; the store is keyed afterwards and carries on at
+  // `calls` and `arrivals`.  A throw leaves the store empty.  snapshot_clear: empty again.
+  const void* snapshot_keys();
+  uint64_t calls() const;
+  void snapshot_merge(const void* const* rows, const void* const* keys, const uint64_t* counts, uint32_t n_parts, int nranks,
+                      int rank, uint64_t calls, uint64_t arrivals);
+  void snapshot_clear();
 
  private:
   struct Impl;
@@ -545,6 +557,16 @@ class TileStore {
 void snapshot_save(Session* s, Directory* d, TileStore* t, const char* user, size_t user_len, char** blob, size_t* len,
                    uint64_t out[6], double ms[6]);
 void snapshot_load(Session* s, Directory* d, TileStore* t, const char* blob, size_t len, uint64_t out[6], double ms[6]);
+// The snapshot of a stream on several ranks (DESIGN.md §3 rule 17).  save_shard: rank's blob of
+// nranks -- its sessions, the directory, its rows, their keys and the shard record (the store is
+// needed); out and ms as for save.  load_shards, into empty objects: of the n blobs of one save
+// (any order; one blob without a shard record counts as rank 0 of 1) what `rank` of `nranks` holds.
+// out: bytes of all blobs, names, vehicles held, points held, rows held, user bytes of the first
+// blob, calls, saved ranks; ms: upload, check, unpack, rows (the store's merge)
+void snapshot_save_shard(Session* s, Directory* d, TileStore* t, int rank, int nranks, const char* user, size_t user_len,
+                         char** blob, size_t* len, uint64_t out[6], double ms[6]);
+void snapshot_load_shards(Session* s, Directory* d, TileStore* t, const char* const* blobs, const size_t* lens, uint32_t n,
+                          int rank, int nranks, uint64_t out[8], double ms[6]);
 unsigned long long lines_hash_mask();   // RM_LINES_HASH_BITS as the line reader reads it (lines.hip)
 
 // report() (reference py/reporter_service.py:79-179) on the device over host-supplied segment

@@ -892,6 +892,8 @@ void Session::snapshot_loaded(uint64_t n_points) {
   s.n_win = s.n_rep = 0;   // the last call's outputs are not part of a snapshot
 }
 
+void Session::snapshot_sharded() { p_->sharded = true; }
+
 void Session::snapshot_clear() {
   Impl& s = *p_;
   RM_HIP(hipSetDevice(s.m->eng_->device()));

@@ -14,6 +14,8 @@
 //                kSessLon, kSessLat, kSessAcc (f32), kSessTime (f64): the kept points in that order
 //     tile rows  kTileRows   TileStoreRow x rows, in store order
 //                kTileMeta   TileMeta: the store's running arrival number and the quantisation
+//     shard      kTileKeys   u64 per row of kTileRows, rule 16's call << 32 | a, in store order
+//     (rule 17)  kShardRec   ShardRec: the saving rank, the rank count, the store's add-call counter
 // Checksum of a byte range: sum over its 8-byte words w_i (the last zero-padded) of
 // (w_i ^ kSeed) * (2 i + 1) mod 2^64.  An odd factor is invertible, so any single flipped bit
 // changes the sum; an integer sum is the same in any order, so blocks may add their parts atomically.
@@ -35,7 +37,7 @@ constexpr uint64_t kSeed = 0x9e3779b97f4a7c15ull;
 constexpr uint32_t kMaxName = 4096;   // sv::kMaxId: the longest id the line reader keeps
 constexpr uint32_t kRowBytes = 64;    // sizeof(TileStoreRow)
 
-enum Kind : uint32_t { kUser = 1, kDirOff, kDirBytes, kSessRec, kSessLon, kSessLat, kSessAcc, kSessTime, kTileRows, kTileMeta, kNumKinds };
+enum Kind : uint32_t { kUser = 1, kDirOff, kDirBytes, kSessRec, kSessLon, kSessLat, kSessAcc, kSessTime, kTileRows, kTileMeta, kTileKeys, kShardRec, kNumKinds };
 
 struct Header {
   uint64_t magic;
@@ -56,16 +58,23 @@ struct TileMeta {
   uint64_t arrivals;
   uint32_t quantisation, pad;
 };
+struct ShardRec {   // (calls < 2^32 - 1: the store numbers no more add calls)
+  uint32_t rank, nranks, calls, pad;
+};
+constexpr uint32_t kMaxRanks = 16;
+constexpr uint64_t kPadKey = ~0ull;   // the exchange's padding key (tilestore.hip kTsPadKey): no row has it
+static_assert(sizeof(ShardRec) == 16, "snapshot layout");
 static_assert(sizeof(Header) == 32 && sizeof(Entry) == 40 && sizeof(SessRec) == 24 && sizeof(TileMeta) == 16, "snapshot layout");
 
 RM_HD uint32_t elem_size(uint32_t kind) {
   switch (kind) {
     case kUser: case kDirBytes: return 1u;
-    case kDirOff: case kSessTime: return 8u;
+    case kDirOff: case kSessTime: case kTileKeys: return 8u;
     case kSessRec: return (uint32_t)sizeof(SessRec);
     case kSessLon: case kSessLat: case kSessAcc: return 4u;
     case kTileRows: return kRowBytes;
     case kTileMeta: return (uint32_t)sizeof(TileMeta);
+    case kShardRec: return (uint32_t)sizeof(ShardRec);
     default: return 0u;
   }
 }
@@ -79,6 +88,7 @@ RM_HD uint64_t sum_word(uint64_t w, uint64_t i) { return (w ^ kSeed) * (2ull * i
 // and the lowest bit set is the one reported, on the host and on the device alike
 enum Err : uint32_t {
   kESum = 0, kECntZero, kEVehOrder, kEMaxSep, kECntSum, kETimeNaN, kEOffMono, kEOffRange, kENameLen, kEDupName, kEVehRange,
+  kEPadKey, kEShardRank, kEShardRanks, kEShardPad, kEVehTwice,
   kENumErr
 };
 inline const char* message(uint32_t bit) {
@@ -93,7 +103,12 @@ inline const char* message(uint32_t bit) {
       "snapshot: name offsets do not stay inside the name bytes",
       "snapshot: a name is empty or longer than 4096 bytes",
       "snapshot: two names are equal",
-      "snapshot: a vehicle index is not below the session's n_vehicles"};
+      "snapshot: a vehicle index is not below the session's n_vehicles",
+      "snapshot: a tile row's key is the padding key",
+      "snapshot: the shard record's rank is not below its nranks",
+      "snapshot: the shard record's nranks is 0 or above 16",
+      "snapshot: the shard record's padding is not zero",
+      "snapshot: a vehicle's session is in two blobs"};
   return bit < kENumErr ? m[bit] : "snapshot: unknown error";
 }
 inline const char* first_message(uint64_t bits) {
@@ -122,6 +137,14 @@ RM_HD uint32_t name_bits(const uint64_t* off, uint64_t i, uint64_t n, uint64_t n
   return e;
 }
 RM_HD uint32_t time_bits(double t) { return t == t ? 0u : 1u << kETimeNaN; }
+RM_HD uint32_t key_bits(uint64_t key) { return key == kPadKey ? 1u << kEPadKey : 0u; }
+RM_HD uint32_t shard_bits(const ShardRec& x) {
+  uint32_t e = 0u;
+  if (x.rank >= x.nranks) e |= 1u << kEShardRank;
+  if (x.nranks == 0u || x.nranks > kMaxRanks) e |= 1u << kEShardRanks;
+  if (x.pad != 0u) e |= 1u << kEShardPad;
+  return e;
+}
 
 // ---- host only from here
 inline uint64_t checksum(const void* p, uint64_t bytes) {
@@ -218,6 +241,14 @@ inline std::string parse_table(const void* blob, uint64_t len, Table& t) {
     if (t.ent[kTileMeta].count != 1) return "snapshot: the tile store's numbers are not one record";
     if (t.ent[kTileRows].count >= 0x7fffffffull) return "snapshot: too many tile rows";
   }
+  // rule 17: the keys and the shard record come together, beside tile rows, a key per row
+  if (t.has[kTileKeys] && !t.has[kShardRec]) return "snapshot: tile keys without a shard record";
+  if (t.has[kShardRec] && !t.has[kTileKeys]) return "snapshot: a shard record without tile keys";
+  if (t.has[kShardRec]) {
+    if (!t.has[kTileRows]) return "snapshot: tile keys and a shard record without tile rows";
+    if (t.ent[kShardRec].count != 1) return "snapshot: the shard record is not one record";
+    if (t.ent[kTileKeys].count != t.ent[kTileRows].count) return "snapshot: the tile keys' count is not the row count";
+  }
   return "";
 }
 
@@ -225,6 +256,12 @@ inline TileMeta tile_meta(const void* blob, const Table& t) {
   TileMeta m{};
   if (t.has[kTileMeta]) std::memcpy(&m, (const uint8_t*)blob + t.ent[kTileMeta].off, sizeof m);
   return m;
+}
+
+inline ShardRec shard_rec(const void* blob, const Table& t) {   // (no record: all zero, nranks 0)
+  ShardRec r{};
+  if (t.has[kShardRec]) std::memcpy(&r, (const uint8_t*)blob + t.ent[kShardRec].off, sizeof r);
+  return r;
 }
 
 // what depends on the loading objects (0: that object is not loaded)
@@ -237,8 +274,9 @@ inline std::string check_targets(const void* blob, const Table& t, uint32_t n_ve
 }
 
 // The whole rule on the host: header, table, checksums, elements.  info: version, bytes, names,
-// vehicles, points, rows, quantisation, user offset, user bytes.
-inline std::string check_host(const void* blob, uint64_t len, uint64_t info[9], uint32_t n_vehicles = 0) {
+// vehicles, points, rows, quantisation, user offset, user bytes; shard (null: not wanted): the
+// shard record's rank, nranks and calls (all 0 in a blob without one).
+inline std::string check_host(const void* blob, uint64_t len, uint64_t info[9], uint32_t n_vehicles = 0, uint64_t shard[3] = nullptr) {
   Table t;
   std::string why = parse_table(blob, len, t);
   if (!why.empty()) return why;
@@ -265,7 +303,16 @@ inline std::string check_host(const void* blob, uint64_t len, uint64_t info[9], 
         if (!seen.emplace(nb + off[i], (size_t)(off[i + 1] - off[i])).second) bits |= 1ull << kEDupName;
     }
   }
+  if (t.has[kShardRec] && !(bits & 1ull)) {
+    const uint64_t* key = (const uint64_t*)(s + t.ent[kTileKeys].off);
+    for (uint64_t i = 0; i < t.rows(); ++i) bits |= key_bits(key[i]);
+    bits |= shard_bits(shard_rec(blob, t));
+  }
   if (bits) return first_message(bits);
+  if (shard) {
+    const ShardRec r = shard_rec(blob, t);
+    shard[0] = r.rank; shard[1] = r.nranks; shard[2] = r.calls;
+  }
   if (info) {
     info[0] = t.h.version; info[1] = len; info[2] = t.names(); info[3] = t.vehicles(); info[4] = t.points();
     info[5] = t.rows(); info[6] = tile_meta(blob, t).quantisation;

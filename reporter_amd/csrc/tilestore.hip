@@ -153,6 +153,13 @@ __global__ void k_ts_backfill(uint64_t b, uint64_t e, const TileStoreRow* rows, 
   if (k < e) keys[k] = key_hi | ((rows[k].arrival - arrival0) & 0xffffffffull);
 }
 
+// rows [at, at + n) of the gathered rows, taken from a one-rank snapshot (rule 17): call 0, keyed by
+// their position in that store, whose order is arrival order
+__global__ void k_ts_poskey(uint64_t n, uint64_t at, unsigned long long* keys) {
+  const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k < n) keys[at + k] = k & 0xffffffffull;
+}
+
 // the exchange (rule 16): the gathered rows whose file this rank writes (padding rows carry kTsPadKey)
 __global__ void k_ts_own(uint64_t n, const TileStoreRow* rows, const unsigned long long* keys, int rank, int nranks,
                          unsigned long long* flag) {
@@ -511,6 +518,55 @@ void TileStore::snapshot_loaded(uint64_t n_rows, uint64_t arrivals) {
   p_->arrivals = arrivals;
   p_->restored = n_rows;
   p_->unkeyed.clear();
+}
+
+// a sharded stream's snapshot (DESIGN.md §3 rule 17)
+uint64_t TileStore::calls() const { return p_->calls; }
+const void* TileStore::snapshot_keys() {
+  Impl& s = *p_;
+  RM_HIP(hipSetDevice(s.device));
+  s.make_keyed();
+  return s.keys;
+}
+void TileStore::snapshot_clear() {
+  Impl& s = *p_;
+  s.n_rows = 0; s.arrivals = 0; s.calls = 0; s.restored = 0;
+  s.unkeyed.clear();
+}
+void TileStore::snapshot_merge(const void* const* rows, const void* const* keys, const uint64_t* counts, uint32_t n_parts,
+                               int nranks, int rank, uint64_t calls, uint64_t arrivals) {
+  Impl& s = *p_;
+  if (nranks < 1 || rank < 0 || rank >= nranks) throw std::runtime_error("tile store import needs 0 <= rank < nranks");
+  RM_HIP(hipSetDevice(s.device));
+  if (s.n_rows) throw std::runtime_error("snapshot: the tile store is not empty");
+  uint64_t total = 0;
+  for (uint32_t i = 0; i < n_parts; ++i) {
+    total += counts[i];
+    if (total >= kTsMaxRows) throw BatchTooLarge("tile store too large (rows >= 2^31 - 1)");
+  }
+  s.make_keyed();
+  s.begin_exchange();
+  try {
+    s.ensure_gather(total);
+    s.xtimer.tic(1, s.st);
+    uint64_t at = 0;
+    for (uint32_t i = 0; i < n_parts; ++i) {
+      const uint64_t c = counts[i];
+      if (!c) continue;
+      RM_HIP(hipMemcpyAsync(s.grows + at, rows[i], c * sizeof(TileStoreRow), hipMemcpyDeviceToDevice, s.st));
+      if (keys[i]) RM_HIP(hipMemcpyAsync(s.gkeys + at, keys[i], c * 8, hipMemcpyDeviceToDevice, s.st));
+      else hipLaunchKernelGGL(k_ts_poskey, dim3(grid(c)), dim3(256), 0, s.st, c, at, s.gkeys);
+      at += c;
+    }
+    s.xtimer.toc(s.st);
+    RM_HIP(hipGetLastError());
+    s.merge_owned(total, 0, 0, nranks, rank, nullptr);
+  } catch (...) {
+    snapshot_clear();
+    throw;
+  }
+  s.calls = calls;
+  s.arrivals = arrivals;
 }
 
 void TileStore::add(const TileSegment* segs, uint64_t n, uint64_t out[4]) {

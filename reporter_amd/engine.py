@@ -1056,16 +1056,63 @@ def load_stream(blob, sessions=None, directory=None, store=None):
 
 
 def snapshot_info(blob):
-    """Check a snapshot on the host alone (rm_snapshot_check_host: header, table, checksums and the
-    structural rule) and return its numbers (SNAPSHOT_INFO) and its user bytes; raises with the reason."""
+    """Check a snapshot on the host alone (rm_snapshot_check_host_shard: header, table, checksums and
+    the structural rule) and return its numbers (SNAPSHOT_INFO) and its user bytes; a sharded
+    stream's blob (rule 17) also gives rank, nranks and calls.  Raises with the reason."""
     blob = bytes(blob)
-    info = (C.c_uint64 * 9)()
+    info = (C.c_uint64 * 12)()
     err = C.create_string_buffer(512)
-    if _lib.lib().rm_snapshot_check_host(blob, len(blob), info, err, 512) != 0:
+    if _lib.lib().rm_snapshot_check_host_shard(blob, len(blob), info, err, 512) != 0:
         raise _lib.RmError(err.value.decode("utf-8", "replace"))
     d = dict(zip(SNAPSHOT_INFO, (int(x) for x in info)))
     d["user"] = blob[d["user_offset"]:d["user_offset"] + d["user_bytes"]]
+    if info[10]:
+        d.update(rank=int(info[9]), nranks=int(info[10]), calls=int(info[11]))
     return d
+
+
+def save_stream_shard(sessions=None, directory=None, store=None, shard=(0, 1), user=b""):
+    """Rank shard[0]'s blob of a stream of shard[1] ranks (rm_snapshot_save_shard; DESIGN.md §3 rule
+    17): save_stream's sections, the tile rows' keys and the shard record.  The store is needed and
+    keeps keys from here on; nothing the stream will output changes."""
+    blob = C.c_void_p()
+    n = C.c_size_t()
+    out = (C.c_uint64 * 6)()
+    ms = (C.c_double * 6)()
+    user = bytes(user)
+    rank, nranks = (int(x) for x in shard)
+    handles = (_snapshot_handle(sessions, "sessions"), _snapshot_handle(directory, "directory"), _snapshot_handle(store, "store"))
+    _lib.check(_lib.lib().rm_snapshot_save_shard(*handles, rank, nranks, user, len(user), C.byref(blob), C.byref(n), out, ms))
+    try:
+        raw = C.string_at(blob.value, n.value)
+    finally:
+        _lib.lib().rm_free(blob)
+    save_stream_shard.last = dict(zip(SNAPSHOT_COUNTS, (int(x) for x in out)),
+                                  ms=dict(zip(("pack", "gather", "checksum", "download"), (float(x) for x in ms))))
+    return raw
+
+
+SNAPSHOT_SHARD_COUNTS = SNAPSHOT_COUNTS + ("calls", "saved_ranks")
+
+
+def load_stream_shards(blobs, sessions=None, directory=None, store=None, shard=(0, 1)):
+    """Restore, into empty objects, what rank shard[0] of shard[1] holds of the state that the blobs'
+    ranks saved (rm_snapshot_load_shards): `blobs` are all the blobs of one save_stream_shard round in
+    any order, or one save_stream blob, which counts as rank 0 of 1.  Returns the counts
+    (SNAPSHOT_SHARD_COUNTS) and the device ms of upload, check, unpack and the rows' merge.  A load
+    that raises leaves the objects empty and usable."""
+    blobs = [bytes(b) for b in blobs]
+    n = len(blobs)
+    ptrs = (C.c_char_p * max(n, 1))(*blobs)
+    lens = (C.c_size_t * max(n, 1))(*[len(b) for b in blobs])
+    out = (C.c_uint64 * 8)()
+    ms = (C.c_double * 6)()
+    rank, nranks = (int(x) for x in shard)
+    handles = (_snapshot_handle(sessions, "sessions"), _snapshot_handle(directory, "directory"), _snapshot_handle(store, "store"))
+    _lib.check(_lib.lib().rm_snapshot_load_shards(*handles, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, rank, nranks,
+                                                  out, ms))
+    return dict(zip(SNAPSHOT_SHARD_COUNTS, (int(x) for x in out)),
+                ms=dict(zip(("upload", "check", "unpack", "rows"), (float(x) for x in ms))))
 
 
 def split_by_points(trace_off, parts):

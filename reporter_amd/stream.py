@@ -23,7 +23,13 @@ from torch.distributed.run through RANK / WORLD_SIZE / LOCAL_RANK); every rank r
 the text, holds the sessions of the vehicles it owns, and before each flush the tile rows go to the
 rank that owns their file, which alone writes it.  --transport host carries the exchange over gloo,
 so several ranks can share one GPU (rank r takes GPU LOCAL_RANK modulo the device count).  Rank 0
-prints the summed statistics.  --ranks cannot be combined with --checkpoint.
+prints the summed statistics.
+
+With --ranks N and --checkpoint FILE (DESIGN.md §3 rule 17) every rank writes its shard of the state
+to FILE.g<generation>.r<rank>, and FILE itself becomes a small manifest naming them; --resume reads
+the manifest and all its rank files and continues on any number of ranks, the saved number or
+another (no --ranks: one), and a one-rank FILE resumes on several ranks as well.  A resume that
+finds a rank file missing, or of another save than the manifest's, refuses.
 """
 import argparse
 import json
@@ -65,6 +71,54 @@ def write_checkpoint(path, blob):
     os.replace(tmp, path)
 
 
+def rank_file(path, generation, rank):
+    """The file of one rank's shard of a several-rank checkpoint (DESIGN.md §3 rule 17)."""
+    return "%s.g%d.r%d" % (path, generation, rank)
+
+
+def manifest_blob(user):
+    """A snapshot blob (snapshot.hpp, version 1) that holds user bytes and nothing else: the manifest
+    of a several-rank checkpoint.  engine.snapshot_info reads it like any other."""
+    import struct
+    seed, mask = 0x9E3779B97F4A7C15, (1 << 64) - 1
+
+    def checksum(data):
+        data = data + b"\0" * (-len(data) % 8)
+        words = struct.unpack("<%dQ" % (len(data) // 8), data)
+        return sum(((w ^ seed) * (2 * i + 1)) & mask for i, w in enumerate(words)) & mask
+    user = bytes(user)
+    total = 80 + ((len(user) + 15) & ~15)   # header 32, one table entry 40, padded to 80
+    entry = struct.pack("<IIQQQQ", 1, 1, 80, len(user), len(user), checksum(user))
+    tsum = checksum(struct.pack("<QIIQQ", 0x0150414E534D5253, 1, 1, total, 0) + entry)
+    head = struct.pack("<QIIQQ", 0x0150414E534D5253, 1, 1, total, tsum) + entry
+    return head + b"\0" * 8 + user + b"\0" * (-len(user) % 16)
+
+
+def read_checkpoint(path):
+    """The blobs a resume loads and their user records: FILE itself (a one-rank checkpoint), or, when
+    FILE is the manifest of a several-rank one, every rank file of its generation -- all present and
+    of that one save, else ValueError.  Returns (blobs, users, manifest or None)."""
+    from . import engine
+    with open(path, "rb") as f:
+        blob = f.read()
+    info = engine.snapshot_info(blob)
+    user = json.loads(info["user"].decode())
+    if "ranks" not in user:
+        return [blob], [user], None
+    blobs, users = [], []
+    for r in range(user["ranks"]):
+        p = rank_file(path, user["generation"], r)
+        if not os.path.exists(p):
+            raise ValueError("the checkpoint is incomplete: %s, which its manifest names, is missing" % p)
+        with open(p, "rb") as f:
+            blobs.append(f.read())
+        u = json.loads(engine.snapshot_info(blobs[-1])["user"].decode())
+        if u.get("generation") != user["generation"] or u.get("ranks") != user["ranks"] or u.get("rank") != r:
+            raise ValueError("the checkpoint is incomplete: %s is of another save than its manifest" % p)
+        users.append(u)
+    return blobs, users, user
+
+
 def write_flush(files, dest, k):
     from .batch import write_tiles
     out = {}
@@ -99,26 +153,59 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
     stats = dict(polls=0, messages=0, dropped=0, forwarded=0, flushes=0, files=0)
     rank, nranks = (comm.rank, comm.world_size) if comm is not None else (0, 1)
     shard = (rank, nranks) if comm is not None else None
-    if comm is not None and (checkpoint or resume):
-        raise ValueError("a stream of several ranks keeps no checkpoint")
     last_flush = now = None
     inputs = [[os.path.abspath(p), os.path.getsize(p)] for p in paths]
     pos = [0, 0]   # file index and byte offset of the next poll
+    # a several-rank checkpoint (rule 17): the generation last written and the rank files it has;
+    # sharded: this stream's state is saved as shards (several ranks, or one that resumed from shards)
+    generation, old_files, sharded = 0, [], comm is not None
     try:
         if resume:
-            with open(checkpoint, "rb") as f:
-                blob = f.read()
-            user = json.loads(engine.snapshot_info(blob)["user"].decode())
-            if user["inputs"] != inputs:
+            blobs, users, manifest = read_checkpoint(checkpoint)
+            if (manifest or users[0])["inputs"] != inputs:
                 raise ValueError("the checkpoint was written for other inputs (their list or sizes differ)")
-            if user.get("done"):   # written behind the final flush: nothing is left to do
-                return user["stats"]
-            engine.load_stream(blob, sess, vdir, store)
-            pos, now, last_flush, stats = [user["file"], user["offset"]], user["now"], user["last_flush"], user["stats"]
+            if (manifest or users[0]).get("done"):   # written behind the final flush: nothing is left to do
+                return (manifest or users[0])["stats"]
+            user = users[0]
+            for u in users[1:]:   # the ranks ran in lockstep: position and stream time are replicated
+                if any(u[k] != user[k] for k in ("inputs", "file", "offset", "now", "last_flush")):
+                    raise ValueError("the checkpoint's rank files disagree on the stream's position")
+            if manifest is None and comm is None and "nranks" not in engine.snapshot_info(blobs[0]):
+                engine.load_stream(blobs[0], sess, vdir, store)
+            else:
+                engine.load_stream_shards(blobs, sess, vdir, store, shard=(rank, nranks))
+                sharded = True
+            pos, now, last_flush, stats = [user["file"], user["offset"]], user["now"], user["last_flush"], dict(user["stats"])
+            for k in ("forwarded", "files"):   # what the saved ranks did apart: their sum to rank 0
+                stats[k] = sum(u["stats"][k] for u in users) if rank == 0 else 0
+            if manifest is not None:
+                generation = manifest["generation"]
+                old_files = [rank_file(checkpoint, generation, r) for r in range(manifest["ranks"])]
 
         def save(done=False):
+            nonlocal generation, old_files
             user = dict(inputs=inputs, file=pos[0], offset=pos[1], now=now, last_flush=last_flush, stats=stats, done=done)
-            write_checkpoint(checkpoint, engine.save_stream(sess, vdir, store, json.dumps(user).encode()))
+            if not sharded:
+                write_checkpoint(checkpoint, engine.save_stream(sess, vdir, store, json.dumps(user).encode()))
+                return
+            # every rank its file of a new generation; then, all written, the manifest replaces FILE;
+            # only then do the files of the generation before go: a run killed anywhere leaves a
+            # manifest whose rank files all exist and are of one save
+            generation += 1
+            user.update(rank=rank, ranks=nranks, generation=generation)
+            blob = engine.save_stream_shard(sess, vdir, store, (rank, nranks), json.dumps(user).encode())
+            write_checkpoint(rank_file(checkpoint, generation, rank), blob)
+            if comm is not None:
+                comm.barrier()
+            if rank == 0:
+                head = dict(ranks=nranks, generation=generation, inputs=inputs, done=done)
+                if done:
+                    head["stats"] = stats
+                write_checkpoint(checkpoint, manifest_blob(json.dumps(head).encode()))
+                for p in old_files:
+                    if os.path.exists(p):
+                        os.remove(p)
+            old_files = [rank_file(checkpoint, generation, r) for r in range(nranks)]
 
         def flush():
             if comm is not None:
@@ -154,6 +241,9 @@ def run(paths, conf, dest, formatter, mode="auto", report_levels=(0, 1), transit
         if stop_after_polls is not None:
             save()
             stats["stopped"] = True
+            if comm is not None:
+                for k in ("forwarded", "files"):
+                    stats[k] = int(comm.allreduce_host(stats[k]))
             return stats
         if now is not None:
             out = sess.punctuate(int(now * 1000) + 10 ** 7)   # every vehicle is stale: all report and leave
@@ -209,8 +299,6 @@ def main(argv=None):
     world = int(os.environ.get("WORLD_SIZE", "1")) if "RANK" in os.environ else 0
     if world and a.ranks > 1 and a.ranks != world:
         ap.error("--ranks %d under a launcher that started %d ranks (WORLD_SIZE)" % (a.ranks, world))
-    if (a.ranks > 1 or world > 1) and a.checkpoint:
-        ap.error("--ranks cannot be combined with --checkpoint (a sharded stream's state is not saved)")
     if world > MAX_RANKS:
         ap.error("at most %d ranks" % MAX_RANKS)
     if a.ranks > 1 and not world:

@@ -20,7 +20,13 @@ instead measures the stream snapshot (rule 15) on the separated-value messages: 
 load, and the remaining pushes; the outputs of the pushes behind K and the hash of the flushed files
 must equal the unbroken run's.  Reported: the blob's bytes per section, the save and load parts (HIP
 events, after one warm-up save and load), the checksum kernel's bytes/s, and beside them the only
-read-out there was before, VehicleSessions.store() plus VehicleDirectory.names() on the same state."""
+read-out there was before, VehicleSessions.store() plus VehicleDirectory.names() on the same state.
+
+    python scripts/stream_probe.py --snapshot-shard-at 5 [--out profiles/snapshot_shard/snapshot_shard_probe.json]
+
+measures the sharded snapshot (rule 17) beside the plain one: two ranks sharing this GPU and process,
+saved after push K, loaded on two ranks and on three, the calls alternating; the loaded sets go on to
+the end and must flush the unbroken run's files."""
 import argparse
 import json
 import os
@@ -176,6 +182,107 @@ def snapshot_probe(bm, texts, fmt, n_vehicles, at):
                             note="VehicleSessions.store() + VehicleDirectory.names(): read-outs only, no tile rows, nothing loads them"))
 
 
+def snapshot_shard_probe(eng, texts, fmt, n_vehicles, at, runs=5):
+    """Rule 17 beside rule 15 on one state: the stream runs unbroken on one rank, then to push `at`
+    once on one rank and once on two ranks sharing this GPU and process (the exchange by export /
+    import).  After a warm-up of each kind, `runs` rounds alternate: the plain save and load, the
+    two ranks' shard saves, the loads of the two blobs on two ranks and on three.  The two- and
+    three-rank loads of the last round go on to the end; their files must be the unbroken run's."""
+    import hashlib
+    digest = lambda files: hashlib.sha256(b"".join(k.encode() + b"\0" + v for k, v in sorted(files.items()))).hexdigest()
+
+    def make(R):
+        bms = [engine.BatchMatcher(eng) for _ in range(R)]
+        return [(bm, engine.VehicleSessions(bm, n_vehicles), engine.VehicleDirectory(n_vehicles), engine.TileStore(0)) for bm in bms]
+
+    def close(sets):
+        for s in sets:
+            for o in reversed(s):
+                o.close()
+
+    def pushes(sets, first, last, sharded):
+        R = len(sets)
+        for text in texts[first:last]:
+            for r, (_, sess, vdir, store) in enumerate(sets):
+                sess.push_messages([text], fmt, vdir, shard=(r, R) if sharded else None)
+                store.add_session(sess)
+
+    def finish(sets, sharded):
+        if sharded:
+            blobs = [s[3].export_rows() for s in sets]
+            for r, s in enumerate(sets):
+                s[3].import_owned(blobs, r, len(sets))
+        files = {}
+        for s in sets:
+            got = s[3].flush()[0]
+            assert not set(got) & set(files)
+            files.update(got)
+        return digest(files), len(files)
+
+    timed = lambda f: (lambda t0, r: (r, (time.perf_counter() - t0) * 1e3))(time.perf_counter(), f())
+    one = make(1)
+    pushes(one, 0, len(texts), False)
+    want = finish(one, False)
+    close(one)
+    print("unbroken run done", file=sys.stderr, flush=True)
+    one, two = make(1), make(2)
+    pushes(one, 0, at, False)
+    pushes(two, 0, at, True)
+    print("states at push %d ready" % at, file=sys.stderr, flush=True)
+
+    def save_plain():
+        blob, wall = timed(lambda: engine.save_stream(*one[0][1:], user=b"stream_probe"))
+        return blob, dict(engine.save_stream.last["ms"], wall=wall, bytes=len(blob))
+
+    def save_shard(r):
+        blob, wall = timed(lambda: engine.save_stream_shard(*two[r][1:], shard=(r, 2), user=b"stream_probe"))
+        return blob, dict(engine.save_stream_shard.last["ms"], wall=wall, bytes=len(blob))
+
+    def load_plain(blob):
+        s = make(1)
+        got, wall = timed(lambda: engine.load_stream(blob, *s[0][1:]))
+        close(s)
+        return dict(got["ms"], wall=wall)
+
+    def load_shards(blobs, N, keep=False):
+        sets, out = make(N), []
+        for r in range(N):
+            got, wall = timed(lambda: engine.load_stream_shards(blobs, *sets[r][1:], shard=(r, N)))
+            out.append(dict(got["ms"], wall=wall, held=dict(vehicles=got["vehicles"], points=got["points"], rows=got["rows"])))
+        if keep:
+            return out, sets
+        close(sets)
+        return out, None
+
+    plain, _ = save_plain()             # one warm-up of each kind
+    shards = [save_shard(r)[0] for r in range(2)]
+    load_plain(plain)
+    load_shards(shards, 2)
+    load_shards(shards, 3)
+    rounds = []
+    for k in range(runs):
+        rd = {}
+        plain, rd["plain_save"] = save_plain()
+        saves = [save_shard(r) for r in range(2)]
+        shards, rd["shard_save"] = [b for b, _ in saves], [m for _, m in saves]
+        rd["plain_load"] = load_plain(plain)
+        rd["shard_load_2_to_2"], keep2 = load_shards(shards, 2, keep=k + 1 == runs)
+        rd["shard_load_2_to_3"], keep3 = load_shards(shards, 3, keep=k + 1 == runs)
+        rounds.append(rd)
+    close(one)
+    close(two)
+    ends = {}
+    for name, sets in (("2_to_2", keep2), ("2_to_3", keep3)):
+        pushes(sets, at, len(texts), True)
+        ends[name] = finish(sets, True)
+        close(sets)
+    infos = [engine.snapshot_info(b) for b in [plain] + shards]
+    return dict(snapshot_at=at, pushes=len(texts), flush_sha256=want[0], files=want[1],
+                continued_equal={k: v == want for k, v in ends.items()},
+                blobs=[{k: i.get(k) for k in ("bytes", "names", "vehicles", "points", "rows", "rank", "nranks", "calls")} for i in infos],
+                rounds=rounds, note="two ranks sharing one GPU and process: the calls' cost, not scaling")
+
+
 def sharded_probe(bm, texts, fmt, n_vehicles, comm, flush_every):
     """The stream of rule 16 on this rank: masked pushes, the tile store fed device to device, and every
     `flush_every` pushes (and at the end) the exchange and a flush.  Per flush the exchange's three stage
@@ -214,6 +321,8 @@ def main():
     ap.add_argument("--per-push", type=int, default=60)
     ap.add_argument("--runs", type=int, default=4)
     ap.add_argument("--snapshot-at", type=int, help="measure the stream snapshot: save after this push, load, finish")
+    ap.add_argument("--snapshot-shard-at", type=int, help="measure the sharded snapshot (rule 17) beside the plain one: two "
+                    "ranks sharing this GPU, saved after this push, loaded on two and on three ranks")
     ap.add_argument("--out")
     ap.add_argument("--ranks", type=int, default=1, help="the stream of DESIGN.md §3 rule 16 on this many ranks (one fresh "
                     "process each): per flush the exchange's stage times and rows moved, one JSON file per rank")
@@ -227,6 +336,7 @@ def main():
         os.environ["PYTHONPATH"] = env_path
         sys.exit(dist.self_launch("stream_probe", sys.argv[1:], a.ranks))
     a.out = a.out or (os.path.join("profiles", "snapshot", "snapshot_probe.json") if a.snapshot_at is not None
+                      else os.path.join("profiles", "snapshot_shard", "snapshot_shard_probe.json") if a.snapshot_shard_at is not None
                       else os.path.join("profiles", "stream", "stream_probe.json"))
     cfg = world.CONFIGS["C2"]
     tmp = tempfile.mkdtemp(prefix="stream_probe")
@@ -241,7 +351,8 @@ def main():
         arr[f] = np.ascontiguousarray(tr[f][order])
     per = a.per_push * T
     cuts = [(s, min(s + per, T * n)) for s in range(0, T * n, per)]
-    texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in ((0,) if a.snapshot_at is not None else (0, 1))}
+    sv_only = a.snapshot_at is not None or a.snapshot_shard_at is not None
+    texts = {kind: [write_text(arr, s, e, kind) for s, e in cuts] for kind in ((0,) if sv_only else (0, 1))}
     fmt = {0: engine.MessageFormat(0), 1: engine.MessageFormat(1)}
     device = 0
     if ranked:   # each rank its own GPU, as python -m reporter_amd.stream takes them; only the host transport may share one
@@ -272,6 +383,19 @@ def main():
             f.write(json.dumps(out) + "\n")
         if rank == 0:
             print(json.dumps(dict(out, pushes=None)))
+        bm.close()
+        eng.close()
+        return
+    if a.snapshot_shard_at is not None:
+        print("text written", file=sys.stderr, flush=True)
+        route_a(bm, texts[0][:2], fmt[0], T)   # warm the route
+        out = dict(args=dict(vehicles=a.vehicles, points=a.points, per_push=a.per_push, snapshot_shard_at=a.snapshot_shard_at),
+                   messages_per_push=per, **snapshot_shard_probe(eng, texts[0], fmt[0], T, a.snapshot_shard_at))
+        line = json.dumps(out)
+        print(line)
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
         bm.close()
         eng.close()
         return

@@ -431,6 +431,18 @@ int rm_runner_get_batch(rm_runner* r, uint32_t* trace_off, float* lon, float* la
  * uuid 0, time 1, lat 2, lon 3, accuracy 4 of the trace files (:113), epoch seconds, no cap, no box. */
 typedef struct { uint8_t sep; int32_t uuid_col, time_col, lat_col, lon_col, acc_col, time_format, accuracy_cap, use_bbox; double bbox[4]; } rm_line_format;
 void rm_default_line_format(rm_line_format* f);
+/* Date patterns (DESIGN.md §3 rule 18): the last argument of the reference's formatter string, a
+ * Joda DateTimeFormat pattern such as yyyy-MM-dd'T'HH:mm:ssZZ, compiled once and read on the device.
+ * rm_time_pattern compiles and registers a pattern: an id >= 16 to put into
+ * rm_line_format.time_format, or -1 with the reason in err.  The same text gives the same id; at
+ * most 240 patterns per process; thread-safe; ids are process-local (never stored in a snapshot).
+ * time_format is 0, 1 or such an id: anything else fails the call that takes the format.  For
+ * separated values a pattern whose literals hold the separator byte is a format error. */
+int32_t rm_time_pattern(const char* pattern, char* err, size_t errlen);
+/* the text of pattern `id` (NUL-terminated, cut to outlen): 0, or 1 when nobody registered the id */
+int     rm_time_pattern_text(int32_t id, char* out, size_t outlen);
+/* host only: one text under one pattern -> 0 and *seconds, 1 (malformed), or 2 (no such id) */
+int     rm_time_pattern_parse(int32_t id, const char* text, size_t n, double* seconds);
 /* The input: n_chunks byte ranges (one per file; a chunk without a final newline ends its last
  * line), under 2^32 bytes together.  Every window takes opts[0]. */
 typedef struct { uint32_t n_chunks; const char* const* data; const uint64_t* len; rm_line_format fmt;

@@ -203,6 +203,9 @@ PROTOTYPES = [
     ("rm_runner_get_trace_uuid", C.c_int, [P, P]),
     ("rm_runner_get_batch", C.c_int, [P, P, P, P, P, P]),
     ("rm_default_line_format", None, [C.POINTER(RmLineFormat)]),
+    ("rm_time_pattern", C.c_int32, [C.c_char_p, C.c_char_p, C.c_size_t]),
+    ("rm_time_pattern_text", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t]),
+    ("rm_time_pattern_parse", C.c_int, [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_double)]),
     ("rm_runner_run_lines", C.c_int, [P, C.POINTER(RmLinesDesc), C.POINTER(RmRunParams)]),
     ("rm_runner_parse_lines", C.c_int, [P, C.POINTER(RmLinesDesc)]),
     ("rm_runner_lines_info", C.c_int, [P, C.POINTER(C.c_uint64)]),

@@ -163,7 +163,8 @@ def main(argv=None):
     ap.add_argument("--source-id", default="smpl_rprt")
     ap.add_argument("--ingest", choices=("device", "host"), default="device", help="where the trace lines are parsed")
     ap.add_argument("--formatter", help="separated-value formatter string, e.g. ',sv,\\|,1,9,10,0,5,yyyy-MM-dd HH:mm:ss' "
-                    "(default: the trace files' uuid,time,lat,lon,accuracy)")
+                    "(default: the trace files' uuid,time,lat,lon,accuracy); the last argument is a date pattern, "
+                    "e.g. yyyy-MM-dd'T'HH:mm:ssZZ or yyyyMMddHHmmss (DESIGN.md rule 18)")
     ap.add_argument("--bbox", help="min_lat,min_lon,max_lat,max_lon: points outside are dropped")
     ap.add_argument("--accuracy-cap", type=int, default=0, help="cap on the accuracy column (0: none)")
     a = ap.parse_args(argv)

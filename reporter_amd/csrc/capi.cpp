@@ -1753,6 +1753,31 @@ void rm_default_line_format(rm_line_format* f) {
   const sv::Format d = sv::default_format();
   std::memcpy(f, &d, sizeof d);
 }
+int32_t rm_time_pattern(const char* pattern, char* err, size_t errlen) {
+  std::string why;
+  int32_t id = -1;
+  try {
+    id = time_pattern_register(pattern, why);
+  } catch (const std::exception& e) {
+    why = e.what();
+  }
+  if (id < 0 && err && errlen) std::snprintf(err, errlen, "%s", why.c_str());
+  return id;
+}
+int rm_time_pattern_text(int32_t id, char* out, size_t outlen) {
+  const tp::Pattern* p = time_pattern_find(id);
+  if (!p) return 1;
+  if (out && outlen) std::snprintf(out, outlen, "%s", p->text);
+  return 0;
+}
+int rm_time_pattern_parse(int32_t id, const char* text, size_t n, double* seconds) {
+  const tp::Pattern* p = time_pattern_find(id);
+  if (!p) return 2;
+  double v = 0.0;
+  if (!text || n > 0xffff || !tp::match(p->prog, (const uint8_t*)text, (uint32_t)n, v)) return 1;
+  if (seconds) *seconds = v;
+  return 0;
+}
 static LinesDesc to_lines(const rm_lines_desc* d) {
   if (!d) throw std::runtime_error("lines descriptor is NULL");
   LinesDesc ld;

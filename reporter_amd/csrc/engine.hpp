@@ -260,6 +260,12 @@ struct LineState;   // lines.hip: the device buffers and the last call's results
 // info as Matcher::lines_info
 void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
                       uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len);
+// The process's date patterns (DESIGN.md §3 rule 18; lines.hip).  register: the pattern compiled
+// and kept -> the id (16 and up) to put into sv::Format::time_format, the same id for the same
+// text, or -1 with the reason in err.  find: null for an id nobody registered.  Both thread-safe;
+// a found pattern stays where it is for the life of the process.
+int32_t time_pattern_register(const char* pattern, std::string& err);
+const tp::Pattern* time_pattern_find(int32_t id);
 
 // Raw stream messages for Matcher::parse_messages (lines.hip; DESIGN.md §3 rule 14): chunks as in
 // LinesDesc, one message per line, either kind of msg::Format
@@ -711,7 +717,7 @@ class Matcher {
   std::string tiles(const TileParams& tp, struct TileComm* comm = nullptr);
 
  private:
-  void parse_text(const MessagesDesc& d);
+  void parse_text(const MessagesDesc& d, const tp::Pattern* pat);
   void ensure(uint64_t points, uint32_t traces, uint32_t nopts);
   void check_batch(uint32_t T, const uint32_t* trace_off, const MatchOptions* opts, uint32_t n_opts,
                    const uint32_t* trace_opt);

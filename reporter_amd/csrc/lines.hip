@@ -24,6 +24,10 @@
 // msg::generic_message -- and a tolerant call drops malformed lines (patched to "bad": no point),
 // counts them and lists the first 64.  The directory (directory.hip) then turns the per-call vehicle
 // numbers left here into indices that hold for the whole stream.
+//
+// Date patterns (rule 18): a time_format from 16 up is the id of a pattern registered in this
+// process (time_pattern_register below).  time_pattern_of resolves it, once per call; the program
+// goes to k_line_parse<KIND, true> by value and to the host's generic readers by pointer.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -31,6 +35,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <mutex>
 #include <string_view>
 #include <unordered_map>
 
@@ -89,11 +94,15 @@ struct LineArrays {   // one entry per line
 // KIND 0: separated values (rule 11); KIND 1: JSON messages (rule 14), whose five keys arrive by
 // value in `keys` (KIND 0 takes an empty struct there: its code and arguments are what they were)
 struct NoKeys {};
-template <int KIND>
+// PAT: the time is read by a date pattern (rule 18), whose program arrives by value in `prog`; it
+// is wave-uniform, so the step loop of tp::match branches on scalars.  Without one `prog` is an
+// empty struct behind the other arguments, which stay where they were.
+struct NoProgram {};
+template <int KIND, bool PAT>
 __global__ void __launch_bounds__(64) k_line_parse(const uint8_t* buf, uint64_t N, const uint32_t* first,
                                                    const uint32_t* cnt, uint32_t L, sv::Format fmt,
                                                    std::conditional_t<KIND == 1, msg::Keys, NoKeys> keys, LineArrays o,
-                                                   uint32_t* err) {
+                                                   uint32_t* err, std::conditional_t<PAT, tp::Program, NoProgram> prog) {
   __shared__ uint4 win4[kLineLds / 16];
   __shared__ uint16_t starts[kLineRing];
   const uint8_t* win = reinterpret_cast<const uint8_t*>(win4);   // win[i]: text position a - kLineFront + i
@@ -112,8 +121,10 @@ __global__ void __launch_bounds__(64) k_line_parse(const uint8_t* buf, uint64_t 
       const uint32_t pos = starts[(head + lane) & (kLineRing - 1)];
       sv::Line ln;
       uint32_t st;
-      if constexpr (KIND == 1) st = msg::compact_json(win + kLineFront + pos, fmt, keys, ln);
-      else st = sv::compact_line(win + kLineFront + pos, fmt, ln);
+      const tp::Program* pp = nullptr;
+      if constexpr (PAT) pp = &prog;
+      if constexpr (KIND == 1) st = msg::compact_json(win + kLineFront + pos, fmt, keys, ln, pp);
+      else st = sv::compact_line(win + kLineFront + pos, fmt, ln, pp);
       o.status[k] = (uint8_t)st;
       if (st == sv::kPoint) {
         o.lat[k] = ln.lat;
@@ -296,9 +307,43 @@ struct HostLine {
   const char* why = nullptr;
 };
 
+// the process's date patterns: entries are written once, under the lock, and never move
+struct PatternTable {
+  std::mutex mu;
+  int32_t n = 0;
+  tp::Pattern at[tp::kMaxPatterns];
+};
+PatternTable& patterns() {
+  static PatternTable t;
+  return t;
+}
+
+// the one place a format's time_format becomes a program: null for 0, 1 and ids nobody registered
+// (format_error then says so)
+const tp::Pattern* time_pattern_of(const sv::Format& f) { return time_pattern_find(f.time_format); }
+
 }  // namespace
 
 unsigned long long lines_hash_mask() { return hash_mask(); }
+
+int32_t time_pattern_register(const char* pattern, std::string& err) {
+  if (!pattern) { err = "the pattern is NULL"; return -1; }
+  tp::Pattern p;
+  if (!tp::compile(pattern, p, err)) return -1;
+  PatternTable& t = patterns();
+  std::lock_guard<std::mutex> lock(t.mu);
+  for (int32_t i = 0; i < t.n; ++i)
+    if (!std::strcmp(t.at[i].text, p.text)) return tp::kFirstId + i;
+  if (t.n == tp::kMaxPatterns) { err = "a process registers at most 240 time patterns"; return -1; }
+  t.at[t.n] = p;
+  return tp::kFirstId + t.n++;
+}
+
+const tp::Pattern* time_pattern_find(int32_t id) {
+  PatternTable& t = patterns();
+  std::lock_guard<std::mutex> lock(t.mu);
+  return id >= tp::kFirstId && id - tp::kFirstId < t.n ? &t.at[id - tp::kFirstId] : nullptr;
+}
 
 struct LineState {
   DevBuf<uint8_t> text, status, patch;
@@ -329,24 +374,26 @@ struct LineState {
 void Matcher::parse_lines(const LinesDesc& d) {
   if (ls_) ls_->parsed = false;
   if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
-  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  const tp::Pattern* pat = time_pattern_of(d.fmt);
+  if (const char* e = sv::format_error(d.fmt, pat ? &pat->prog : nullptr); *e) throw std::runtime_error(std::string("line format: ") + e);
   MessagesDesc md;
   md.n_chunks = d.n_chunks; md.data = d.data; md.len = d.len;
   std::memset(&md.fmt, 0, sizeof md.fmt);
   md.fmt.line = d.fmt;
   md.strict = 1;
-  parse_text(md);
+  parse_text(md, pat);
 }
 
 void Matcher::parse_messages(const MessagesDesc& d) {
   if (ls_) ls_->parsed = false;
   if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("message chunks are NULL");
-  if (const char* e = msg::format_error(d.fmt); *e) throw std::runtime_error(std::string("message format: ") + e);
-  parse_text(d);
+  const tp::Pattern* pat = time_pattern_of(d.fmt.line);
+  if (const char* e = msg::format_error(d.fmt, pat ? &pat->prog : nullptr); *e) throw std::runtime_error(std::string("message format: ") + e);
+  parse_text(d, pat);
 }
 
 // rule 11 (d.fmt.kind 0) and rule 14 over the chunks: the kept points in StageBufs, numbered per call
-void Matcher::parse_text(const MessagesDesc& d) {
+void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
   RM_HIP(hipSetDevice(eng_->device()));
   if (!ls_) ls_ = std::make_shared<LineState>();
   LineState& z = *ls_;
@@ -405,12 +452,18 @@ void Matcher::parse_text(const MessagesDesc& d) {
   need(z.id_off, L, st); need(z.id_len, L, st); need(z.hash, L, st); need(z.flag, L, st); need(z.pos, L, st);
   LineArrays la{z.status, z.lat, z.lon, z.acc, z.time, z.id_off, z.id_len, z.hash};
   const msg::Keys keys = msg::make_keys(d.fmt);
-  if (d.fmt.kind == 1)
-    hipLaunchKernelGGL(k_line_parse<1>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
-                       (uint32_t)L, d.fmt.line, keys, la, z.derr);
+  if (d.fmt.kind == 1 && pat)
+    hipLaunchKernelGGL((k_line_parse<1, true>), dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, keys, la, z.derr, pat->prog);
+  else if (d.fmt.kind == 1)
+    hipLaunchKernelGGL((k_line_parse<1, false>), dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, keys, la, z.derr, NoProgram{});
+  else if (pat)
+    hipLaunchKernelGGL((k_line_parse<0, true>), dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr, pat->prog);
   else
-    hipLaunchKernelGGL(k_line_parse<0>, dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
-                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr);
+    hipLaunchKernelGGL((k_line_parse<0, false>), dim3(nwin), dim3(64), 0, st, text, N, z.wfirst, z.wcnt,
+                       (uint32_t)L, d.fmt.line, NoKeys{}, la, z.derr, NoProgram{});
   RM_HIP(hipGetLastError());
   // ---- "is a point" flags and the counts of the rest
   const uint32_t sb = std::min<uint32_t>(1024u, grid(L));
@@ -453,7 +506,7 @@ void Matcher::parse_text(const MessagesDesc& d) {
         const uint8_t* b = (const uint8_t*)d.data[c] + (at - z.chunk_base[c]);
         const uint8_t* ce = (const uint8_t*)d.data[c] + d.len[c];
         const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(ce - b));
-        h.status = msg::generic_message(b, nl ? nl : ce, d.fmt, h.v, &h.why);
+        h.status = msg::generic_message(b, nl ? nl : ce, d.fmt, h.v, &h.why, pat);
         h.v.id_off += (uint32_t)at;
       }
     });
@@ -654,7 +707,8 @@ void Matcher::get_vehicles(uint32_t* chunk, uint64_t* off, uint32_t* len) {
 void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
                       uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len) {
   if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("line chunks are NULL");
-  if (const char* e = sv::format_error(d.fmt); *e) throw std::runtime_error(std::string("line format: ") + e);
+  const tp::Pattern* pat = time_pattern_of(d.fmt);
+  if (const char* e = sv::format_error(d.fmt, pat ? &pat->prog : nullptr); *e) throw std::runtime_error(std::string("line format: ") + e);
   std::fill(info, info + 7, 0);
   std::unordered_map<std::string_view, uint32_t> table;
   uint64_t P = 0;
@@ -669,7 +723,7 @@ void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, doub
       ++line;
       sv::Line v{};
       const char* why = nullptr;
-      const uint32_t st = sv::generic_line(b, le, d.fmt, v, &why);
+      const uint32_t st = sv::generic_line(b, le, d.fmt, v, &why, pat);
       if (st == sv::kBad) throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + why);
       ++info[0];
       info[1] += st == sv::kBlank;
@@ -702,7 +756,8 @@ void lines_parse_host(const LinesDesc& d, uint64_t info[7], uint32_t* uuid, doub
 void messages_parse_host(const MessagesDesc& d, uint64_t info[8], uint32_t* uuid, double* time, float* lon, float* lat, float* acc,
                          uint32_t* v_chunk, uint64_t* v_off, uint32_t* v_len, std::vector<DroppedMessage>* dropped) {
   if (d.n_chunks && (!d.data || !d.len)) throw std::runtime_error("message chunks are NULL");
-  if (const char* e = msg::format_error(d.fmt); *e) throw std::runtime_error(std::string("message format: ") + e);
+  const tp::Pattern* pat = time_pattern_of(d.fmt.line);
+  if (const char* e = msg::format_error(d.fmt, pat ? &pat->prog : nullptr); *e) throw std::runtime_error(std::string("message format: ") + e);
   std::fill(info, info + 8, 0);
   if (dropped) dropped->clear();
   std::unordered_map<std::string_view, uint32_t> table;
@@ -718,7 +773,7 @@ void messages_parse_host(const MessagesDesc& d, uint64_t info[8], uint32_t* uuid
       ++line;
       sv::Line v{};
       const char* why = nullptr;
-      const uint32_t st = msg::generic_message(b, le, d.fmt, v, &why);
+      const uint32_t st = msg::generic_message(b, le, d.fmt, v, &why, pat);
       if (st == sv::kBad && d.strict)
         throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + why);
       ++info[0];

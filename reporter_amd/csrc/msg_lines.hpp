@@ -2,7 +2,8 @@
 // message per line becomes a vehicle key and a point (reference KeyedFormattingProcessor.java,
 // Formatter.java:86-124).  A message format is a kind and rule 11's line format; kind 0 is rule 11
 // unchanged (sv::generic_line / sv::compact_line), kind 1 is one JSON object per line with five
-// named members.  Two readers of kind 1, shared by the device reader (lines.hip k_line_parse<1>),
+// named members; under a date pattern (rule 18) the time member is a string that tp::match reads.
+// Two readers of kind 1, shared by the device reader (lines.hip k_line_parse<1>),
 // the host reader and the host test (tests/cpp/msg_lines_test.cpp):
 //   * generic_json (host): the rule that defines every value.  The stripped line is one JSON value
 //     (json.hpp) that must be an object; of a repeated key the last wins; lat, lon and accuracy from
@@ -66,7 +67,7 @@ inline Keys make_keys(const Format& f) {
 }
 
 // The compact reader.  s: the line's first byte; reads no byte outside s[0, sv::kMaxLine).
-RM_HD uint32_t compact_json(const uint8_t* s, const sv::Format& f, const Keys& K, sv::Line& o) {
+RM_HD uint32_t compact_json(const uint8_t* s, const sv::Format& f, const Keys& K, sv::Line& o, const tp::Program* prog = nullptr) {
   // a byte past the reach reads as NUL, which no state accepts
   auto at = [&](uint32_t i) -> uint8_t { return i < sv::kMaxLine ? s[i] : (uint8_t)0; };
   if (at(0) == '\n' || (at(0) == '\r' && at(1) == '\n')) return sv::kBlank;
@@ -170,7 +171,10 @@ RM_HD uint32_t compact_json(const uint8_t* s, const sv::Format& f, const Keys& K
   if (sv::outside(f, la, lo)) return sv::kOutside;
   if (!(str & (1u << kId)) || ve[kId] == vb[kId]) return sv::kHost;
   double tm = 0.0;
-  if (f.time_format == 1) {
+  if (prog) {
+    const uint32_t nt = ve[kTime] - vb[kTime];
+    if (!(str & (1u << kTime)) || nt > tp::kMaxText || !tp::match(*prog, s + vb[kTime], nt, tm)) return sv::kHost;
+  } else if (f.time_format == 1) {
     if (!(str & (1u << kTime)) || ve[kTime] - vb[kTime] != 19u || !sv::civil_time(s + vb[kTime], tm)) return sv::kHost;
   } else {
     if (str & (1u << kTime)) return sv::kHost;
@@ -279,7 +283,8 @@ constexpr const char* kWhyTime1 = "malformed time (YYYY-MM-DD HH:MM:SS)";
 
 // One line [b, e) (no '\n' inside) by the generic rule: kBlank, kPoint, kOutside, or kBad with the
 // reason in *why.  o.id_off counts from b.
-inline uint32_t generic_json(const uint8_t* b, const uint8_t* e, const Format& mf, sv::Line& o, const char** why) {
+inline uint32_t generic_json(const uint8_t* b, const uint8_t* e, const Format& mf, sv::Line& o, const char** why,
+                             const tp::Pattern* pat = nullptr) {
   const sv::Format& f = mf.line;
   const uint8_t* const line0 = b;
   sv::strip(b, e);
@@ -337,7 +342,13 @@ inline uint32_t generic_json(const uint8_t* b, const uint8_t* e, const Format& m
   if ((size_t)(ie - ib) > sv::kMaxId) { *why = "vehicle id longer than 4096 bytes"; return sv::kBad; }
   const json::Value& tv = root.obj[(size_t)at[kTime]].second;
   double tm = 0.0;
-  if (f.time_format == 1) {
+  if (pat) {   // a number node is malformed under a pattern
+    if (tv.type != json::Value::String || tv.str.size() > 0xffff ||
+        !tp::match(pat->prog, (const uint8_t*)tv.str.data(), (uint32_t)tv.str.size(), tm)) {
+      *why = pat->why;
+      return sv::kBad;
+    }
+  } else if (f.time_format == 1) {
     if (tv.type != json::Value::String || tv.str.size() != 19 || !sv::civil_time((const uint8_t*)tv.str.data(), tm)) {
       *why = kWhyTime1;
       return sv::kBad;
@@ -381,15 +392,16 @@ inline uint32_t generic_json(const uint8_t* b, const uint8_t* e, const Format& m
 }
 
 // either kind by the generic rule
-inline uint32_t generic_message(const uint8_t* b, const uint8_t* e, const Format& mf, sv::Line& o, const char** why) {
-  return mf.kind == 1 ? generic_json(b, e, mf, o, why) : sv::generic_line(b, e, mf.line, o, why);
+inline uint32_t generic_message(const uint8_t* b, const uint8_t* e, const Format& mf, sv::Line& o, const char** why,
+                                const tp::Pattern* pat = nullptr) {
+  return mf.kind == 1 ? generic_json(b, e, mf, o, why, pat) : sv::generic_line(b, e, mf.line, o, why, pat);
 }
 
 // "" when the format can be read, else what is wrong with it
-inline const char* format_error(const Format& f) {
+inline const char* format_error(const Format& f, const tp::Program* prog = nullptr) {
   if (f.kind != 0 && f.kind != 1) return "kind must be 0 (separated values) or 1 (JSON)";
-  if (f.kind == 0) return sv::format_error(f.line);
-  if (f.line.time_format != 0 && f.line.time_format != 1) return "time_format must be 0 (epoch seconds) or 1 (YYYY-MM-DD HH:MM:SS)";
+  if (f.kind == 0) return sv::format_error(f.line, prog);
+  if (const char* e = sv::time_format_error(f.line, prog); *e) return e;
   if (f.line.accuracy_cap < 0) return "accuracy_cap must be >= 0";
   for (int k = 0; k < 5; ++k) {
     const size_t n = strnlen(f.key[k], kKeyBytes);

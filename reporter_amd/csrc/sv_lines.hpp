@@ -14,6 +14,9 @@
 //     (at most 15 digits, no exponent, no '+', digits on both sides of a '.'), an integer time of
 //     at most 15 digits.  Everything else is "host": the generic reader reads that line, so what
 //     a line yields or fails with never depends on the reader.
+// A time_format from 16 up names a registered date pattern (rule 18, time_pattern.hpp): the caller
+// resolves it and hands its program to the readers, which then give the stripped time column to
+// tp::match; the compact reader takes a time text of at most 64 bytes with no whitespace at its ends.
 // Order of the checks in both: enough fields, lat, lon, the bounding box (a point outside is
 // dropped whatever its other fields hold, as the reference's `continue` at :105-106), then the
 // id, the time and the accuracy.
@@ -25,6 +28,7 @@
 
 #include "json_points.hpp"
 #include "rm_common.hpp"
+#include "time_pattern.hpp"
 #include "trace_json.hpp"
 
 namespace rm {
@@ -97,10 +101,11 @@ RM_HD bool outside(const Format& f, double la, double lo) {
 }
 
 // The compact reader.  s: the line's first byte; reads no byte outside s[0, kMaxLine).
-RM_HD uint32_t compact_line(const uint8_t* s, const Format& f, Line& o) {
+RM_HD uint32_t compact_line(const uint8_t* s, const Format& f, Line& o, const tp::Program* prog = nullptr) {
   const bool t1 = f.time_format == 1;
+  const bool tw = t1 || prog;   // whitespace may stand inside the time column
   if (space(f.sep)) return kHost;
-  if (t1 && (f.time_col == f.uuid_col || f.time_col == f.lat_col || f.time_col == f.lon_col || f.time_col == f.acc_col))
+  if (tw && (f.time_col == f.uuid_col || f.time_col == f.lat_col || f.time_col == f.lon_col || f.time_col == f.acc_col))
     return kHost;
   uint32_t ub = 0, ue = 0, tb = 0, te = 0, lab = 0, lae = 0, lob = 0, loe = 0, ab = 0, ae = 0;
   uint32_t field = 0, start = 0, end = kMaxLine;
@@ -116,7 +121,7 @@ RM_HD uint32_t compact_line(const uint8_t* s, const Format& f, Line& o) {
     if (c == '\n') { end = i; break; }
     if (c == '\r' && i + 1 < kMaxLine && s[i + 1] == '\n') { end = i; break; }
     if (c == f.sep) { close(i); ++field; start = i + 1; continue; }
-    if (space(c) && !(t1 && (int32_t)field == f.time_col)) return kHost;
+    if (space(c) && !(tw && (int32_t)field == f.time_col)) return kHost;
   }
   if (end == kMaxLine) return kHost;   // no '\n' within reach
   if (end == 0) return kBlank;
@@ -135,7 +140,10 @@ RM_HD uint32_t compact_line(const uint8_t* s, const Format& f, Line& o) {
   if (outside(f, la, lo)) return kOutside;
   if (ue == ub) return kHost;
   double tm = 0.0;
-  if (t1) {
+  if (prog) {
+    const uint32_t nt = te - tb;
+    if (nt == 0u || nt > tp::kMaxText || space(s[tb]) || space(s[te - 1u]) || !tp::match(*prog, s + tb, nt, tm)) return kHost;
+  } else if (t1) {
     if (te - tb != 19u || !civil_time(s + tb, tm)) return kHost;
   } else {
     uint32_t i = tb;
@@ -212,7 +220,8 @@ inline bool generic_number(const uint8_t* b, const uint8_t* e, double& out) {
 
 // One line [b, e) (no '\n' inside) by the generic rule: kBlank, kPoint, kOutside, or kBad with
 // the reason in *why.  o.id_off counts from b.
-inline uint32_t generic_line(const uint8_t* b, const uint8_t* e, const Format& f, Line& o, const char** why) {
+inline uint32_t generic_line(const uint8_t* b, const uint8_t* e, const Format& f, Line& o, const char** why,
+                             const tp::Pattern* pat = nullptr) {
   const uint8_t* const line0 = b;
   strip(b, e);
   if (b == e) return kBlank;
@@ -240,7 +249,9 @@ inline uint32_t generic_line(const uint8_t* b, const uint8_t* e, const Format& f
   if (fb[0] == fe[0]) { *why = "empty vehicle id"; return kBad; }
   if ((size_t)(fe[0] - fb[0]) > kMaxId) { *why = "vehicle id longer than 4096 bytes"; return kBad; }
   double tm = 0.0;
-  if (f.time_format == 1) {
+  if (pat) {
+    if (fe[1] - fb[1] > 0xffff || !tp::match(pat->prog, fb[1], (uint32_t)(fe[1] - fb[1]), tm)) { *why = pat->why; return kBad; }
+  } else if (f.time_format == 1) {
     if (fe[1] - fb[1] != 19 || !civil_time(fb[1], tm)) { *why = "malformed time (YYYY-MM-DD HH:MM:SS)"; return kBad; }
   } else {
     const uint8_t* p = fb[1];
@@ -271,12 +282,19 @@ inline uint32_t generic_line(const uint8_t* b, const uint8_t* e, const Format& f
   return kPoint;
 }
 
-// "" when the format can be read, else what is wrong with it
-inline const char* format_error(const Format& f) {
+inline const char* time_format_error(const Format& f, const tp::Program* prog) {
+  if (f.time_format == 0 || f.time_format == 1 || (f.time_format >= tp::kFirstId && prog)) return "";
+  return "time_format must be 0 (epoch seconds), 1 (YYYY-MM-DD HH:MM:SS) or an id that rm_time_pattern gave";
+}
+
+// "" when the format can be read, else what is wrong with it (prog: the pattern that
+// f.time_format names, null when it names none)
+inline const char* format_error(const Format& f, const tp::Program* prog = nullptr) {
   if (f.sep == '\n') return "the separator cannot be a newline";
   if (f.uuid_col < 0 || f.time_col < 0 || f.lat_col < 0 || f.lon_col < 0) return "uuid, time, lat and lon columns must be >= 0";
   if (f.acc_col < -1) return "the accuracy column must be >= 0, or -1 for none";
-  if (f.time_format != 0 && f.time_format != 1) return "time_format must be 0 (epoch seconds) or 1 (YYYY-MM-DD HH:MM:SS)";
+  if (const char* e = time_format_error(f, prog); *e) return e;
+  if (prog && tp::has_literal(*prog, f.sep)) return "the time pattern's literals hold the separator";
   if (f.accuracy_cap < 0) return "accuracy_cap must be >= 0";
   return "";
 }

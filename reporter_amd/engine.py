@@ -152,12 +152,38 @@ LINES_INFO = ("lines", "blank", "outside", "points", "vehicles", "host_lines", "
 DATE_PATTERN = "yyyy-MM-dd HH:mm:ss"
 
 
+def time_pattern_id(pattern):
+    """Compile and register a date pattern (rm_time_pattern; DESIGN.md §3 rule 18): the id that
+    rm_line_format.time_format takes, the same for the same text.  ValueError with the compiler's
+    message for a pattern that is not read."""
+    text = pattern.encode() if isinstance(pattern, str) else bytes(pattern)
+    err = C.create_string_buffer(256)
+    pid = _lib.lib().rm_time_pattern(text, err, 256)
+    if pid < 0:
+        raise ValueError("time pattern %r: %s" % (text.decode("utf-8", "replace"), err.value.decode("utf-8", "replace")))
+    return int(pid)
+
+
+def parse_time(pattern, text):
+    """One time text under one date pattern, on the host (rm_time_pattern_parse): the instant in
+    whole seconds since 1970 UTC, or None for a text the pattern does not read."""
+    pid = time_pattern_id(pattern)
+    text = text.encode() if isinstance(text, str) else bytes(text)
+    out = C.c_double(0.0)
+    rc = _lib.lib().rm_time_pattern_parse(pid, text, len(text), C.byref(out))
+    if rc == 2:
+        raise _lib.RmError("time pattern id %d is not registered" % pid)
+    return None if rc else float(out.value)
+
+
 class LineFormat:
     """Layout of separated-value trace lines (rm_line_format).  The default is the trace files'
-    ``uuid,time,lat,lon,accuracy`` (reference py/simple_reporter.py:113)."""
+    ``uuid,time,lat,lon,accuracy`` (reference py/simple_reporter.py:113).  `time_pattern`: a date
+    pattern (DESIGN.md §3 rule 18) that reads the time column, in place of a time_format; it is
+    compiled here (ValueError with the compiler's message) and its id goes into the C struct."""
 
     def __init__(self, sep=b",", uuid_col=0, time_col=1, lat_col=2, lon_col=3, acc_col=4, time_format=0, accuracy_cap=0,
-                 bbox=None):
+                 bbox=None, time_pattern=None):
         sep = sep.encode() if isinstance(sep, str) else bytes(sep)
         if len(sep) != 1:
             raise ValueError("the separator must be one byte")
@@ -166,13 +192,20 @@ class LineFormat:
         self.sep, self.uuid_col, self.time_col, self.lat_col, self.lon_col = sep, int(uuid_col), int(time_col), int(lat_col), int(lon_col)
         self.acc_col, self.time_format, self.accuracy_cap = int(acc_col), int(time_format), int(accuracy_cap)
         self.bbox = None if bbox is None else tuple(float(x) for x in bbox)
+        self.time_pattern = None
+        if time_pattern is not None:
+            if self.time_format != 0:
+                raise ValueError("time_pattern stands in place of a time_format: give one of them")
+            self.time_pattern = time_pattern.decode() if isinstance(time_pattern, bytes) else str(time_pattern)
+            time_pattern_id(self.time_pattern)
 
     @classmethod
     def from_spec(cls, spec, **kw):
         """A formatter string of the reference (Formatter.java:36-51), e.g.
         ``,sv,\\|,1,9,10,0,5,yyyy-MM-dd HH:mm:ss``: the first character splits the rest into type,
         separator (one byte, optionally backslash-escaped), the uuid, lat, lon, time and accuracy
-        columns, and an optional date pattern (only yyyy-MM-dd HH:mm:ss)."""
+        columns, and an optional date pattern: yyyy-MM-dd HH:mm:ss is time_format 1, any other is
+        compiled (rule 18)."""
         if len(spec) < 2:
             raise ValueError("empty formatter spec")
         args = spec[1:].split(spec[0])
@@ -191,7 +224,7 @@ class LineFormat:
             raise ValueError("sv formatter columns must be integers")
         pattern = args[7] if len(args) > 7 else None
         if pattern not in (None, DATE_PATTERN):
-            raise ValueError("only the date pattern %r is read" % DATE_PATTERN)
+            return cls(sep, uuid, tm, lat, lon, acc, 0, time_pattern=pattern, **kw)
         return cls(sep, uuid, tm, lat, lon, acc, 1 if pattern else 0, **kw)
 
     def _c(self):
@@ -200,6 +233,8 @@ class LineFormat:
         f.sep = self.sep[0]
         f.uuid_col, f.time_col, f.lat_col, f.lon_col, f.acc_col = self.uuid_col, self.time_col, self.lat_col, self.lon_col, self.acc_col
         f.time_format, f.accuracy_cap = self.time_format, self.accuracy_cap
+        if self.time_pattern is not None:
+            f.time_format = time_pattern_id(self.time_pattern)
         f.use_bbox = 0 if self.bbox is None else 1
         for k in range(4):
             f.bbox[k] = 0.0 if self.bbox is None else self.bbox[k]
@@ -285,8 +320,9 @@ class MessageFormat:
     @classmethod
     def from_spec(cls, spec, **kw):
         """Either formatter string of the reference (Formatter.java:36-51): the separated-value form
-        LineFormat.from_spec reads, or ``@json@id@lat@lon@time@accuracy[@yyyy-MM-dd HH:mm:ss]`` (the
-        first character splits the rest into type, the five keys and an optional date pattern)."""
+        LineFormat.from_spec reads, or ``@json@id@lat@lon@time@accuracy[@yyyy-MM-dd'T'HH:mm:ssZZ]`` (the
+        first character splits the rest into type, the five keys and an optional date pattern, read
+        as LineFormat.from_spec reads it)."""
         if len(spec) < 2:
             raise ValueError("empty formatter spec")
         args = spec[1:].split(spec[0])
@@ -298,7 +334,7 @@ class MessageFormat:
             raise ValueError("json formatter needs the id, lat, lon, time and accuracy keys")
         pattern = args[6] if len(args) > 6 else None
         if pattern not in (None, DATE_PATTERN):
-            raise ValueError("only the date pattern %r is read" % DATE_PATTERN)
+            return cls(1, LineFormat(time_pattern=pattern, **kw), args[1:6])
         return cls(1, LineFormat(time_format=1 if pattern else 0, **kw), args[1:6])
 
     def _c(self):
@@ -349,11 +385,11 @@ def parse_messages_host(chunks, fmt=None, strict=False):
     ln = np.empty(nv, np.uint32)
     nd = C.c_uint32(0)
     dchunk = (C.c_uint32 * 64)()
-    dline = (C.c_uint64 * 64)()
-    reasons = C.create_string_buffer(64 * 64)
+    dline = (C.c_uint64 * 96)()
+    reasons = C.create_string_buffer(64 * 96)
     if L.rm_messages_parse_host(C.byref(d), info, uuid.ctypes.data, time.ctypes.data, lon.ctypes.data, lat.ctypes.data,
                                 acc.ctypes.data, chunk.ctypes.data, off.ctypes.data, ln.ctypes.data, C.byref(nd),
-                                C.addressof(dchunk), C.addressof(dline), C.addressof(reasons), 64 * 64, err, 512) != 0:
+                                C.addressof(dchunk), C.addressof(dline), C.addressof(reasons), 64 * 96, err, 512) != 0:
         raise _lib.RmError(err.value.decode("utf-8", "replace"))
     return dict(uuid=uuid, time=time, lon=lon, lat=lat, accuracy=acc, names=_names(chunks, chunk, off, ln),
                 info=dict(zip(MESSAGES_INFO, (int(x) for x in info))), dropped=_dropped(nd, dchunk, dline, reasons))
@@ -828,10 +864,10 @@ class VehicleSessions:
         """The first (at most 64) messages the last push_messages dropped: (chunk, line, reason)."""
         nd = C.c_uint32(0)
         dchunk = (C.c_uint32 * 64)()
-        dline = (C.c_uint64 * 64)()
-        reasons = C.create_string_buffer(64 * 64)
+        dline = (C.c_uint64 * 96)()
+        reasons = C.create_string_buffer(64 * 96)
         _lib.check(_lib.lib().rm_session_dropped_messages(self._h, C.byref(nd), C.addressof(dchunk), C.addressof(dline),
-                                                          C.addressof(reasons), 64 * 64))
+                                                          C.addressof(reasons), 64 * 96))
         return _dropped(nd, dchunk, dline, reasons)
 
     def messages_span(self):

@@ -269,7 +269,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("inputs", nargs="+", help="files (or directories of files) of raw messages, one per line")
     ap.add_argument("--formatter", required=True, help="the reference's formatter string, e.g. ',sv,\\|,1,9,10,0,5' or "
-                    "'@json@id@latitude@longitude@timestamp@accuracy'")
+                    "'@json@id@latitude@longitude@timestamp@accuracy'; a last argument is the date pattern of the "
+                    "time, e.g. '@json@id@lat@lon@time@acc@yyyy-MM-dd'T'HH:mm:ssZZ' (DESIGN.md rule 18)")
     ap.add_argument("--match-config", required=True)
     ap.add_argument("--output-location", required=True, help="a directory for the tile files")
     ap.add_argument("--mode", default="auto")

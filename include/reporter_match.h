@@ -82,6 +82,41 @@ int rm_match_points_batch(rm_matcher* m, const char* const* traces, size_t n, ch
  * released with rm_free. */
 int rm_match_edges(rm_matcher* m, const char* trace_json, char** out_json);
 int rm_match_edges_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs);
+/* The whole /report reply from one call (DESIGN.md section 3 rule 19; reference
+ * py/reporter_service.py:240-243: Match, json.loads, report(), json.dumps): the request rm_match
+ * takes in, the complete body out --
+ *   {"stats":{...}[,"shape_used":S],"segment_matcher":{"segments":[...],"mode":"auto"},
+ *    "datastore":{"mode":"auto","reports":[...]}}
+ * (keys and order: rm_report_replies below) -- with report() run on the device in the same run as
+ * the match, the trace's end time being its last point's in request order (:81).  threshold_sec is
+ * the service's THRESHOLD_SEC: one finite value per call.  match_options.report_levels and
+ * match_options.transition_levels (first match_options, first occurrence of either) must be arrays:
+ * a number entry that is an integer in -1..7 selects that level, other numbers select nothing, and a
+ * missing or non-array value fails the request with the service's own text ("match_options must
+ * include report_levels array" / "... transition_levels array"); a non-number entry fails it with
+ * "report_levels entries must be numbers" / "transition_levels entries must be numbers" (Python
+ * would merely never match it).  A request that fails as an rm_match request fails with that error
+ * first.  stats.*.length is the metres as kilometres with three decimals (0 when never assigned) and
+ * the times are the shortest decimals that parse back to the same double: round-trip equal to the
+ * interpreted reply, not byte equal.
+ * rm_report goes through the coalescer as rm_match does; a coalesced batch holds requests of one
+ * kind (and one threshold) only, so an rm_match reply is never made by a run with reporting on.
+ * rm_report_batch / _packed run their requests as one uncoalesced batch, the device JSON parse
+ * included, whatever n is (one request too: unlike rm_match_batch, whose single request takes the
+ * coalescer); any failing trace fails the call, naming the trace.  A run above
+ * RM_REPLY_DEVICE_MIN_POINTS points (default 65536, the matcher's small-run limit; read per call; 0:
+ * always) has its reply text written on the device; a smaller one downloads the records and formats
+ * them on the host.  The bytes are the same.  Replies are released with rm_free. */
+int rm_report(rm_matcher* m, const char* trace_json, double threshold_sec, char** out_json);
+int rm_report_batch(rm_matcher* m, const char* const* traces, size_t n, double threshold_sec, char** outs);
+int rm_report_batch_packed(rm_matcher* m, const char* const* traces, size_t n, double threshold_sec, char** buf,
+                           uint64_t* off);
+/* Diagnostic (the probe and the tests read it; a service needs none of it): the matcher's last
+ * rm_report_batch*: [0] reply bytes [1] flagged traces (rm_report_replies)
+ * [2] the writer used (1 host, 2 device) [3] the device writer's kernels and scans in microseconds;
+ * rm_matcher_timing gives its parse, stage, engine, download, format and total (the device writer's
+ * kernels count as format, its downloads as download) */
+int rm_report_info(const rm_matcher* m, uint64_t out[4]);
 void rm_free(char* p);
 /* Host wall times (ms) of the matcher's last uncoalesced rm_match_batch: out[0] JSON parse
  * (single pass, up to 16 host threads), [1] staging into pinned host arrays, [2] engine run
@@ -391,6 +426,26 @@ typedef struct {
   const uint32_t* transition_mask;
 } rm_report_desc;
 int rm_report_segments(const rm_report_desc* d, uint32_t* rep_off, void* reps, void* stats);
+/* The same report() and then the complete /report reply of every trace (DESIGN.md section 3 rule 19):
+ *   {"stats":{"successful_matches":{"count","length"},"unreported_matches":{"count","length"},
+ *    "match_errors":{"discontinuities","invalid_speeds","invalid_times"},"unassociated_segments"}
+ *    [,"shape_used"],"segment_matcher":{"segments":[...],"mode":"auto"},
+ *    "datastore":{"mode":"auto","reports":[{"id","t0","t1","length","queue_length"[,"next_id"]}...]}}
+ * with the segment objects of rm_match.  The n replies come in one malloc'd, NUL-terminated buffer
+ * (rm_free): reply i is (*buf)[off[i], off[i+1]) (off: n_traces + 1 entries).  writer 1: the records
+ * come down and the host formats them; 2: the text is written on the device from the records in HBM
+ * and only text and offsets come down; 0: by size (2 above RM_REPLY_DEVICE_MIN_POINTS segments,
+ * default 65536, read per call).  Both give the same bytes.  A trace holding a time that is
+ * negative (other than -1), below 1 (other than 0), 2^53 or more or not finite is flagged: either
+ * writer formats it on the host with std::to_chars.
+ * info (may be NULL): [0] reply bytes [1] flagged traces [2] the writer used [3] the device writer's
+ * kernels and scans in whole microseconds. */
+int rm_report_replies(const rm_report_desc* d, int writer, char** buf, uint64_t* off, uint64_t info[4]);
+/* The formatting alone, no GPU: trace k's segments are segs[seg_off[k] .. seg_off[k+1]) (56-byte
+ * rm::SegmentRec), its reports reps[rep_off[k] .. rep_off[k+1]) (48-byte rm::ReportRec), stats
+ * 40-byte rm::ReportStats per trace.  buf and off as above. */
+int rm_report_format_host(uint32_t n, const uint32_t* seg_off, const void* segs, const uint32_t* rep_off,
+                          const void* reps, const void* stats, char** buf, uint64_t* off);
 
 /* ---------------- batch-pipeline stages around the matcher (reference py/simple_reporter.py) ----------------
  * rm_runner_run_points replaces the per-vehicle grouping, time sort and inactivity

@@ -136,6 +136,10 @@ PROTOTYPES = [
     ("rm_match_edges", C.c_int, [P, C.c_char_p, C.POINTER(P)]),
     ("rm_match_edges_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.POINTER(P)]),
     ("rm_free", None, [P]),
+    ("rm_report", C.c_int, [P, C.c_char_p, C.c_double, C.POINTER(C.c_void_p)]),
+    ("rm_report_batch", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.c_double, C.POINTER(C.c_void_p)]),
+    ("rm_report_batch_packed", C.c_int, [P, C.POINTER(C.c_char_p), C.c_size_t, C.c_double, C.POINTER(C.c_void_p), P]),
+    ("rm_report_info", C.c_int, [P, P]),
     ("rm_matcher_timing", C.c_int, [P, P]),
     ("rm_coalesce_stats", C.c_int, [C.POINTER(C.c_uint64)]),
     ("rm_coalesce_timing", C.c_int, [C.POINTER(C.c_double)]),
@@ -195,6 +199,8 @@ PROTOTYPES = [
     ("rm_runner_set_locality", C.c_int, [P, C.c_int]),
     ("rm_runner_locality_used", C.c_int, [P, C.POINTER(C.c_int)]),
     ("rm_report_segments", C.c_int, [C.POINTER(RmReportDesc), P, P, P]),
+    ("rm_report_replies", C.c_int, [C.POINTER(RmReportDesc), C.c_int, C.POINTER(C.c_void_p), P, P]),
+    ("rm_report_format_host", C.c_int, [C.c_uint32, P, P, P, P, P, C.POINTER(C.c_void_p), P]),
     ("rm_runner_kernel_times", C.c_int, [P, P, P, C.c_int]),
     ("rm_runner_reset_times", C.c_int, [P]),
     ("rm_kernel_name", C.c_char_p, [C.c_int]),

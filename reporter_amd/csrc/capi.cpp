@@ -125,12 +125,34 @@ std::string read_file(const std::string& path) {
 struct ParsedTrace {
   tj::PointSink pts;
   MatchOptions opt;
+  // a Report request (DESIGN.md §3 rule 19): its threshold and level masks
+  bool report = false;
+  double threshold = 0.0;
+  uint32_t rmask = 0, tmask = 0;
+  // requests of one kind (and, for Report, one threshold) share a coalesced batch
+  bool same_kind(const ParsedTrace& o) const { return report == o.report && (!report || threshold == o.threshold); }
 };
 
 // one /report Match request (trace_json.hpp: single validating pass, the DOM reader's contract)
 ParsedTrace parse_trace(const char* text, const Config& conf) {
   ParsedTrace t;
   t.opt = tj::parse_request(text, conf.mode_defaults, t.pts);
+  return t;
+}
+
+void check_threshold(double threshold_sec) {
+  if (!std::isfinite(threshold_sec)) throw std::runtime_error("threshold_sec must be finite");
+}
+
+// one /report request whose whole reply the library writes (rm_report)
+ParsedTrace parse_report_trace(const char* text, const Config& conf, double threshold_sec) {
+  ParsedTrace t;
+  tj::ReportLevels lv;
+  t.opt = tj::parse_report_request(text, std::strlen(text), conf.mode_defaults, t.pts, lv);
+  t.report = true;
+  t.threshold = threshold_sec;
+  t.rmask = lv.report_mask;
+  t.tmask = lv.transition_mask;
   return t;
 }
 
@@ -148,8 +170,14 @@ struct MatchRequest {
   // a dispatched request's segments: its caller formats the reply itself after the batch (the
   // dispatcher moves on to the next batch instead of formatting tens of replies)
   std::vector<SegmentRec> segs;
+  std::vector<ReportRec> reps;   // (a Report request: its reports and stats too)
+  ReportStats stats{};
   bool raw = false;
   bool done = false;
+  void format() {
+    if (trace->report) reply_format_one(segs.data(), (uint32_t)segs.size(), reps.data(), (uint32_t)reps.size(), stats, out);
+    else tj::format_segments(segs.data(), (uint32_t)segs.size(), out);
+  }
   // its caller waits here alone, on the request's own mutex: a batch's callers wake without
   // queueing on the coalescer's lock (at 256 clients that convoy cost ~0.1 ms of CPU per request)
   std::mutex mu;
@@ -218,7 +246,7 @@ class Coalescer {
       r.cv.wait(lk, [&] { return r.done; });
     }
     if (!r.err.empty()) throw std::runtime_error(r.err);
-    if (r.raw) tj::format_segments(r.segs.data(), (uint32_t)r.segs.size(), r.out);
+    if (r.raw) r.format();
     return std::move(r.out);
   }
   void stats(uint64_t out[4]) {
@@ -319,8 +347,13 @@ void parallel_for(size_t n, F&& fn, size_t per = 32) {
 // [3] reply formatting
 // raw (optional): each trace's segments instead of its formatted reply (the coalescer's callers
 // format their own)
+struct RawRecords {   // per trace: its segments and, for a Report batch, its reports and stats
+  std::vector<std::vector<SegmentRec>> segs;
+  std::vector<std::vector<ReportRec>> reps;
+  std::vector<ReportStats> stats;
+};
 std::vector<std::string> match_parsed(Matcher& m, const std::vector<ParsedTrace*>& pt, std::vector<std::string>* errs,
-                                      double* tm = nullptr, std::vector<std::vector<SegmentRec>>* raw = nullptr) {
+                                      double* tm = nullptr, RawRecords* raw = nullptr) {
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
   clk::time_point t0 = clk::now();
@@ -359,18 +392,32 @@ std::vector<std::string> match_parsed(Matcher& m, const std::vector<ParsedTrace*
   hb.n_traces = (uint32_t)n; hb.trace_off = off.data(); hb.lon = lon; hb.lat = lat;
   hb.time = time; hb.accuracy = acc; hb.n_opts = (uint32_t)n; hb.opts = opts.data();
   hb.trace_opt = topt.data();
+  const bool report = n && pt[0]->report;   // (a batch is of one kind: Coalescer::loop)
+  std::vector<uint32_t> rmask, tmask;
   RunParams rp;
   rp.do_report = 0;
   rp.prefetch_segments = 1;   // the replies are the segments: a small run readies them itself
+  if (report) {
+    rmask.resize(n); tmask.resize(n);
+    for (size_t i = 0; i < n; ++i) { rmask[i] = pt[i]->rmask; tmask[i] = pt[i]->tmask; }
+    rp.do_report = 1;
+    rp.threshold_sec = pt[0]->threshold;
+    rp.trace_report_mask = rmask.data();
+    rp.trace_transition_mask = tmask.data();
+    rp.prefetch_reports = 1;   // ... and the reports and stats
+  }
   m.set_isolation(true);
   if (tm) { tm[0] += ms_since(t0); t0 = clk::now(); }
   m.run(hb, rp);
   if (tm) { tm[1] += ms_since(t0); t0 = clk::now(); }
   std::vector<uint32_t> terr(n, 0u);
   if (m.error_bits()) m.get_trace_errors(terr.data());
-  std::vector<uint32_t> soff;
+  std::vector<uint32_t> soff, rbase, rcnt;
   std::vector<SegmentRec> segs;
-  m.get_segments(soff, segs);
+  std::vector<ReportRec> reps;
+  std::vector<ReportStats> stats;
+  if (report) m.get_report_records(soff, segs, rbase, rcnt, reps, stats);
+  else m.get_segments(soff, segs);
   if (tm) { tm[2] += ms_since(t0); t0 = clk::now(); }
   std::vector<std::string> out(n);
   if (errs) errs->assign(n, std::string());
@@ -380,15 +427,21 @@ std::vector<std::string> match_parsed(Matcher& m, const std::vector<ParsedTrace*
     (*errs)[i] = error_text(terr[i]);
   }
   if (raw) {
-    raw->resize(n);
-    for (size_t i = 0; i < n; ++i)
-      if (!terr[i]) (*raw)[i].assign(segs.data() + soff[i], segs.data() + soff[i + 1]);
+    raw->segs.resize(n);
+    if (report) { raw->reps.resize(n); raw->stats = stats; }
+    for (size_t i = 0; i < n; ++i) {
+      if (terr[i]) continue;
+      raw->segs[i].assign(segs.data() + soff[i], segs.data() + soff[i + 1]);
+      if (report) raw->reps[i].assign(reps.data() + rbase[i], reps.data() + rbase[i] + rcnt[i]);
+    }
     if (tm) tm[3] += ms_since(t0);
     return out;
   }
   // replies of a coalesced batch (tens of requests, ~10 us each) over the pool in chunks of 4
   parallel_for(n, [&](size_t i) {
-    if (!terr[i]) tj::format_segments(segs.data() + soff[i], soff[i + 1] - soff[i], out[i]);
+    if (terr[i]) return;
+    if (report) reply_format_one(segs.data() + soff[i], soff[i + 1] - soff[i], reps.data() + rbase[i], rcnt[i], stats[i], out[i]);
+    else tj::format_segments(segs.data() + soff[i], soff[i + 1] - soff[i], out[i]);
   }, 4);
   if (tm) tm[3] += ms_since(t0);
   return out;
@@ -407,13 +460,14 @@ void serve_batch(std::unique_ptr<Matcher>& m, Engine* eng, const std::vector<Mat
       std::vector<ParsedTrace*> pt(n);
       for (size_t i = 0; i < n; ++i) pt[i] = reqs[i]->trace;
       std::vector<std::string> errs;
-      std::vector<std::vector<SegmentRec>> raw;
+      RawRecords raw;
       std::vector<std::string> outs = match_parsed(*m, pt, &errs, tm, defer_format ? &raw : nullptr);
       for (size_t i = 0; i < n; ++i) {
         if (!errs[i].empty()) {
           reqs[i]->err = errs[i];
         } else if (defer_format) {
-          reqs[i]->segs = std::move(raw[i]);
+          reqs[i]->segs = std::move(raw.segs[i]);
+          if (pt[i]->report) { reqs[i]->reps = std::move(raw.reps[i]); reqs[i]->stats = raw.stats[i]; }
           reqs[i]->raw = true;
         } else {
           reqs[i]->out = std::move(outs[i]);
@@ -441,12 +495,18 @@ void Coalescer::loop() {
         const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds((int64_t)(window_ms_ * 1000));
         while (!stop_ && q_.size() < max_ && cv_req_.wait_until(lk, until) != std::cv_status::timeout) {}
       }
-      while (!q_.empty() && batch.size() < max_) { batch.push_back(q_.front()); q_.pop_front(); }
+      // a batch holds requests of one kind: the first of another kind waits for the next batch (a
+      // Match reply is never made by a run with reporting on)
+      while (!q_.empty() && batch.size() < max_ && (batch.empty() || q_.front()->trace->same_kind(*batch[0]->trace))) {
+        batch.push_back(q_.front());
+        q_.pop_front();
+      }
       batches_++;
       requests_ += batch.size();
       max_seen_ = std::max<uint64_t>(max_seen_, batch.size());
       lone_ = batch.size() == 1 ? lone_ + 1 : 0;
       ++busy_;
+      if (!q_.empty()) cv_req_.notify_one();   // (the other kind's requests: another dispatcher may take them now)
     }
     double tm[4] = {0, 0, 0, 0};
     serve_batch(m, eng_.get(), batch, tm, fmt_callers());   // out / err (or segs) of each request, not under the lock
@@ -496,7 +556,9 @@ struct rm_matcher {
   HostStaging stage;
   std::vector<tj::PointSink> sinks;   // per parse thread, grow-only (no page faults on a warm matcher)
   std::vector<PinnedBytes> arenas;    // per parse thread: trace-array bytes for the device parser
-  double ms[6] = {};   // the last rm_match_batch: parse, stage, engine, download, format, total
+  ReplyWriter reply;                  // rm_report_batch*: the device writer's buffers (grow-only)
+  double ms[6] = {};   // the last rm_match_batch / rm_report_batch: parse, stage, engine, download, format, total
+  uint64_t reply_info[4] = {};   // the last rm_report_batch: reply bytes, flagged traces, writer (1 host, 2 device), device us
 };
 
 namespace {
@@ -517,6 +579,81 @@ struct PointsIn {
   const float* lat;
   const uint32_t* off;
 };
+
+// what makes a batch call a Report call (rm_report_batch*): the call's threshold and, filled by the
+// structure read, every request's level masks
+struct ReportCall {
+  double threshold = 15.0;
+  std::vector<uint32_t> rmask, tmask;
+  void params(RunParams& rp) const {
+    rp.do_report = 1;
+    rp.threshold_sec = threshold;
+    rp.trace_report_mask = rmask.data();
+    rp.trace_transition_mask = tmask.data();
+  }
+};
+
+// one request of a batch call, as Match or as Report reads it (span: left to the device parser)
+MatchOptions parse_batch_request(const char* text, size_t len, const Config& conf, tj::PointSink& sk, tj::TraceSpan* span,
+                                 ReportCall* rc, size_t i) {
+  if (!rc) return span ? tj::parse_request_deferred(text, len, conf.mode_defaults, sk, *span) : tj::parse_request(text, len, conf.mode_defaults, sk);
+  tj::ReportLevels lv;
+  const MatchOptions o = tj::parse_report_request(text, len, conf.mode_defaults, sk, lv, span);
+  rc->rmask[i] = lv.report_mask;
+  rc->tmask[i] = lv.transition_mask;
+  return o;
+}
+
+// The reply side of rm_report_batch*: per-trace failures fail the call naming the trace; a run
+// above the small-run limit (RM_REPLY_DEVICE_MIN_POINTS) has its replies written on the device and
+// downloads text and offsets straight into the packed buffer, a smaller one downloads the records
+// and the host writer formats them.  Both give the same bytes.
+void finish_report_batch(rm_matcher* m, Matcher& mt, size_t n, uint64_t points, char** outs, const PackedOut* pk) {
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+  std::vector<uint32_t> terr(n, 0u);
+  if (mt.error_bits()) mt.get_trace_errors(terr.data());
+  for (size_t i = 0; i < n; ++i)
+    if (terr[i]) throw std::runtime_error("trace " + std::to_string(i) + ": " + error_text(terr[i]));
+  std::vector<uint64_t> own_off;
+  uint64_t* off = pk ? pk->off : (own_off.resize(n + 1), own_off.data());
+  char* buf = nullptr;
+  uint64_t flagged = 0;
+  const auto t3 = clk::now();
+  if (points > reply_device_min_points()) {
+    double dev_ms = 0.0;
+    m->reply.write(mt.device(), mt.stream(), mt.reply_source(), &buf, off, &flagged, &dev_ms);
+    m->ms[4] = dev_ms;                                   // the writer's kernels and scans
+    m->ms[3] = std::max(0.0, ms_since(t3) - dev_ms);     // the downloads (and the host's share)
+    m->reply_info[2] = 2; m->reply_info[3] = (uint64_t)(dev_ms * 1000.0 + 0.5);
+  } else {
+    std::vector<uint32_t> soff, rbase, rcnt;
+    std::vector<SegmentRec> segs;
+    std::vector<ReportRec> reps;
+    std::vector<ReportStats> stats;
+    mt.get_report_records(soff, segs, rbase, rcnt, reps, stats);
+    m->ms[3] = ms_since(t3);
+    const auto t4 = clk::now();
+    reply_format_host((uint32_t)n, soff.data(), segs.data(), rbase.data(), rcnt.data(), reps.data(), stats.data(), &buf, off, &flagged);
+    m->ms[4] = ms_since(t4);
+    m->reply_info[2] = 1; m->reply_info[3] = 0;
+  }
+  m->reply_info[0] = off[n]; m->reply_info[1] = flagged;
+  if (pk) { *pk->buf = buf; return; }
+  try {
+    for (size_t i = 0; i < n; ++i) {
+      const size_t k = (size_t)(off[i + 1] - off[i]);
+      outs[i] = static_cast<char*>(std::malloc(k + 1));
+      if (!outs[i]) throw std::bad_alloc();
+      std::memcpy(outs[i], buf + off[i], k);
+      outs[i][k] = 0;
+    }
+  } catch (...) {
+    std::free(buf);
+    throw;
+  }
+  std::free(buf);
+}
 
 void finish_json_batch(rm_matcher* m, Matcher& mt, size_t n, size_t nt, char** outs, const PackedOut* pk = nullptr,
                        const PointsIn* pin = nullptr, bool with_edges = false) {
@@ -609,7 +746,8 @@ uint64_t json_device_min_bytes() {
   return (uint64_t)(std::max(0.0, mb) * 1048576.0);
 }
 
-bool match_json_batch_device(rm_matcher* m, const char* const* traces, size_t n, char** outs, const PackedOut* pk) {
+bool match_json_batch_device(rm_matcher* m, const char* const* traces, size_t n, char** outs, const PackedOut* pk,
+                             ReportCall* rc = nullptr) {
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   const auto t0 = clk::now();
@@ -653,11 +791,11 @@ bool match_json_batch_device(rm_matcher* m, const char* const* traces, size_t n,
       tj::TraceSpan sp;
       const size_t before = sk.size();
       try {
-        opts[i] = tj::parse_request_deferred(traces[i], len[i], conf.mode_defaults, sk, sp);
+        opts[i] = parse_batch_request(traces[i], len[i], conf, sk, &sp, rc, i);
       } catch (const std::exception&) {
         try {
           sp = tj::TraceSpan();
-          opts[i] = tj::parse_request(traces[i], len[i], conf.mode_defaults, sk);
+          opts[i] = parse_batch_request(traces[i], len[i], conf, sk, nullptr, rc, i);
         } catch (const std::exception&) {
           failed[t] = 1;   // the host path reports it (as the first failing request)
           break;
@@ -712,7 +850,7 @@ bool match_json_batch_device(rm_matcher* m, const char* const* traces, size_t n,
     // not the compact layout after all: the host reader's points, if they fit the trace's slots
     tj::PointSink& fix = fixes.emplace_back();
     try {
-      opts[i] = tj::parse_request(traces[i], len[i], conf.mode_defaults, fix);
+      opts[i] = parse_batch_request(traces[i], len[i], conf, fix, nullptr, rc, i);
     } catch (const std::exception&) {
       mt.sync();   // the uploads queued so far read host memory this function owns
       return false;
@@ -724,10 +862,12 @@ bool match_json_batch_device(rm_matcher* m, const char* const* traces, size_t n,
   const auto t2 = clk::now();
   RunParams rp;
   rp.do_report = 0;
+  if (rc) rc->params(rp);
   mt.set_isolation(true);
   mt.run_parsed(off.data(), (uint32_t)n, opts.data(), (uint32_t)n, topt.data(), tsp.data(), rp);
   m->ms[2] = ms_since(t2);
-  finish_json_batch(m, mt, n, nt, outs, pk);
+  if (rc) finish_report_batch(m, mt, n, P, outs, pk);
+  else finish_json_batch(m, mt, n, nt, outs, pk);
   m->ms[5] = ms_since(t0);
   return true;
 }
@@ -747,9 +887,12 @@ bool json_device_enabled() {
 // points: the replies also carry matched_points (rm_match_points*); the requests are then parsed
 // on the host, whose staging keeps the input points an unmatched entry reports.
 // edges: the replies also carry edges and shape (rm_match_edges*); parsed on the host likewise.
+// rc: a Report call (rm_report_batch*): the level arrays are read with the structure, report() runs
+// with the match and the replies are the complete /report bodies (finish_report_batch).
 void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char** outs,
-                      const PackedOut* pk = nullptr, bool points = false, bool edges = false) {
-  if (n && !points && !edges && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk)) return;
+                      const PackedOut* pk = nullptr, bool points = false, bool edges = false, ReportCall* rc = nullptr) {
+  if (rc) { rc->rmask.assign(n, 0u); rc->tmask.assign(n, 0u); }
+  if (n && !points && !edges && json_device_enabled() && match_json_batch_device(m, traces, n, outs, pk, rc)) return;
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
   const auto t0 = clk::now();
@@ -771,7 +914,7 @@ void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char**
     sk.lon.reserve(guess); sk.lat.reserve(guess); sk.acc.reserve(guess); sk.time.reserve(guess);
     for (size_t i = a; i < b; ++i) {
       const size_t before = sk.size();
-      opts[i] = tj::parse_request(traces[i], len[i], conf.mode_defaults, sk);
+      opts[i] = parse_batch_request(traces[i], len[i], conf, sk, nullptr, rc, i);
       cnt[i] = (uint32_t)(sk.size() - before);
       topt[i] = (uint32_t)i;
     }
@@ -806,11 +949,13 @@ void match_json_batch(rm_matcher* m, const char* const* traces, size_t n, char**
   RunParams rp;
   rp.do_report = 0;
   rp.prefetch_segments = 1;
+  if (rc) { rc->params(rp); rp.prefetch_reports = 1; }
   mt.set_isolation(true);
   mt.run(hb, rp);
   m->ms[2] = ms_since(t2);
   const PointsIn pin{hs.lon, hs.lat, off.data()};
-  finish_json_batch(m, mt, n, nt, outs, pk, points ? &pin : nullptr, edges);
+  if (rc) finish_report_batch(m, mt, n, P, outs, pk);
+  else finish_json_batch(m, mt, n, nt, outs, pk, points ? &pin : nullptr, edges);
   m->ms[5] = ms_since(t0);
 }
 
@@ -1042,6 +1187,72 @@ int rm_match_edges(rm_matcher* m, const char* trace_json, char** out_json) {
   if (!out_json) return fail("out_json is NULL");
   *out_json = nullptr;
   return rm_match_edges_batch(m, &trace_json, 1, out_json);
+}
+
+int rm_report_batch(rm_matcher* m, const char* const* traces, size_t n, double threshold_sec, char** outs) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("matcher is NULL");
+    for (size_t i = 0; i < n; ++i) outs[i] = nullptr;
+    check_threshold(threshold_sec);
+    if (n == 0) return;
+    for (size_t i = 0; i < n; ++i)
+      if (!traces[i]) throw std::runtime_error("trace string is NULL");
+    ReportCall rc;
+    rc.threshold = threshold_sec;
+    try {
+      match_json_batch(m, traces, n, outs, nullptr, false, false, &rc);   // any failing trace fails the call, naming the trace
+    } catch (...) {
+      for (size_t i = 0; i < n; ++i) { std::free(outs[i]); outs[i] = nullptr; }
+      throw;
+    }
+  });
+}
+
+int rm_report_batch_packed(rm_matcher* m, const char* const* traces, size_t n, double threshold_sec, char** buf,
+                           uint64_t* off) {
+  return guarded([&] {
+    if (!m) throw std::runtime_error("matcher is NULL");
+    if (!buf || !off) throw std::runtime_error("buf / off is NULL");
+    *buf = nullptr;
+    off[0] = 0;
+    check_threshold(threshold_sec);
+    for (size_t i = 0; i < n; ++i)
+      if (!traces[i]) throw std::runtime_error("trace string is NULL");
+    if (n == 0) {
+      *buf = static_cast<char*>(std::calloc(1, 1));
+      return;
+    }
+    ReportCall rc;
+    rc.threshold = threshold_sec;
+    const PackedOut pk{buf, off};
+    match_json_batch(m, traces, n, nullptr, &pk, false, false, &rc);
+  });
+}
+
+int rm_report(rm_matcher* m, const char* trace_json, double threshold_sec, char** out_json) {
+  if (!out_json) return fail("out_json is NULL");
+  *out_json = nullptr;
+  return guarded([&] {
+    if (!m) throw std::runtime_error("matcher is NULL");
+    if (!trace_json) throw std::runtime_error("trace string is NULL");
+    check_threshold(threshold_sec);
+    if (!m->conf->coalescer) {
+      ReportCall rc;
+      rc.threshold = threshold_sec;
+      match_json_batch(m, &trace_json, 1, out_json, nullptr, false, false, &rc);
+      return;
+    }
+    ParsedTrace pt = parse_report_trace(trace_json, *m->conf, threshold_sec);
+    const std::string js = m->conf->coalescer->submit(&pt, &m->m);
+    *out_json = dup_string(js);
+  });
+}
+
+int rm_report_info(const rm_matcher* m, uint64_t out[4]) {
+  return guarded([&] {
+    if (!m || !out) throw std::runtime_error("matcher or out is NULL");
+    for (int i = 0; i < 4; ++i) out[i] = m->reply_info[i];
+  });
 }
 
 int rm_match(rm_matcher* m, const char* trace_json, char** out_json) {
@@ -1473,6 +1684,56 @@ int rm_report_segments(const rm_report_desc* d, uint32_t* rep_off, void* reps, v
       throw std::runtime_error("report descriptor or output is NULL");
     report_segments(g_device, d->n_traces, d->seg_off, (const SegmentRec*)d->segs, d->trace_end_time, d->threshold_sec,
                     d->report_mask, d->transition_mask, rep_off, (ReportRec*)reps, (ReportStats*)stats);
+  });
+}
+int rm_report_replies(const rm_report_desc* d, int writer, char** buf, uint64_t* off, uint64_t info[4]) {
+  return guarded([&] {
+    if (!d || !buf || !off || (d->n_traces && (!d->seg_off || !d->trace_end_time || !d->threshold_sec || !d->report_mask ||
+                                               !d->transition_mask)))
+      throw std::runtime_error("report descriptor or output is NULL");
+    if (writer < 0 || writer > 2) throw std::runtime_error("reply writer must be 0, 1 or 2");
+    const uint32_t T = d->n_traces;
+    const uint64_t S = T ? d->seg_off[T] : 0;
+    // by size: the segments stand in for the points a matcher run is judged by
+    const int used = writer ? writer : (S > reply_device_min_points() ? 2 : 1);
+    uint64_t flagged = 0;
+    double ms = 0.0;
+    const SegmentRec* segs = (const SegmentRec*)d->segs;
+    if (used == 2) {
+      DeviceReports dr;
+      if (T) report_segments_device(g_device, T, d->seg_off, segs, d->trace_end_time, d->threshold_sec, d->report_mask,
+                                    d->transition_mask, dr);
+      ReplySource src;
+      src.T = T; src.seg_base = dr.seg_off; src.seg_cnt = dr.seg_cnt; src.rep_base = dr.seg_off;
+      src.segs = dr.segs; src.reps = dr.reps; src.stats = dr.stats; src.cap = S;
+      ReplyWriter w;
+      w.write(g_device, nullptr, src, buf, off, &flagged, &ms);
+    } else {
+      std::vector<uint32_t> rep_off(T + 1, 0u);
+      std::vector<ReportRec> reps(std::max<uint64_t>(S, 1));
+      std::vector<ReportStats> stats(std::max<uint32_t>(T, 1));
+      report_segments(g_device, T, d->seg_off, segs, d->trace_end_time, d->threshold_sec, d->report_mask, d->transition_mask,
+                      rep_off.data(), reps.data(), stats.data());
+      std::vector<uint32_t> rep_cnt(T);
+      for (uint32_t k = 0; k < T; ++k) rep_cnt[k] = rep_off[k + 1] - rep_off[k];
+      const uint32_t zero[1] = {0u};
+      reply_format_host(T, T ? d->seg_off : zero, segs, rep_off.data(), rep_cnt.data(), reps.data(), stats.data(), buf, off, &flagged);
+    }
+    if (info) { info[0] = off[T]; info[1] = flagged; info[2] = (uint64_t)used; info[3] = (uint64_t)(ms * 1000.0 + 0.5); }
+  });
+}
+int rm_report_format_host(uint32_t n, const uint32_t* seg_off, const void* segs, const uint32_t* rep_off, const void* reps,
+                          const void* stats, char** buf, uint64_t* off) {
+  return guarded([&] {
+    if (!buf || !off || (n && (!seg_off || !rep_off || !stats))) throw std::runtime_error("reply records or output is NULL");
+    const uint32_t zero[1] = {0u};
+    std::vector<uint32_t> rep_cnt(n);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (rep_off[k + 1] < rep_off[k]) throw std::runtime_error("report offsets not monotone");
+      rep_cnt[k] = rep_off[k + 1] - rep_off[k];
+    }
+    reply_format_host(n, n ? seg_off : zero, (const SegmentRec*)segs, n ? rep_off : zero, rep_cnt.data(), (const ReportRec*)reps,
+                      (const ReportStats*)stats, buf, off, nullptr);
   });
 }
 int rm_runner_kernel_times(rm_runner* r, double* ms, uint64_t* launches, int n) {

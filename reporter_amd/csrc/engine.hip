@@ -1276,6 +1276,20 @@ __global__ void __launch_bounds__(1024) k_seg_offsets_small(DevBatch b, uint32_t
   if (threadIdx.x == 1023) off[T] = (uint32_t)ea;
 }
 
+// a small Report run's reports beside its compacted segments: trace k's rep_cnt[k] reports (at
+// most its segments) to dst[off[k] ..), off the segments' offsets; nothing when the run is gated off
+__global__ void __launch_bounds__(64) k_gather_reports_small(DevBatch b, const uint32_t* off, unsigned long long* dst) {
+  if (small_abort(b)) return;
+  constexpr uint32_t kWords = sizeof(ReportRec) / 8;
+  for (uint32_t k = blockIdx.x; k < b.T; k += gridDim.x) {
+    const uint32_t base = b.seg_base[k], c = min(b.rep_cnt[k], b.seg_cnt[k]);
+    if ((uint64_t)base + c > b.seg_cap || (uint64_t)off[k] + c > b.seg_cap) continue;
+    const unsigned long long* s = (const unsigned long long*)(b.reps + base);
+    unsigned long long* d = dst + (uint64_t)off[k] * kWords;
+    for (uint32_t q = threadIdx.x; q < c * kWords; q += 64) d[q] = s[q];
+  }
+}
+
 // descriptor field access (see Workspace::cand_desc)
 __device__ __forceinline__ uint32_t d_spf(const uint4& d0) { return d0.w & 0xffffu; }
 __device__ __forceinline__ uint32_t d_spr(const uint4& d0) { return d0.w >> 16; }
@@ -3825,7 +3839,19 @@ __device__ __forceinline__ K4Slot k4_slot(const DevBatch& b, uint32_t l) {
   return s;
 }
 
-__global__ void __launch_bounds__(64) k_seg_wave(DevGraph g, DevBatch b, const uint32_t* rec_slot, uint32_t total_arg, ReportArgs ra) {
+// A Report run's arguments: the level masks per trace (DESIGN.md §3 rule 19).  k_seg_wave is
+// compiled once for either struct, so a run without them executes the code it always did.
+struct ReportArgsPerTrace : ReportArgs {
+  const uint32_t* trace_rmask;
+  const uint32_t* trace_tmask;
+};
+__device__ __forceinline__ uint2 report_masks(const ReportArgs& ra, uint32_t) { return make_uint2(ra.rmask, ra.tmask); }
+__device__ __forceinline__ uint2 report_masks(const ReportArgsPerTrace& ra, uint32_t k) {
+  return make_uint2(ra.trace_rmask[k], ra.trace_tmask[k]);
+}
+
+template <class RA>
+__global__ void __launch_bounds__(64) k_seg_wave(DevGraph g, DevBatch b, const uint32_t* rec_slot, uint32_t total_arg, RA ra) {
   const uint32_t k = blockIdx.x;
   if (k >= b.T || small_abort(b)) return;
   const uint32_t total = total_arg != kNone ? total_arg : (uint32_t)b.tot[2];   // kNone: a small run's
@@ -4008,8 +4034,9 @@ __global__ void __launch_bounds__(64) k_seg_wave(DevGraph g, DevBatch b, const u
   }
   if (ra.on) {
     __threadfence_block();   // this wave's segment stores are visible to its loads
-    const ReportStats st = report_wave(b.segs + Rb, runs, o1 > o, o1 > o ? b.time[o1 - 1] : 0.0, ra.threshold, ra.rmask,
-                                       ra.tmask, b.reps + Rb, ra.hist, ra.dur);
+    const uint2 masks = report_masks(ra, k);
+    const ReportStats st = report_wave(b.segs + Rb, runs, o1 > o, o1 > o ? b.time[o1 - 1] : 0.0, ra.threshold, masks.x,
+                                       masks.y, b.reps + Rb, ra.hist, ra.dur);
     if (lane == 0) {
       b.rep_cnt[k] = (uint32_t)st.n_reports;
       b.stats[k] = st;
@@ -5728,7 +5755,16 @@ void Matcher::Stages::k4(const RunParams& rp, const DevBatch& v, uint32_t total)
   if (rp.do_report && rp.zero_hist) m.zero_hist(rp);
   if (total != kNone)
     hipLaunchKernelGGL(k_rec_slot, dim3((uint32_t)((v.P + 255) / 256)), dim3(256), 0, st, v, m.ws_.rec_slot);
-  hipLaunchKernelGGL(k_seg_wave, dim3(v.T), dim3(64), 0, st, g, v, (const uint32_t*)m.ws_.rec_slot, total, report_args(rp));
+  if (m.levels_on_) {   // (the run's per-trace masks in HBM: report masks, then transition masks)
+    ReportArgsPerTrace a;
+    static_cast<ReportArgs&>(a) = report_args(rp);
+    a.trace_rmask = m.levels_dev_.get();
+    a.trace_tmask = m.levels_dev_.get() + v.T;
+    hipLaunchKernelGGL(k_seg_wave<ReportArgsPerTrace>, dim3(v.T), dim3(64), 0, st, g, v, (const uint32_t*)m.ws_.rec_slot, total, a);
+  } else {
+    hipLaunchKernelGGL(k_seg_wave<ReportArgs>, dim3(v.T), dim3(64), 0, st, g, v, (const uint32_t*)m.ws_.rec_slot, total,
+                       report_args(rp));
+  }
 }
 
 // A run that reads nothing back before its end (run_small, run_steady), launch for launch
@@ -5800,9 +5836,10 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
   constexpr uint32_t kSegWords = sizeof(SegmentRec) / 8;
   const size_t offb = ((T + 1) * 4ull + 7) & ~(size_t)7;
   bool prefetch = rp.prefetch_segments != 0;
+  const bool with_reports = prefetch && rp.prefetch_reports != 0 && rp.do_report != 0;
   if (prefetch) {
     try {
-      grow_dl_dev(offb + v.seg_cap * sizeof(SegmentRec));
+      grow_dl_dev(offb + v.seg_cap * (sizeof(SegmentRec) + (with_reports ? sizeof(ReportRec) : 0)));
     } catch (const BatchTooLarge&) {
       prefetch = false;   // the ordinary download sizes its buffer from the counts instead
     }
@@ -5814,11 +5851,16 @@ bool Matcher::run_small(const RunParams& rp, const DevGraph& g) {
     hipLaunchKernelGGL(k_gather_recs, dim3(std::min<uint32_t>(T, 8192u)), dim3(64), 0, st, T, (const uint32_t*)w.seg_base,
                        (const uint32_t*)w.seg_cnt, (const uint32_t*)d_off, (const unsigned long long*)w.segs.get(), kSegWords,
                        (unsigned long long*)(dl_dev_ + offb));
+    if (with_reports)
+      hipLaunchKernelGGL(k_gather_reports_small, dim3(std::min<uint32_t>(T, 8192u)), dim3(64), 0, st, v, (const uint32_t*)d_off,
+                         (unsigned long long*)(dl_dev_ + offb + v.seg_cap * sizeof(SegmentRec)));
     RM_HIP(hipMemcpyAsync(hoff_, d_off, (T + 1) * 4ull, hipMemcpyDeviceToHost, st));
   }
   read_back(true);
   if (small_aborted(v, hctl_, htot())) return false;
   seg_prefetched_ = prefetch;
+  rep_prefetched_ = prefetch && with_reports;
+  rep_prefetch_at_ = offb + v.seg_cap * sizeof(SegmentRec);
   finish_run(rp);
   return true;
 }
@@ -5909,6 +5951,24 @@ void Matcher::run_device(const RunParams& rp) {
   const DevGraph g = eng_->dev_snapshot();
   if (!hctl_) hctl_.reserve(32);
   seg_prefetched_ = false;
+  rep_prefetched_ = false;
+  // a Report run's per-trace level masks (RunParams): through pinned staging, behind the inputs.
+  // Set here for every run: Stages::k4, which reads levels_on_, is reached only through this
+  // function (run_small, run_steady and the ordinary path below), so no run sees another's masks.
+  levels_on_ = rp.do_report && rp.trace_report_mask && rp.trace_transition_mask;
+  if (levels_on_) {
+    if (2ull * T > levels_dev_.cap() || !levels_dev_ || !levels_host_) {
+      RM_HIP(hipStreamSynchronize(st));
+      levels_host_.reset();
+      levels_dev_.reset();
+      const uint64_t c = std::max<uint64_t>(2ull * T + T, 8192);
+      levels_host_.reserve(c, "pinned staging of the report levels does not fit in host memory");
+      grow_workspace([&] { levels_dev_.reserve(c); });
+    }
+    std::memcpy(levels_host_, rp.trace_report_mask, T * 4ull);
+    std::memcpy(levels_host_ + T, rp.trace_transition_mask, T * 4ull);
+    RM_HIP(hipMemcpyAsync(levels_dev_, levels_host_, 2ull * T * 4u, hipMemcpyHostToDevice, st));
+  }
   // (a forced locality order takes the ordinary path: the small one runs in slot order)
   if (P <= small_batch_points() && locality_ <= 0 && run_small(rp, g)) return;
   // locality mode: 0 slot order, 1 K1 + K2 in locality order, 2 the path stage too; auto (-1): 2 on
@@ -6040,33 +6100,49 @@ void Matcher::get_trace_errors(uint32_t* out) {
   if (n_traces_) RM_HIP(hipMemcpy(out, ws_.trace_err, n_traces_ * 4ull, hipMemcpyDeviceToHost));
 }
 
-// report() on host-supplied segment lists, one thread per trace (rm_report_segments)
+// report() on host-supplied segment lists, one wave per trace (rm_report_segments, rm_report_replies):
+// uploaded, run and left in HBM; trace k's reports start at reps[seg_off[k]]
+void report_segments_device(int device, uint32_t T, const uint32_t* seg_off, const SegmentRec* segs, const double* end_time,
+                            const double* threshold, const uint32_t* rmask, const uint32_t* tmask, DeviceReports& out) {
+  RM_HIP(hipSetDevice(device));
+  for (uint32_t k = 0; k < T; ++k)
+    if (seg_off[k + 1] < seg_off[k]) throw std::runtime_error("segment offsets not monotone");
+  const uint64_t S = seg_off[T];
+  out.seg_off.reserve(T + 1);
+  out.segs.reserve(S);
+  out.reps.reserve(S);
+  out.stats.reserve(T);
+  DevBuf<double> d_end(T), d_thr(T);
+  DevBuf<uint32_t> d_rm(T), d_tm(T);
+  RM_HIP(hipMemcpy(out.seg_off, seg_off, (T + 1) * 4ull, hipMemcpyHostToDevice));
+  {
+    std::vector<uint32_t> cnt(T);
+    for (uint32_t k = 0; k < T; ++k) cnt[k] = seg_off[k + 1] - seg_off[k];
+    out.seg_cnt.reserve(T);
+    RM_HIP(hipMemcpy(out.seg_cnt, cnt.data(), T * 4ull, hipMemcpyHostToDevice));
+  }
+  if (S) RM_HIP(hipMemcpy(out.segs, segs, S * sizeof(SegmentRec), hipMemcpyHostToDevice));
+  RM_HIP(hipMemcpy(d_end, end_time, T * 8ull, hipMemcpyHostToDevice));
+  RM_HIP(hipMemcpy(d_thr, threshold, T * 8ull, hipMemcpyHostToDevice));
+  RM_HIP(hipMemcpy(d_rm, rmask, T * 4ull, hipMemcpyHostToDevice));
+  RM_HIP(hipMemcpy(d_tm, tmask, T * 4ull, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_report_lists, dim3(T), dim3(64), 0, 0, T, out.seg_off, out.segs, d_end, d_thr, d_rm, d_tm,
+                     out.reps, out.stats);
+  RM_HIP(hipGetLastError());
+  RM_HIP(hipStreamSynchronize(0));   // (the parameter arrays go with this call)
+}
+
 void report_segments(int device, uint32_t T, const uint32_t* seg_off, const SegmentRec* segs, const double* end_time,
                      const double* threshold, const uint32_t* rmask, const uint32_t* tmask, uint32_t* rep_off,
                      ReportRec* reps, ReportStats* stats) {
   RM_HIP(hipSetDevice(device));
   if (T == 0) { rep_off[0] = 0; return; }
-  for (uint32_t k = 0; k < T; ++k)
-    if (seg_off[k + 1] < seg_off[k]) throw std::runtime_error("segment offsets not monotone");
+  DeviceReports d;
+  report_segments_device(device, T, seg_off, segs, end_time, threshold, rmask, tmask, d);
   const uint64_t S = seg_off[T];
-  DevBuf<uint32_t> d_off(T + 1);
-  DevBuf<SegmentRec> d_segs(S);
-  DevBuf<double> d_end(T), d_thr(T);
-  DevBuf<uint32_t> d_rm(T), d_tm(T);
-  DevBuf<ReportRec> d_reps(S);
-  DevBuf<ReportStats> d_st(T);
-  RM_HIP(hipMemcpy(d_off, seg_off, (T + 1) * 4ull, hipMemcpyHostToDevice));
-  if (S) RM_HIP(hipMemcpy(d_segs, segs, S * sizeof(SegmentRec), hipMemcpyHostToDevice));
-  RM_HIP(hipMemcpy(d_end, end_time, T * 8ull, hipMemcpyHostToDevice));
-  RM_HIP(hipMemcpy(d_thr, threshold, T * 8ull, hipMemcpyHostToDevice));
-  RM_HIP(hipMemcpy(d_rm, rmask, T * 4ull, hipMemcpyHostToDevice));
-  RM_HIP(hipMemcpy(d_tm, tmask, T * 4ull, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_report_lists, dim3(T), dim3(64), 0, 0, T, d_off, d_segs, d_end, d_thr, d_rm, d_tm,
-                     d_reps, d_st);
-  RM_HIP(hipGetLastError());
   std::vector<ReportRec> all(S);
-  if (S) RM_HIP(hipMemcpy(all.data(), d_reps, S * sizeof(ReportRec), hipMemcpyDeviceToHost));
-  RM_HIP(hipMemcpy(stats, d_st, T * sizeof(ReportStats), hipMemcpyDeviceToHost));
+  if (S) RM_HIP(hipMemcpy(all.data(), d.reps, S * sizeof(ReportRec), hipMemcpyDeviceToHost));
+  RM_HIP(hipMemcpy(stats, d.stats, T * sizeof(ReportStats), hipMemcpyDeviceToHost));
   uint64_t at = 0;
   for (uint32_t k = 0; k < T; ++k) {
     rep_off[k] = (uint32_t)at;
@@ -6297,6 +6373,68 @@ void Matcher::get_segments(std::vector<uint32_t>& seg_off, std::vector<SegmentRe
                        return segs.data();
                      });
 }
+// A Report run's records for the host writer (reply.hip reply_format_host): the segments compacted
+// per trace; trace k's reports are reps[rep_base[k] .. + rep_cnt[k]).  A small run that readied them
+// (RunParams::prefetch_reports) gives all three in one read-back, the reports at the segments' offsets.
+void Matcher::get_report_records(std::vector<uint32_t>& seg_off, std::vector<SegmentRec>& segs, std::vector<uint32_t>& rep_base,
+                                 std::vector<uint32_t>& rep_cnt, std::vector<ReportRec>& reps, std::vector<ReportStats>& stats) {
+  sync();
+  if (!has_report_) throw std::runtime_error("the last run did not compute reports");
+  const uint32_t T = n_traces_;
+  seg_off.assign((size_t)T + 1, 0u);
+  segs.clear(); reps.clear();
+  rep_base.assign(T, 0u); rep_cnt.assign(T, 0u); stats.resize(T);
+  if (!T) return;
+  RM_HIP(hipSetDevice(eng_->device()));
+  if (seg_prefetched_ && rep_prefetched_) {
+    seg_prefetched_ = rep_prefetched_ = false;   // once: the buffers are shared with the other downloads
+    std::memcpy(seg_off.data(), hoff_, ((size_t)T + 1) * 4);
+    const uint64_t at = seg_off[T];
+    const size_t offb = (((size_t)T + 1) * 4 + 7) & ~(size_t)7;
+    const size_t sb = (size_t)at * sizeof(SegmentRec), rb = (size_t)at * sizeof(ReportRec), tb = (size_t)T * sizeof(ReportStats);
+    grow_dl_host(sb + rb + tb);
+    if (at) {
+      RM_HIP(hipMemcpyAsync(dl_host_, dl_dev_ + offb, sb, hipMemcpyDeviceToHost, stream_));
+      RM_HIP(hipMemcpyAsync(dl_host_ + sb, dl_dev_ + rep_prefetch_at_, rb, hipMemcpyDeviceToHost, stream_));
+    }
+    RM_HIP(hipMemcpyAsync(dl_host_ + sb + rb, ws_.stats, tb, hipMemcpyDeviceToHost, stream_));
+    RM_HIP(hipStreamSynchronize(stream_));
+    segs.resize(at); reps.resize(at);
+    if (at) {
+      std::memcpy(segs.data(), dl_host_, sb);
+      std::memcpy(reps.data(), dl_host_ + sb, rb);
+    }
+    std::memcpy(stats.data(), dl_host_ + sb + rb, tb);
+    for (uint32_t k = 0; k < T; ++k) {
+      rep_base[k] = seg_off[k];
+      const uint32_t S = seg_off[k + 1] - seg_off[k];
+      rep_cnt[k] = stats[k].n_reports <= 0 ? 0u : std::min<uint32_t>((uint32_t)stats[k].n_reports, S);
+    }
+    return;
+  }
+  get_segments(seg_off, segs);
+  RM_HIP(hipMemcpy(stats.data(), ws_.stats, T * sizeof(ReportStats), hipMemcpyDeviceToHost));
+  std::vector<uint32_t> rep_off((size_t)T + 1, 0u);
+  download_compacted(ws_.seg_base, ws_.rep_cnt, ws_.reps, sizeof(ReportRec) / 8, rep_off.data(), nullptr,
+                     [&](uint64_t n) -> void* {
+                       reps.resize(n);
+                       return reps.data();
+                     });
+  for (uint32_t k = 0; k < T; ++k) { rep_base[k] = rep_off[k]; rep_cnt[k] = rep_off[k + 1] - rep_off[k]; }
+}
+
+// where a Report run left its records in HBM, for the device writer (reply.hip ReplyWriter)
+ReplySource Matcher::reply_source() {
+  sync();
+  if (!has_report_) throw std::runtime_error("the last run did not compute reports");
+  ReplySource s;
+  s.T = n_traces_;
+  s.seg_base = ws_.seg_base; s.seg_cnt = ws_.seg_cnt; s.rep_base = ws_.seg_base;
+  s.segs = ws_.segs; s.reps = ws_.reps; s.stats = ws_.stats;
+  s.cap = ws_.cap_segs;
+  return s;
+}
+
 uint64_t Matcher::count_reports() {
   sync();
   if (!has_report_) return 0;

@@ -96,6 +96,12 @@ struct RunParams {
   // a small batch (Matcher::run_small) also lays out and compacts its segments on the device
   // before its one read-back, so get_segments is a single copy (the service's reply path)
   int prefetch_segments = 0;
+  // A Report run (DESIGN.md §3 rule 19): the level masks per trace (host arrays of n_traces words,
+  // both or neither; null: the two scalars above for every trace) ...
+  const uint32_t* trace_report_mask = nullptr;
+  const uint32_t* trace_transition_mask = nullptr;
+  // ... and a small run also readies its reports and stats for its one read-back (prefetch_segments)
+  int prefetch_reports = 0;
 };
 
 // Device addresses of a batch's inputs: the workspace's arrays, or (a small run()) the one
@@ -581,6 +587,57 @@ unsigned long long lines_hash_mask();   // RM_LINES_HASH_BITS as the line reader
 void report_segments(int device, uint32_t T, const uint32_t* seg_off, const SegmentRec* segs, const double* end_time,
                      const double* threshold, const uint32_t* rmask, const uint32_t* tmask, uint32_t* rep_off,
                      ReportRec* reps, ReportStats* stats);
+// the same, left in HBM (T >= 1): trace k's reports are reps[seg_off[k] .. + stats[k].n_reports)
+struct DeviceReports {
+  DevBuf<uint32_t> seg_off, seg_cnt;
+  DevBuf<SegmentRec> segs;
+  DevBuf<ReportRec> reps;
+  DevBuf<ReportStats> stats;
+};
+void report_segments_device(int device, uint32_t T, const uint32_t* seg_off, const SegmentRec* segs, const double* end_time,
+                            const double* threshold, const uint32_t* rmask, const uint32_t* tmask, DeviceReports& out);
+
+// ---- the /report reply (DESIGN.md §3 rule 19; reply.hip, reply_text.hpp) ----
+// Both writers give the n replies in one malloc'd, NUL-terminated buffer: reply i is
+// (*buf)[off[i], off[i+1]) (off: T + 1 entries).  A trace holding a time outside the time routine's
+// range is flagged and written with std::to_chars by either writer (the device writer splices it in
+// on the host after the download); *flagged counts them.
+// host: trace k's segments are segs[seg_off[k] .. seg_off[k+1]), its reports reps[rep_base[k] .. + rep_cnt[k])
+void reply_format_host(uint32_t T, const uint32_t* seg_off, const SegmentRec* segs, const uint32_t* rep_base,
+                       const uint32_t* rep_cnt, const ReportRec* reps, const ReportStats* stats, char** buf, uint64_t* off,
+                       uint64_t* flagged);
+// one trace's reply into a string (a coalesced request's caller formats its own)
+void reply_format_one(const SegmentRec* segs, uint32_t S, const ReportRec* reps, uint32_t R, const ReportStats& st, std::string& o);
+// device: the records of T traces in HBM; trace k's segments are segs[seg_base[k] .. + seg_cnt[k]), its
+// reports reps[rep_base[k] .. + stats[k].n_reports); cap: the records either pool holds
+struct ReplySource {
+  uint32_t T = 0;
+  const uint32_t* seg_base = nullptr;
+  const uint32_t* seg_cnt = nullptr;
+  const uint32_t* rep_base = nullptr;
+  const SegmentRec* segs = nullptr;
+  const ReportRec* reps = nullptr;
+  const ReportStats* stats = nullptr;
+  uint64_t cap = 0;
+};
+// The device writer with its grow-only buffers.  write() runs on st and returns synchronised;
+// *ms: its kernels' and scans' device time.
+class ReplyWriter {
+ public:
+  void write(int device, hipStream_t st, const ReplySource& src, char** buf, uint64_t* off, uint64_t* flagged, double* ms);
+
+ private:
+  DevBuf<uint32_t> flag_, item_trace_;
+  DevBuf<unsigned long long> cnt_, ioff_, roff_, len_, ofs_;
+  DevBuf<char> blob_;
+  PinBuf<unsigned long long> hn_;
+  uint64_t t_cap_ = 0, i_cap_ = 0, blob_cap_ = 0;
+  ScanScratch scr_{"reply buffers do not fit in HBM"};
+  PartTimer timer_;
+};
+// runs at or below this many points are written on the host (RM_REPLY_DEVICE_MIN_POINTS, read per
+// call; default: the matcher's small-run limit)
+uint64_t reply_device_min_points();
 
 // The tile stage's collectives (one process per GPU): RCCL over xGMI, or a host transport the
 // caller injects (capi.cpp rm_comm_init_host).  Both are blocking on `st`.
@@ -641,6 +698,10 @@ class Matcher {
   uint64_t count_segments();
   void get_reports(uint32_t* rep_off, ReportRec* reps, ReportStats* stats);
   uint64_t count_reports();
+  // a Report run's records for the host writer, and where they lie in HBM for the device writer
+  void get_report_records(std::vector<uint32_t>& seg_off, std::vector<SegmentRec>& segs, std::vector<uint32_t>& rep_base,
+                          std::vector<uint32_t>& rep_cnt, std::vector<ReportRec>& reps, std::vector<ReportStats>& stats);
+  struct ReplySource reply_source();
   // Matched points of the last run()/rerun (rule 9; points.hip): one record per input point in
   // batch point order (n_points()), computed on request from what the run left in HBM
   void matched_points(MatchedPoint* out);
@@ -781,7 +842,12 @@ class Matcher {
   PinBuf<char> hpack_;         // pinned staging and device block of a small run()'s inputs (grow-only,
   DevBuf<char> dpack_;         // both of dpack_.cap() bytes)
   PinBuf<uint32_t> hoff_;      // pinned: a small run's per-trace segment offsets (T + 1), prefetched
+  DevBuf<uint32_t> levels_dev_;    // a Report run's per-trace level masks (report, then transition) and
+  PinBuf<uint32_t> levels_host_;   // their pinned staging (grow-only, both of levels_dev_.cap() words)
+  bool levels_on_ = false;         // the current run reads them
   bool seg_prefetched_ = false;
+  bool rep_prefetched_ = false;    // ... and its reports beside them, rep_prefetch_at_ bytes into dl_dev_
+  size_t rep_prefetch_at_ = 0;
   DevBuf<char> dl_dev_;        // grow-only device / pinned host buffers of download_compacted
   PinBuf<char> dl_host_;
   DevBuf<MatchedPoint> mp_dev_;   // grow-only device buffer of matched_points

@@ -55,6 +55,22 @@ struct PointSink {
   size_t size() const { return lon.size(); }
 };
 
+// match_options.report_levels / transition_levels as the Report calls take them (DESIGN.md §3 rule
+// 19; reference py/reporter_service.py:228-235): bit (level + 1) per number entry that is an
+// integer in -1..7 (engine.levels_mask), other numbers set nothing.  Match ignores both keys.
+struct ReportLevels {
+  uint32_t report_mask = 0, transition_mask = 0;
+  int report_state = 0, transition_state = 0;   // 0 absent, 1 an array of numbers, 2 not an array, 3 a non-number entry
+  // the request's failure as a Report request, or null
+  const char* error() const {
+    if (report_state == 0 || report_state == 2) return "match_options must include report_levels array";
+    if (report_state == 3) return "report_levels entries must be numbers";
+    if (transition_state == 0 || transition_state == 2) return "match_options must include transition_levels array";
+    if (transition_state == 3) return "transition_levels entries must be numbers";
+    return nullptr;
+  }
+};
+
 inline int mode_index(const char* s, size_t n) {
   auto eq = [&](const char* m) { return std::strlen(m) == n && std::memcmp(s, m, n) == 0; };
   if (eq("auto")) return kModeAuto;
@@ -108,6 +124,9 @@ class Reader {
     throw std::runtime_error(err);
   }
 
+  // what the first match_options said about the report levels (after request())
+  const ReportLevels& levels() const { return levels_; }
+
   // the correctly rounded double of one number token in JSON's grammar (s[n] is a NUL), by the
   // conversion every request number takes; the separated-value reader (sv_lines.hpp) shares it
   static double number_value(const char* s, size_t n) {
@@ -142,6 +161,8 @@ class Reader {
   int opt_state_[kNumOpt] = {};  // 0 absent / null, 1 number, 2 wrong type (first occurrence)
   double opt_val_[kNumOpt] = {};
   bool opt_seen_[kNumOpt] = {};
+  ReportLevels levels_;
+  bool levels_seen_[2] = {false, false};
 
   static void truncate(PointSink& s, size_t n) {
     s.lon.resize(n); s.lat.resize(n); s.acc.resize(n); s.time.resize(n);
@@ -502,6 +523,12 @@ class Reader {
         const Kind kd = scalar(2, v);
         opt_state_[k] = kd == kNum ? 1 : (kd == kNull ? 0 : 2);
         opt_val_[k] = v;
+      } else if (key_is(b, e, "report_levels") && !levels_seen_[0]) {
+        levels_seen_[0] = true;
+        levels_.report_state = levels_value(levels_.report_mask);
+      } else if (key_is(b, e, "transition_levels") && !levels_seen_[1]) {
+        levels_seen_[1] = true;
+        levels_.transition_state = levels_value(levels_.transition_mask);
       } else if (key_is(b, e, "mode") && !mode_seen_) {
         mode_seen_ = true;
         ws();
@@ -522,6 +549,25 @@ class Reader {
       if (*p_ == ',') { ++p_; continue; }
       if (*p_ == '}') { ++p_; return; }
       fail("expected ',' or '}'");
+    }
+  }
+
+  // a level array: its state (ReportLevels) and the mask of its entries
+  int levels_value(uint32_t& mask) {
+    mask = 0;
+    ws();
+    if (*p_ != '[') { skip(2); return 2; }
+    ++p_; ws();
+    if (*p_ == ']') { ++p_; return 1; }
+    int state = 1;
+    for (;;) {
+      double v = 0.0;
+      if (scalar(3, v) != kNum) state = 3;
+      else if (v >= -1.0 && v <= 7.0 && v == std::floor(v)) mask |= 1u << ((int)v + 1);
+      ws();
+      if (*p_ == ',') { ++p_; continue; }
+      if (*p_ == ']') { ++p_; return state; }
+      fail("expected ',' or ']'");
     }
   }
 
@@ -681,6 +727,21 @@ inline MatchOptions parse_request_deferred(const char* text, size_t len, const M
   span = TraceSpan();
   Reader r(text, len, mode_defaults, &span);
   return r.request(sink);
+}
+// Parse one Report request: parse_request, then the level arrays' own failures (a request that
+// fails as a Match request fails with that error first).  lv may be filled on a deferred read too.
+inline MatchOptions parse_report_request(const char* text, size_t len, const MatchOptions mode_defaults[5], PointSink& sink,
+                                         ReportLevels& lv, TraceSpan* span = nullptr) {
+  if (span) *span = TraceSpan();
+  Reader r(text, len, mode_defaults, span);
+  const size_t n0 = sink.size();
+  const MatchOptions o = r.request(sink);
+  lv = r.levels();
+  if (const char* e = lv.error()) {
+    sink.lon.resize(n0); sink.lat.resize(n0); sink.acc.resize(n0); sink.time.resize(n0);
+    throw std::runtime_error(e);
+  }
+  return o;
 }
 // the same, with the text's length known (len = strlen(text): the NUL at text[len] ends it)
 inline MatchOptions parse_request(const char* text, size_t len, const MatchOptions mode_defaults[5], PointSink& sink) {

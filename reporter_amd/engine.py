@@ -1271,6 +1271,53 @@ def report_segments(seg_off, segs, trace_end_time, threshold_sec, report_mask, t
     return rep_off, reps[: rep_off[-1]], stats[:n]
 
 
+def _take_replies(buf, off):
+    """The n replies (bytes) of a library-allocated packed buffer, which is released."""
+    try:
+        n = len(off) - 1
+        blob = C.string_at(buf.value, int(off[n])) if n else b""
+    finally:
+        _lib.lib().rm_free(buf)
+    return [blob[int(off[i]):int(off[i + 1])] for i in range(n)]
+
+
+def report_replies(seg_off, segs, trace_end_time, threshold_sec, report_mask, transition_mask, writer=0):
+    """report() and the complete /report reply of every trace (rm_report_replies, DESIGN.md rule 19)
+    over host segment lists, arguments as report_segments.  writer 0: by size, 1: the host formats
+    the downloaded records, 2: the text is written on the device.  Returns (replies, info) with info
+    = dict(bytes, flagged, writer, device_ms)."""
+    seg_off = _c(seg_off, np.uint32)
+    n = len(seg_off) - 1
+    segs = np.ascontiguousarray(segs, SEGMENT_DTYPE)
+    bc = lambda x, dt: _c(np.broadcast_to(np.asarray(x, dt), (n,)), dt)
+    end, thr = bc(trace_end_time, np.float64), bc(threshold_sec, np.float64)
+    rm, tm = bc(report_mask, np.uint32), bc(transition_mask, np.uint32)
+    d = _lib.RmReportDesc(n, seg_off.ctypes.data, segs.ctypes.data if len(segs) else None, end.ctypes.data,
+                          thr.ctypes.data, rm.ctypes.data, tm.ctypes.data)
+    buf = C.c_void_p()
+    off = np.zeros(n + 1, np.uint64)
+    info = np.zeros(4, np.uint64)
+    _lib.check(_lib.lib().rm_report_replies(C.byref(d), int(writer), C.byref(buf), off.ctypes.data, info.ctypes.data))
+    return _take_replies(buf, off), dict(bytes=int(info[0]), flagged=int(info[1]), writer=int(info[2]),
+                                         device_ms=int(info[3]) / 1000.0)
+
+
+def format_replies_host(seg_off, segs, rep_off, reps, stats):
+    """The /report replies of given segment, report and stats records (rm_report_format_host): the
+    formatting alone, no GPU."""
+    seg_off, rep_off = _c(seg_off, np.uint32), _c(rep_off, np.uint32)
+    n = len(seg_off) - 1
+    segs = np.ascontiguousarray(segs, SEGMENT_DTYPE)
+    reps = np.ascontiguousarray(reps, REPORT_DTYPE)
+    stats = np.ascontiguousarray(stats, STATS_DTYPE)
+    buf = C.c_void_p()
+    off = np.zeros(n + 1, np.uint64)
+    _lib.check(_lib.lib().rm_report_format_host(n, seg_off.ctypes.data, segs.ctypes.data if len(segs) else None,
+                                                rep_off.ctypes.data, reps.ctypes.data if len(reps) else None,
+                                                stats.ctypes.data if n else None, C.byref(buf), off.ctypes.data))
+    return _take_replies(buf, off)
+
+
 def segment_dicts(segs):
     """Match-reply segments (README.md:288-301 schema) from SEGMENT_DTYPE records."""
     out = []

@@ -87,6 +87,55 @@ class SegmentMatcher(object):
         finally:
             _lib.lib().rm_free(buf)
 
+    def Report(self, trace_json, threshold_sec=15):
+        """The whole /report reply from one call (rm_report): the request Match takes in, the body
+        the reference's service builds from Match, json.loads, report() and json.dumps
+        (py/reporter_service.py:240-243) out -- stats, shape_used, segment_matcher and datastore --
+        with report() run on the GPU in the same run.  The request's match_options must carry the
+        report_levels and transition_levels arrays; threshold_sec is the service's THRESHOLD_SEC."""
+        if _fast is not None and hasattr(_fast, "report"):
+            return _fast.report(self._h or 0, trace_json, float(threshold_sec))
+        if isinstance(trace_json, str):
+            trace_json = trace_json.encode("utf-8")
+        out = C.c_void_p()
+        rc = _lib.lib().rm_report(self._h, trace_json, float(threshold_sec), C.byref(out))
+        if rc != 0:
+            raise RuntimeError(_lib.last_error())
+        try:
+            return C.string_at(out.value).decode("utf-8")
+        finally:
+            _lib.lib().rm_free(out)
+
+    def ReportMany(self, trace_jsons, threshold_sec=15):
+        """Batched Report: many requests in one uncoalesced GPU pass (rm_report_batch_packed).  A
+        run above RM_REPLY_DEVICE_MIN_POINTS points has its reply text written on the GPU."""
+        n = len(trace_jsons)
+        if n == 0:
+            return []
+        try:
+            arr = (C.c_char_p * n)(*trace_jsons)   # bytes, as the service receives them
+        except TypeError:
+            arr = (C.c_char_p * n)(*[t.encode("utf-8") if isinstance(t, str) else t for t in trace_jsons])
+        off = (C.c_uint64 * (n + 1))()
+        buf = C.c_void_p()
+        rc = _lib.lib().rm_report_batch_packed(self._h, arr, n, float(threshold_sec), C.byref(buf), off)
+        if rc != 0:
+            raise RuntimeError(_lib.last_error())
+        try:
+            o = list(off)
+            mv = memoryview((C.c_char * max(o[n], 1)).from_address(buf.value)).cast("B")
+            return [str(mv[o[i]:o[i + 1]], "utf-8") for i in range(n)]
+        finally:
+            _lib.lib().rm_free(buf)
+
+    def last_report_info(self):
+        """The last ReportMany: reply bytes, flagged traces, the writer used (1 host, 2 device) and
+        the device writer's kernel time (ms)."""
+        out = (C.c_uint64 * 4)()
+        if _lib.lib().rm_report_info(self._h, out) != 0:
+            raise RuntimeError(_lib.last_error())
+        return dict(bytes=int(out[0]), flagged=int(out[1]), writer=int(out[2]), device_ms=int(out[3]) / 1000.0)
+
     def MatchPoints(self, trace_json):
         """Match plus the snapped road position of every input point: the same request in,
         {"segments": [...], "matched_points": [...]} out (rm_match_points; one entry per point,

@@ -16,14 +16,19 @@
 
 #include "../include/reporter_match.h"
 
-static PyObject* py_match(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
-  (void)self;
-  if (nargs != 2) {
-    PyErr_SetString(PyExc_TypeError, "match(handle, trace_json)");
+/* the shared body: report == 0 is match(handle, trace_json), else report(handle, trace_json, threshold_sec) */
+static PyObject* call(PyObject* const* args, Py_ssize_t nargs, int report) {
+  if (nargs != (report ? 3 : 2)) {
+    PyErr_SetString(PyExc_TypeError, report ? "report(handle, trace_json, threshold_sec)" : "match(handle, trace_json)");
     return NULL;
   }
   const unsigned long long h = PyLong_AsUnsignedLongLong(args[0]);
   if (PyErr_Occurred()) return NULL;
+  double threshold = 0.0;
+  if (report) {
+    threshold = PyFloat_AsDouble(args[2]);
+    if (threshold == -1.0 && PyErr_Occurred()) return NULL;
+  }
   if (h == 0) {
     PyErr_SetString(PyExc_RuntimeError, "matcher is NULL");   /* the library's own message */
     return NULL;
@@ -43,7 +48,7 @@ static PyObject* py_match(PyObject* self, PyObject* const* args, Py_ssize_t narg
   int rc;
   Py_INCREF(obj);   /* its buffer is read without the GIL */
   Py_BEGIN_ALLOW_THREADS
-  rc = rm_match((rm_matcher*)(uintptr_t)h, s, &out);
+  rc = report ? rm_report((rm_matcher*)(uintptr_t)h, s, threshold, &out) : rm_match((rm_matcher*)(uintptr_t)h, s, &out);
   Py_END_ALLOW_THREADS
   Py_DECREF(obj);
   if (rc != 0) {
@@ -55,9 +60,22 @@ static PyObject* py_match(PyObject* self, PyObject* const* args, Py_ssize_t narg
   return r;
 }
 
+static PyObject* py_match(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+  (void)self;
+  return call(args, nargs, 0);
+}
+
+/* SegmentMatcher.Report: the whole /report reply (rm_report), same contract as match */
+static PyObject* py_report(PyObject* self, PyObject* const* args, Py_ssize_t nargs) {
+  (void)self;
+  return call(args, nargs, 1);
+}
+
 static PyMethodDef kMethods[] = {
     {"match", (PyCFunction)(void (*)(void))py_match, METH_FASTCALL,
      "match(handle, trace_json) -> str: rm_match on an rm_matcher handle, GIL released"},
+    {"report", (PyCFunction)(void (*)(void))py_report, METH_FASTCALL,
+     "report(handle, trace_json, threshold_sec) -> str: rm_report on an rm_matcher handle, GIL released"},
     {NULL, NULL, 0, NULL}};
 
 static struct PyModuleDef kModule = {PyModuleDef_HEAD_INIT, "_match",

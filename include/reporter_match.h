@@ -514,6 +514,49 @@ int rm_runner_lines_time(rm_runner* r, double ms[4]);   /* upload, parse (+ host
 /* host only, no GPU: the generic rule over the same input; arrays sized by a first call with NULLs */
 int rm_lines_parse_host(const rm_lines_desc* d, uint64_t info[7], uint32_t* uuid, double* time, float* lon, float* lat,
                         float* acc, uint32_t* chunk, uint64_t* off, uint32_t* len, char* err, size_t errlen);
+/* Gzip input (DESIGN.md §3 rule 20): the reference's source files are gzip (load_data.sh:11,
+ * simple_reporter.py:99).  A chunk is a sequence of gzip members read as Python's gzip module reads
+ * them: FEXTRA / FNAME / FCOMMENT / FHCRC skipped (the FHCRC value and the reserved flag bits are
+ * not checked, unlike zlib's gzread), CRC-32 and ISIZE checked per member, zero bytes after a
+ * trailer skipped, the window not carried across members.  status[c]: 0 ok, 1 header, 2 truncated,
+ * 3 malformed block, 4 CRC, 5 size, 6 too large: the first error in stream order.  out_len[c]: the
+ * chunk's inflated bytes (0 for a bad chunk); *blob (library-allocated, rm_free): the good chunks'
+ * bytes end to end in input order.  The call itself fails only for NULL arguments, a device error,
+ * or more than 2^32 inflated bytes.  rm_inflate decodes one chunk per wave on `device`;
+ * rm_inflate_host runs the same decoder core on the host pool, no GPU.  rm_inflate_last: of the
+ * calling thread's last rm_inflate / rm_inflate_host (either may be NULL) info: members, bytes in,
+ * bytes out, chunks that took the device's second pass (their slot, sized from the last member's
+ * ISIZE, was too small); ms: device inflate (with the CRC, which is computed as the window is
+ * flushed), 0, gather. */
+int rm_inflate(int device, uint32_t n, const char* const* data, const uint64_t* len, uint32_t* status,
+               uint64_t* out_len, char** blob, size_t* blob_len);
+int rm_inflate_host(uint32_t n, const char* const* data, const uint64_t* len, uint32_t* status,
+                    uint64_t* out_len, char** blob, size_t* blob_len);
+void rm_inflate_last(uint64_t info[4], double ms[3]);
+const char* rm_inflate_status_text(uint32_t status);
+/* The runner's input coding, sticky: how rm_runner_run_lines, rm_runner_parse_lines and
+ * rm_session_push_messages* read their chunks from now on.  0 plain (the default: bytes are text
+ * whatever they look like), 1 gzip (every chunk), 2 gzip where a chunk begins 1f 8b.  Gzip chunks are
+ * inflated on the device into the text the line reader parses, so line numbers, lines_info and the
+ * points cannot tell the difference; a call with fewer than RM_INFLATE_DEVICE_MIN_CHUNKS gzip chunks
+ * (environment; default 1024, the measured break-even: DESIGN.md §5) inflates them on the host pool with the same decoder core and uploads
+ * plain text.  A bad chunk fails the call with "chunk <c>: gzip: <reason>" (the first in input order);
+ * with skip_bad it counts as empty and its status stays readable (the reference logs and skips the
+ * file, simple_reporter.py:128-129).  The 2^32 byte limit of a call applies to the inflated total.
+ * rm_runner_get_vehicles' spans then refer to inflated text the caller does not hold:
+ * rm_runner_get_text reads bytes [off, off + len) of chunk `chunk` of the last parse back from the
+ * device (any coding).
+ * chunk_count: the chunks of the runner's last parse, whichever call made it (a push included);
+ * chunk_status: that many words (0 for plain chunks).
+ * inflate_info: chunks inflated, members, bytes in, bytes out, second-pass chunks, chunks inflated on
+ * the host.  inflate_time: inflate (with the CRC), 0, gather; the compressed upload is part of
+ * rm_runner_lines_time's "upload". */
+int rm_runner_set_input_coding(rm_runner* r, int coding, int skip_bad);
+int rm_runner_chunk_count(rm_runner* r, uint32_t* n);
+int rm_runner_chunk_status(rm_runner* r, uint32_t* status);
+int rm_runner_inflate_info(rm_runner* r, uint64_t out[6]);
+int rm_runner_inflate_time(rm_runner* r, double ms[3]);
+int rm_runner_get_text(rm_runner* r, uint32_t chunk, uint64_t off, uint64_t len, char* out);
 typedef struct {
   uint32_t quantisation;      /* --quantisation, default 3600 (:343) */
   uint32_t privacy;           /* --privacy, default 2 (:345) */

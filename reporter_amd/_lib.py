@@ -220,6 +220,16 @@ PROTOTYPES = [
     ("rm_runner_lines_time", C.c_int, [P, C.POINTER(C.c_double)]),
     ("rm_lines_parse_host", C.c_int, [C.POINTER(RmLinesDesc), C.POINTER(C.c_uint64), P, P, P, P, P, P, P, P, C.c_char_p,
                                       C.c_size_t]),
+    ("rm_inflate", C.c_int, [C.c_int, C.c_uint32, P, P, P, P, C.POINTER(P), C.POINTER(C.c_size_t)]),
+    ("rm_inflate_host", C.c_int, [C.c_uint32, P, P, P, P, C.POINTER(P), C.POINTER(C.c_size_t)]),
+    ("rm_inflate_last", None, [C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("rm_inflate_status_text", C.c_char_p, [C.c_uint32]),
+    ("rm_runner_set_input_coding", C.c_int, [P, C.c_int, C.c_int]),
+    ("rm_runner_chunk_count", C.c_int, [P, C.POINTER(C.c_uint32)]),
+    ("rm_runner_chunk_status", C.c_int, [P, P]),
+    ("rm_runner_inflate_info", C.c_int, [P, C.POINTER(C.c_uint64)]),
+    ("rm_runner_inflate_time", C.c_int, [P, C.POINTER(C.c_double)]),
+    ("rm_runner_get_text", C.c_int, [P, C.c_uint32, C.c_uint64, C.c_uint64, P]),
     ("rm_default_tile_params", None, [C.POINTER(RmTileParams)]),
     ("rm_runner_tiles", C.c_int, [P, C.POINTER(RmTileParams), P, C.POINTER(P), C.POINTER(C.c_size_t)]),
     ("rm_default_session_params", None, [C.POINTER(RmSessionParams)]),

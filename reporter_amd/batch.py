@@ -20,6 +20,9 @@ Ingest: the files' lines are parsed and the vehicle ids numbered on the GPU as w
 (read_trace_files + dense_ids) in front of rm_runner_run_points.  --formatter takes one of the
 reference's separated-value formatter strings (Formatter.java:36-51), --bbox and --accuracy-cap
 the download phase's filter and cap (py/simple_reporter.py:105,112), so raw lines can be read too.
+--input gzip (or auto: by the magic bytes 1f 8b) reads the reference's own source files, which are
+gzip (load_data.sh:11, py/simple_reporter.py:99): they are inflated and checked on the GPU
+(DESIGN.md rule 20); a file that does not inflate is logged and skipped (:128-129).
 Multi-GPU: trace files are block-split over ranks (simple_reporter.split, :70-79, the
 reference's process split); rows of every rank are all-gathered over RCCL and each rank
 writes the tile files it owns.  There is no CPU path: the library raises without a GPU.
@@ -104,10 +107,14 @@ def read_chunks(paths):
 
 def run(trace_files, conf, dest_dir, mode="auto", report_levels=(0, 1), transition_levels=(0, 1), quantisation=3600,
         inactivity=120, privacy=2, source="smpl_rprt", rank=0, world=1, device=0, comm=None, ingest="device", fmt=None,
-        bbox=None):
+        bbox=None, coding="plain"):
     from . import dist, engine
     if ingest not in ("device", "host"):
         raise ValueError("ingest is 'device' or 'host'")
+    if coding not in engine.INPUT_CODINGS:
+        raise ValueError("coding is 'plain', 'gzip' or 'auto'")
+    if coding != "plain" and ingest != "device":
+        raise ValueError("gzip input needs ingest='device'")
     mine = dist.split(sorted(trace_files), world)[rank] if world > 1 else sorted(trace_files)
     opts, graph = options_from_config(conf, mode)
     if ingest == "host":
@@ -132,13 +139,17 @@ def run(trace_files, conf, dest_dir, mode="auto", report_levels=(0, 1), transiti
             bm.run_points(idx, pts["time"], pts["lon"], pts["lat"], pts["accuracy"], inactivity=inactivity, opts=opts,
                           n_uuids=len(names), report_levels=report_levels, transition_levels=transition_levels)
         else:
+            bm.set_input_coding(coding, skip_bad=True)
             bm.run_lines(chunks, fmt, inactivity=inactivity, opts=opts, report_levels=report_levels,
                          transition_levels=transition_levels)
+            for path, status in zip(mine, bm.chunk_status()):
+                if status:
+                    logging.error("%s was not processed: %s", path, engine.inflate_status_text(status))
         errs = bm.trace_errors()
         if errs.any():
             owner = bm.trace_uuid()
             if ingest == "device":
-                names = bm.vehicle_names(chunks)
+                names = bm.vehicle_names(chunks if coding == "plain" else None)
             for k in np.nonzero(errs)[0]:
                 logging.error("%s window %d failed to match (error bits %d); skipped", names[owner[k]], k, int(errs[k]))
         files = bm.tiles(quantisation=quantisation, privacy=privacy, source=source, mode=mode, comm=comm)
@@ -162,6 +173,8 @@ def main(argv=None):
     ap.add_argument("--privacy", type=int, default=2)
     ap.add_argument("--source-id", default="smpl_rprt")
     ap.add_argument("--ingest", choices=("device", "host"), default="device", help="where the trace lines are parsed")
+    ap.add_argument("--input", choices=("plain", "gzip", "auto"), default="plain", help="the files' coding: gzip files are "
+                    "inflated on the GPU (auto: those that begin 1f 8b); needs --ingest device")
     ap.add_argument("--formatter", help="separated-value formatter string, e.g. ',sv,\\|,1,9,10,0,5,yyyy-MM-dd HH:mm:ss' "
                     "(default: the trace files' uuid,time,lat,lon,accuracy); the last argument is a date pattern, "
                     "e.g. yyyy-MM-dd'T'HH:mm:ssZZ or yyyyMMddHHmmss (DESIGN.md rule 18)")
@@ -187,9 +200,11 @@ def main(argv=None):
     bbox = [float(x) for x in a.bbox.split(",")] if a.bbox else None
     if bbox is not None and len(bbox) != 4:
         ap.error("--bbox takes min_lat,min_lon,max_lat,max_lon")
+    if a.input != "plain" and a.ingest != "device":
+        ap.error("--input gzip and auto need --ingest device")
     try:
         out = run(files, a.match_config, a.dest_dir, a.mode, levels(a.report_levels), levels(a.transition_levels),
-                  a.quantisation, a.inactivity, a.privacy, a.source_id, rank, world, local, comm, a.ingest, fmt, bbox)
+                  a.quantisation, a.inactivity, a.privacy, a.source_id, rank, world, local, comm, a.ingest, fmt, bbox, a.input)
     finally:
         if comm is not None:
             comm.close()

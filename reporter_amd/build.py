@@ -19,10 +19,10 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libreporter_match.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
-SOURCES = ["engine.hip", "points.hip", "edges.hip", "stages.hip", "lines.hip", "sessions.hip", "tilestore.hip", "directory.hip", "snapshot.hip", "reply.hip", "capi.cpp", "graph.cpp", "graph_osm.cpp", "osm_pbf.cpp", "osm_city.cpp", "world.cpp", "balls.cpp"]
+SOURCES = ["engine.hip", "points.hip", "edges.hip", "stages.hip", "lines.hip", "sessions.hip", "tilestore.hip", "directory.hip", "snapshot.hip", "reply.hip", "inflate.hip", "capi.cpp", "graph.cpp", "graph_osm.cpp", "osm_pbf.cpp", "osm_city.cpp", "world.cpp", "balls.cpp"]
 HEADERS = ["engine.hpp", "graph.hpp", "json.hpp", "rm_common.hpp", "balls.hpp", "serve_policy.hpp", "trace_json.hpp",
            "host_pool.hpp", "osm_model.hpp", "edges_json.hpp", "json_points.hpp", "sv_lines.hpp", "sess_dist.hpp", "tile_text.hpp", "msg_lines.hpp", "snapshot.hpp",
-           "dev_util.hpp", "tile_cull.hpp", "wave_util.hpp", "time_pattern.hpp", "reply_text.hpp"]
+           "dev_util.hpp", "tile_cull.hpp", "wave_util.hpp", "time_pattern.hpp", "reply_text.hpp", "inflate.hpp", "inflate_core.hpp", "inflate_ring.hpp"]
 
 
 def _hipcc():

@@ -28,6 +28,8 @@
 #include "engine.hpp"
 #include "graph.hpp"
 #include "host_pool.hpp"
+#include "inflate.hpp"
+#include "inflate_core.hpp"
 #include "edges_json.hpp"
 #include "json.hpp"
 #include "osm_model.hpp"
@@ -2079,6 +2081,87 @@ int rm_lines_parse_host(const rm_lines_desc* d, uint64_t info[7], uint32_t* uuid
   }
   return rc;
 }
+
+int rm_runner_set_input_coding(rm_runner* r, int coding, int skip_bad) {
+  return guarded([&] {
+    if (!r) throw std::runtime_error("runner is NULL");
+    r->m->set_input_coding(coding, skip_bad != 0);
+  });
+}
+static Matcher& runner_matcher(rm_runner* r) {
+  if (!r) throw std::runtime_error("runner is NULL");
+  return *r->m;
+}
+int rm_runner_chunk_count(rm_runner* r, uint32_t* n) {
+  return guarded([&] {
+    if (!n) throw std::runtime_error("n is NULL");
+    *n = runner_matcher(r).chunk_count();
+  });
+}
+int rm_runner_chunk_status(rm_runner* r, uint32_t* status) {
+  return guarded([&] {
+    Matcher& m = runner_matcher(r);
+    if (!status && m.chunk_count()) throw std::runtime_error("status is NULL");
+    m.chunk_status(status);
+  });
+}
+int rm_runner_inflate_info(rm_runner* r, uint64_t out[6]) {
+  return guarded([&] {
+    if (!out) throw std::runtime_error("out is NULL");
+    runner_matcher(r).inflate_info(out);
+  });
+}
+int rm_runner_inflate_time(rm_runner* r, double ms[3]) {
+  return guarded([&] {
+    if (!ms) throw std::runtime_error("ms is NULL");
+    runner_matcher(r).inflate_time(ms);
+  });
+}
+int rm_runner_get_text(rm_runner* r, uint32_t chunk, uint64_t off, uint64_t len, char* out) {
+  return guarded([&] { runner_matcher(r).get_text(chunk, off, len, out); });
+}
+// the calling thread's last rm_inflate / rm_inflate_host: members, bytes in, bytes out, second-pass chunks; the times
+thread_local uint64_t g_inflate_info[4] = {0, 0, 0, 0};
+thread_local double g_inflate_ms[3] = {0.0, 0.0, 0.0};
+static int inflate_out(const InflateResult& z, uint32_t n, uint32_t* status, uint64_t* out_len, char** blob, size_t* blob_len,
+                       const uint64_t* len) {
+  char* b = (char*)std::malloc(std::max<size_t>(z.blob.size(), 1));
+  if (!b) return fail("out of memory");
+  if (!z.blob.empty()) std::memcpy(b, z.blob.data(), z.blob.size());
+  uint64_t members = 0, in = 0;
+  for (uint32_t c = 0; c < n; ++c) {
+    status[c] = z.status[c];
+    out_len[c] = z.off[c + 1] - z.off[c];
+    members += z.members[c];
+    in += len[c];
+  }
+  g_inflate_info[0] = members; g_inflate_info[1] = in; g_inflate_info[2] = z.blob.size(); g_inflate_info[3] = z.second_pass;
+  std::copy(z.ms, z.ms + 3, g_inflate_ms);
+  *blob = b;
+  *blob_len = z.blob.size();
+  return 0;
+}
+int rm_inflate(int device, uint32_t n, const char* const* data, const uint64_t* len, uint32_t* status,
+               uint64_t* out_len, char** blob, size_t* blob_len) {
+  if (!blob || !blob_len || (n && (!status || !out_len))) return fail("inflate: an output argument is NULL");
+  *blob = nullptr;
+  InflateResult z;
+  if (const int rc = guarded([&] { inflate_device(device, n, data, len, z); })) return rc;
+  return inflate_out(z, n, status, out_len, blob, blob_len, len);
+}
+int rm_inflate_host(uint32_t n, const char* const* data, const uint64_t* len, uint32_t* status,
+                    uint64_t* out_len, char** blob, size_t* blob_len) {
+  if (!blob || !blob_len || (n && (!status || !out_len))) return fail("inflate: an output argument is NULL");
+  *blob = nullptr;
+  InflateResult z;
+  if (const int rc = guarded([&] { inflate_host(n, data, len, z); })) return rc;
+  return inflate_out(z, n, status, out_len, blob, blob_len, len);
+}
+void rm_inflate_last(uint64_t info[4], double ms[3]) {
+  if (info) std::copy(g_inflate_info, g_inflate_info + 4, info);
+  if (ms) std::copy(g_inflate_ms, g_inflate_ms + 3, ms);
+}
+const char* rm_inflate_status_text(uint32_t status) { return inf::status_text(status); }
 
 void rm_default_tile_params(rm_tile_params* p) {
   p->quantisation = 3600; p->privacy = 2; p->source = "smpl_rprt"; p->mode = "auto";

@@ -768,6 +768,17 @@ class Matcher {
   void get_line_points(uint32_t* uuid, double* time, float* lon, float* lat, float* acc);   // input order
   void get_vehicles(uint32_t* chunk, uint64_t* off, uint32_t* len);   // name span per vehicle
   void lines_time(double ms[4]) const;   // upload, parse (+ host lines), ids, windows
+  // Gzip chunks (inflate.hip; DESIGN.md §3 rule 20): how parse_lines, run_lines and parse_messages
+  // read their chunks from now on.  0 plain (the default), 1 gzip, 2 gzip where a chunk begins
+  // 1f 8b.  A bad chunk throws "chunk <c>: gzip: <reason>" (the first in input order), or with
+  // skip_bad counts as empty.  The inflated text lives on the device only: get_text reads it back.
+  void set_input_coding(int coding, bool skip_bad);
+  uint32_t chunk_count() const;                // chunks of the last parse
+  void chunk_status(uint32_t* status) const;   // rule 20's status of every chunk of the last parse (0 for plain ones)
+  // chunks inflated, members, bytes in, bytes out, second-pass chunks, chunks inflated on the host
+  void inflate_info(uint64_t out[6]) const;
+  void inflate_time(double ms[3]) const;       // inflate (with the CRC), 0, gather
+  void get_text(uint32_t chunk, uint64_t off, uint64_t len, char* out);   // bytes of the last parse's text
   // vehicle index of every window of the last run_points (n_traces entries)
   void get_trace_uuid(uint32_t* out);
   // the batch the last run matched (after run_points: the windows built on the device)
@@ -873,6 +884,8 @@ class Matcher {
   PinBuf<uint32_t> hctl_;     // pinned host mirror of the control words
   StageBufs sb_;
   std::shared_ptr<LineState> ls_;
+  int input_coding_ = 0;      // rule 20 (set_input_coding)
+  bool skip_bad_chunks_ = false;
   bool from_points_ = false;
   uint32_t mode_mask_ = 0;   // travel modes of the batch (bit per Mode): which route balls K2 needs
   uint32_t turn_mask_ = 0;   // modes of the batch with a turn_penalty_factor > 0: turn rows, route_d

@@ -41,6 +41,8 @@
 
 #include "engine.hpp"
 #include "host_pool.hpp"
+#include "inflate.hpp"
+#include "inflate_core.hpp"
 
 namespace rm {
 
@@ -365,6 +367,13 @@ struct LineState {
   double tmin = 0.0, tmax = 0.0;
   double ms[4] = {0.0, 0.0, 0.0, 0.0};
   bool parsed = false;
+  // rule 20: the last call's gzip chunks
+  InflateJob job;
+  PartTimer gz_timer;                      // parts: gz_ms[0 .. 2]
+  std::vector<uint32_t> gz_status;         // per chunk
+  std::vector<std::vector<uint8_t>> gz_host;   // a chunk's inflated bytes where the host has them
+  uint64_t gz_info[6] = {0, 0, 0, 0, 0, 0};
+  double gz_ms[3] = {0.0, 0.0, 0.0};
   // the chunk holding text position `at`
   uint32_t chunk_of(uint64_t at) const {
     return (uint32_t)(std::upper_bound(chunk_base.begin(), chunk_base.end() - 1, at) - chunk_base.begin()) - 1u;
@@ -406,14 +415,83 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
   z.timer.harvest(nullptr);   // (pairs a call that threw left behind)
   // ---- the text: chunks end to end, each ending in '\n'
   z.chunk_base.assign(d.n_chunks + 1ull, 0);
+  for (uint32_t c = 0; c < d.n_chunks; ++c)
+    if (d.len[c] && !d.data[c]) throw std::runtime_error("line chunk is NULL");
+  // ---- rule 20: gzip chunks inflated, on the device (their bytes stay there: src null) or, for a
+  // call of few, on the host pool (then they are plain chunks from here on)
+  std::vector<const char*> src(d.data, d.data + d.n_chunks);
+  std::vector<uint64_t> slen(d.len, d.len + d.n_chunks);
+  std::vector<uint8_t> on_dev(d.n_chunks, 0), ends_nl(d.n_chunks, 0);
+  z.gz_status.assign(d.n_chunks, 0);
+  z.gz_host.clear();
+  z.gz_host.resize(d.n_chunks);
+  std::fill(z.gz_info, z.gz_info + 6, 0);
+  std::fill(z.gz_ms, z.gz_ms + 3, 0.0);
+  z.gz_timer.harvest(nullptr);
+  uint32_t n_gz = 0;
+  if (input_coding_)
+    for (uint32_t c = 0; c < d.n_chunks; ++c) {
+      const bool magic = d.len[c] >= 2 && (uint8_t)d.data[c][0] == 0x1f && (uint8_t)d.data[c][1] == 0x8b;
+      on_dev[c] = input_coding_ == 1 || magic;
+      n_gz += on_dev[c];
+    }
+  const std::vector<uint8_t> is_gz(on_dev);
+  if (n_gz) {
+    uint64_t members = 0;
+    if (n_gz < inflate_device_min_chunks()) {
+      std::vector<const char*> gd;
+      std::vector<uint64_t> gl;
+      std::vector<uint32_t> which;
+      for (uint32_t c = 0; c < d.n_chunks; ++c)
+        if (on_dev[c]) { gd.push_back(d.data[c]); gl.push_back(d.len[c]); which.push_back(c); on_dev[c] = 0; }
+      InflateResult r;
+      inflate_host(n_gz, gd.data(), gl.data(), r);
+      for (uint32_t k = 0; k < n_gz; ++k) {
+        const uint32_t c = which[k];
+        z.gz_status[c] = r.status[k];
+        z.gz_host[c].assign(r.blob.begin() + (ptrdiff_t)r.off[k], r.blob.begin() + (ptrdiff_t)r.off[k + 1]);
+        src[c] = (const char*)z.gz_host[c].data();
+        slen[c] = z.gz_host[c].size();
+        members += r.members[k];
+        z.gz_info[2] += d.len[c];
+      }
+      z.gz_info[5] = n_gz;
+    } else {
+      z.job.run(d.n_chunks, d.data, d.len, on_dev.data(), st, z.gz_timer);
+      for (uint32_t c = 0; c < d.n_chunks; ++c) {
+        if (!on_dev[c]) continue;
+        z.gz_status[c] = z.job.res[c].status;
+        src[c] = nullptr;
+        slen[c] = z.job.res[c].status == inf::kOk ? z.job.res[c].count : 0;
+        ends_nl[c] = z.job.res[c].last == (uint32_t)'\n';
+        members += z.job.res[c].members;
+      }
+      z.gz_info[2] = z.job.bytes_in;
+      z.gz_info[4] = z.job.second_pass;
+    }
+    z.gz_info[0] = n_gz;
+    z.gz_info[1] = members;
+    for (uint32_t c = 0; c < d.n_chunks; ++c) {
+      if (z.gz_status[c] == inf::kOk) continue;
+      if (!skip_bad_chunks_)
+        throw std::runtime_error("chunk " + std::to_string(c + 1) + ": gzip: " + inf::status_text(z.gz_status[c]));
+      slen[c] = 0;   // (a skipped chunk counts as empty)
+    }
+  }
+  for (uint32_t c = 0; c < d.n_chunks; ++c)
+    if (!on_dev[c]) ends_nl[c] = slen[c] && src[c][slen[c] - 1] == '\n';
   uint64_t N = 0;
   for (uint32_t c = 0; c < d.n_chunks; ++c) {
     z.chunk_base[c] = N;
-    if (d.len[c] && !d.data[c]) throw std::runtime_error("line chunk is NULL");
-    N += d.len[c];
-    if (d.len[c] && d.data[c][d.len[c] - 1] != '\n') ++N;
-    if (N >= (1ull << 32)) throw std::runtime_error("line input too large (the chunks of one call must stay under 2^32 bytes)");
+    N += slen[c];
+    if (slen[c] && !ends_nl[c]) ++N;
+    if (N >= (1ull << 32)) {
+      if (n_gz) throw std::runtime_error(std::string("gzip: ") + inf::status_text(inf::kTooLarge) + " (the chunks of one call must stay under 2^32 bytes)");
+      throw std::runtime_error("line input too large (the chunks of one call must stay under 2^32 bytes)");
+    }
   }
+  for (uint32_t c = 0; c < d.n_chunks; ++c)
+    if (is_gz[c]) z.gz_info[3] += slen[c];
   z.chunk_base[d.n_chunks] = N;
   std::fill(z.info, z.info + 7, 0);
   z.veh_off.clear();
@@ -426,13 +504,32 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
   uint8_t* text = z.text;
   RM_HIP(hipMemsetAsync(text, '\n', kLineFront, st));
   RM_HIP(hipMemsetAsync(text + kLineFront + N, 0, kLineTail, st));
+  std::vector<GatherItem> gather;
   for (uint32_t c = 0; c < d.n_chunks; ++c) {
-    if (!d.len[c]) continue;
+    if (!slen[c]) continue;
     uint8_t* at = text + kLineFront + z.chunk_base[c];
-    RM_HIP(hipMemcpyAsync(at, d.data[c], d.len[c], hipMemcpyHostToDevice, st));
-    if (d.data[c][d.len[c] - 1] != '\n') RM_HIP(hipMemsetAsync(at + d.len[c], '\n', 1, st));
+    if (on_dev[c]) { gather.push_back(GatherItem{z.job.item[c].out, slen[c], kLineFront + z.chunk_base[c], ends_nl[c] ? 0u : 1u, 0}); continue; }
+    RM_HIP(hipMemcpyAsync(at, src[c], slen[c], hipMemcpyHostToDevice, st));
+    if (!ends_nl[c]) RM_HIP(hipMemsetAsync(at + slen[c], '\n', 1, st));
   }
   z.timer.toc(st);
+  double gz_upload = 0.0;
+  if (n_gz) {   // (the chunks inflated on the device: one copy puts them where plain chunks are uploaded to)
+    z.job.gather(gather, text, st, z.gz_timer);
+    double gm[4] = {0.0, 0.0, 0.0, 0.0};
+    z.gz_timer.harvest(gm);
+    std::copy(gm, gm + 3, z.gz_ms);
+    gz_upload = gm[3];
+  }
+  // a chunk's bytes on the host: the caller's, or fetched from the device text (before any use from the pool)
+  auto host_chunk = [&](uint32_t c) -> const char* {
+    if (!src[c] && slen[c]) {
+      z.gz_host[c].resize(slen[c]);
+      RM_HIP(hipMemcpy(z.gz_host[c].data(), text + kLineFront + z.chunk_base[c], slen[c], hipMemcpyDeviceToHost));
+      src[c] = (const char*)z.gz_host[c].data();
+    }
+    return src[c];
+  };
   z.timer.tic(1, st);
   // ---- lines per window, each window's first line
   const uint32_t nwin = (uint32_t)((N + kLineWin - 1) / kLineWin);
@@ -496,6 +593,7 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
     if (hl.size() != H) throw std::runtime_error("line reader: host line count changed");
     std::vector<uint32_t> off(L);
     RM_HIP(hipMemcpy(off.data(), la.id_off, L * 4, hipMemcpyDeviceToHost));
+    for (const HostLine& h : hl) host_chunk(z.chunk_of(off[h.line]));
     HostPool& pool = HostPool::get();
     const size_t nt = std::max<size_t>(1, std::min<size_t>(pool.size(), H / 256u + 1u));
     pool.run(nt, [&](size_t t) {
@@ -503,8 +601,8 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
         HostLine& h = hl[i];
         const uint64_t at = off[h.line];
         const uint32_t c = z.chunk_of(at);
-        const uint8_t* b = (const uint8_t*)d.data[c] + (at - z.chunk_base[c]);
-        const uint8_t* ce = (const uint8_t*)d.data[c] + d.len[c];
+        const uint8_t* b = (const uint8_t*)src[c] + (at - z.chunk_base[c]);
+        const uint8_t* ce = (const uint8_t*)src[c] + slen[c];
         const uint8_t* nl = (const uint8_t*)std::memchr(b, '\n', (size_t)(ce - b));
         h.status = msg::generic_message(b, nl ? nl : ce, d.fmt, h.v, &h.why, pat);
         h.v.id_off += (uint32_t)at;
@@ -516,7 +614,7 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
       if (!d.strict && z.dropped.size() >= kMaxDropped) continue;
       const uint64_t at = off[h.line];
       const uint32_t c = z.chunk_of(at);
-      const char* b = d.data[c];
+      const char* b = src[c];
       const uint64_t line = 1 + (uint64_t)std::count(b, b + (at - z.chunk_base[c]), '\n');
       if (d.strict) throw std::runtime_error("chunk " + std::to_string(c + 1) + " line " + std::to_string(line) + ": " + h.why);
       z.dropped.push_back(DroppedMessage{c + 1, line, h.why});   // (its slot is patched to kBad: no point)
@@ -602,7 +700,7 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
     uint32_t c = 0;
     for (uint64_t k = 0; k < P; ++k) {
       while (off[k] >= z.chunk_base[c + 1]) ++c;   // points are in input order
-      const std::string_view name(d.data[c] + (off[k] - z.chunk_base[c]), len[k]);
+      const std::string_view name(host_chunk(c) + (off[k] - z.chunk_base[c]), len[k]);
       const auto it = table.emplace(name, (uint32_t)table.size());
       if (it.second) { z.veh_off.push_back(off[k]); z.veh_len.push_back(len[k]); }
       id[k] = it.first->second;
@@ -618,6 +716,7 @@ void Matcher::parse_text(const MessagesDesc& d, const tp::Pattern* pat) {
   z.timer.toc(st);
   RM_HIP(hipStreamSynchronize(st));
   z.timer.harvest(z.ms);
+  z.ms[0] += gz_upload;
   z.info[4] = z.veh_off.size();
   z.n_groups = (uint32_t)z.veh_off.size();
   z.parsed = true;
@@ -689,6 +788,45 @@ void Matcher::get_line_points(uint32_t* uuid, double* time, float* lon, float* l
   RM_HIP(hipMemcpy(lon, s.p_lon, P * 4, hipMemcpyDeviceToHost));
   RM_HIP(hipMemcpy(lat, s.p_lat, P * 4, hipMemcpyDeviceToHost));
   RM_HIP(hipMemcpy(acc, s.p_acc, P * 4, hipMemcpyDeviceToHost));
+}
+
+void Matcher::set_input_coding(int coding, bool skip_bad) {
+  if (coding < 0 || coding > 2) throw std::runtime_error("input coding must be 0 (plain), 1 (gzip) or 2 (by magic)");
+  input_coding_ = coding;
+  skip_bad_chunks_ = skip_bad;
+}
+
+uint32_t Matcher::chunk_count() const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  return (uint32_t)ls_->gz_status.size();
+}
+
+void Matcher::chunk_status(uint32_t* status) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  std::copy(ls_->gz_status.begin(), ls_->gz_status.end(), status);
+}
+
+void Matcher::inflate_info(uint64_t out[6]) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  std::copy(ls_->gz_info, ls_->gz_info + 6, out);
+}
+
+void Matcher::inflate_time(double ms[3]) const {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  std::copy(ls_->gz_ms, ls_->gz_ms + 3, ms);
+}
+
+void Matcher::get_text(uint32_t chunk, uint64_t off, uint64_t len, char* out) {
+  if (!ls_ || !ls_->parsed) throw std::runtime_error("no lines have been parsed");
+  const LineState& z = *ls_;
+  if (chunk + 1ull >= z.chunk_base.size()) throw std::runtime_error("get_text: no such chunk");
+  const uint64_t room = z.chunk_base[chunk + 1] - z.chunk_base[chunk];
+  if (off > room || len > room - off) throw std::runtime_error("get_text: the span leaves the chunk");
+  if (!len) return;
+  if (!out) throw std::runtime_error("get_text: out is NULL");
+  RM_HIP(hipSetDevice(eng_->device()));
+  RM_HIP(hipStreamSynchronize(stream_));
+  RM_HIP(hipMemcpy(out, z.text + kLineFront + z.chunk_base[chunk] + off, len, hipMemcpyDeviceToHost));
 }
 
 void Matcher::get_vehicles(uint32_t* chunk, uint64_t* off, uint32_t* len) {

@@ -289,6 +289,62 @@ def parse_lines_host(chunks, fmt=None):
                 info=dict(zip(LINES_INFO, (int(x) for x in info))))
 
 
+INPUT_CODINGS = ("plain", "gzip", "auto")
+INFLATE_INFO = ("members", "bytes_in", "bytes_out", "second_pass")
+
+
+def inflate_status_text(status):
+    return _lib.lib().rm_inflate_status_text(int(status)).decode()
+
+
+def _inflate(chunks, device):
+    views = _chunk_views(chunks)
+    n = len(views)
+    data = (C.c_void_p * max(n, 1))(*[v.ctypes.data if len(v) else None for v in views])
+    lens = (C.c_uint64 * max(n, 1))(*[len(v) for v in views])
+    status = np.zeros(n, np.uint32)
+    out_len = np.zeros(n, np.uint64)
+    blob, blen = C.c_void_p(), C.c_size_t()
+    L = _lib.lib()
+    if device is None:
+        _lib.check(L.rm_inflate_host(n, data, lens, status.ctypes.data, out_len.ctypes.data, C.byref(blob), C.byref(blen)))
+    else:
+        _lib.check(L.rm_inflate(int(device), n, data, lens, status.ctypes.data, out_len.ctypes.data, C.byref(blob),
+                                C.byref(blen)))
+    try:
+        flat = C.string_at(blob, blen.value)
+    finally:
+        L.rm_free(blob)
+    out, at = [], 0
+    for c in range(n):
+        m = int(out_len[c])
+        out.append(flat[at:at + m] if status[c] == 0 else None)
+        at += m
+    return out, [int(s) for s in status]
+
+
+def inflate(chunks, device=0):
+    """Gzip chunks (DESIGN.md §3 rule 20) inflated and checked on the GPU, a wave per chunk:
+    (list of bytes, None for a bad chunk; rule 20's status per chunk).  inflate_last() has the
+    call's counts and times."""
+    return _inflate(chunks, device)
+
+
+def inflate_host(chunks):
+    """The same decoder core on the host pool (no GPU)."""
+    return _inflate(chunks, None)
+
+
+def inflate_last():
+    """Of the calling thread's last inflate / inflate_host call (rm_inflate_last): members,
+    bytes_in, bytes_out, second_pass (chunks the device inflated twice: their slot was too small)
+    and ms (inflate with the CRC, 0, gather)."""
+    info = (C.c_uint64 * 4)()
+    ms = (C.c_double * 3)()
+    _lib.lib().rm_inflate_last(info, ms)
+    return dict(zip(INFLATE_INFO, (int(x) for x in info)), ms=tuple(float(x) for x in ms))
+
+
 MESSAGES_INFO = LINES_INFO + ("dropped",)
 MESSAGE_KEYS = ("id", "lat", "lon", "time", "accuracy")
 
@@ -544,14 +600,55 @@ class BatchMatcher:
         _lib.check(_lib.lib().rm_runner_lines_info(self._h, out))
         return dict(zip(LINES_INFO, (int(x) for x in out)))
 
-    def vehicle_names(self, chunks):
-        """Vehicle id strings of the last run_lines / parse_lines over `chunks`, by vehicle index."""
+    def vehicle_names(self, chunks=None):
+        """Vehicle id strings of the last run_lines / parse_lines over `chunks`, by vehicle index.
+        Without chunks the names are read back from the device text (gzip chunks: the caller does
+        not hold the inflated text)."""
         n = self.lines_info()["vehicles"]
         chunk = np.empty(n, np.uint32)
         off = np.empty(n, np.uint64)
         ln = np.empty(n, np.uint32)
         _lib.check(_lib.lib().rm_runner_get_vehicles(self._h, chunk.ctypes.data, off.ctypes.data, ln.ctypes.data))
-        return _names(chunks, chunk, off, ln)
+        if chunks is not None:
+            return _names(chunks, chunk, off, ln)
+        return [self.text(c, o, m).decode("utf-8", "replace") for c, o, m in zip(chunk, off, ln)]
+
+    def text(self, chunk, off, length):
+        """bytes [off, off + length) of chunk `chunk` of the last parse's text, from the device"""
+        buf = C.create_string_buffer(max(int(length), 1))
+        _lib.check(_lib.lib().rm_runner_get_text(self._h, int(chunk), int(off), int(length), buf))
+        return buf.raw[:int(length)]
+
+    def set_input_coding(self, coding="plain", skip_bad=False):
+        """How run_lines, parse_lines and a VehicleSessions' push_messages over this matcher read
+        their chunks from now on (DESIGN.md rule 20): "plain" (the default), "gzip" (every chunk
+        is a sequence of gzip members, inflated and checked on the device), or "auto" (gzip where
+        a chunk begins 1f 8b).  A bad chunk raises "chunk <c>: gzip: <reason>"; with skip_bad it
+        counts as empty and chunk_status() names it."""
+        _lib.check(_lib.lib().rm_runner_set_input_coding(self._h, INPUT_CODINGS.index(coding), 1 if skip_bad else 0))
+        return self
+
+    def chunk_status(self):
+        """Rule 20's status of every chunk of this matcher's last parse (0: ok or plain), whichever
+        call made it: run_lines, parse_lines or a VehicleSessions' push_messages."""
+        k = C.c_uint32(0)
+        _lib.check(_lib.lib().rm_runner_chunk_count(self._h, C.byref(k)))
+        n = int(k.value)
+        out = np.zeros(max(n, 1), np.uint32)
+        _lib.check(_lib.lib().rm_runner_chunk_status(self._h, out.ctypes.data))
+        return [int(s) for s in out[:n]]
+
+    def inflate_info(self):
+        out = (C.c_uint64 * 6)()
+        _lib.check(_lib.lib().rm_runner_inflate_info(self._h, out))
+        return dict(zip(("chunks", "members", "bytes_in", "bytes_out", "second_pass", "host_chunks"), (int(x) for x in out)))
+
+    def inflate_ms(self):
+        """Times (ms) of the last parse's gzip parts: inflate (with the CRC), crc (0: it is computed
+        as the window is flushed), gather.  The compressed upload is lines_ms()'s upload."""
+        out = (C.c_double * 3)()
+        _lib.check(_lib.lib().rm_runner_inflate_time(self._h, out))
+        return dict(zip(("inflate", "crc", "gather"), (float(x) for x in out)))
 
     def lines_ms(self):
         """Times (ms) of the last run_lines' parts: upload, parse (+ host lines), ids, windows."""
